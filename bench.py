@@ -7,10 +7,18 @@
 A "step" is one full CQL training step over one batch of B=4096 transitions per GPU (sample, window gather, encoder,
 full-catalog Q-head LSE + argmax, double-Q TD target, CQL loss, backward, [RCCL gradient all-reduce], Adam + Polyak).
 Weak scaling: per-GPU batch fixed, users sharded by rank, no data-path collective besides the gradient all-reduce.
-`value` = (N * K steps of 4096 transitions) / max-over-ranks time, inputs resident in HBM.  After the timed training
-region the all-users top-K pass (K=10, seen items filtered) is timed on a user block and reported in `topk`.
+`value` = (N * K steps of 4096 transitions) / max-over-ranks time, inputs resident in HBM.
 
-The oracle (oracle/) is used ONLY for the cpu_baseline leg (rank 0, N=1), never in the measured path."""
+A plain run does only that: set-up, W warm-up steps, the K timed steps, and the JSON line.  `--full` adds what else the
+benchmark measures: after the timed training region the all-users top-K pass (K=10, seen items filtered), timed on a
+user block and reported in `topk`; the per-kernel durations and rooflines (HIP events around the reported kernel inside
+the timed region, then a serialised pass); and, for N=1, the CPU baseline and the parity check against the oracle.
+`--no-topk`, `--no-prof` and `--no-cpu-baseline` switch single legs of `--full` off.
+
+`--dump-outputs DIR` writes what the timed steps handed back after the last of them as float32 .npy files
+(see dump_outputs); the inputs are seeded, so two builds run with the same arguments can be compared file by file.
+
+The oracle (oracle/) is used ONLY for the cpu_baseline leg (rank 0, N=1, --full), never in the measured path."""
 from __future__ import annotations
 
 import argparse
@@ -121,7 +129,17 @@ def parse():
                          "ranks agree on (recorded in config.dp_variant / dp_probe)")
     ap.add_argument("--serial", action="store_true",
                     help="no intra-step concurrency for the whole run (per-kernel durations then match rocprofv3)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also the top-K pass, per-kernel durations and rooflines, CPU baseline and parity check "
+                         "(off: only the timed training steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the losses and parameters of the last timed step to DIR/<name>.npy (float32)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:
+        args.no_topk = args.no_prof = args.no_cpu_baseline = True
+    return args
 
 
 def cpu_baseline(cfg, off, items, rew, budget_s=20.0):
@@ -209,6 +227,27 @@ def hbm_roofline(alg_bytes, ms, table_bytes, **extra):
          "big_table_evidence": "profiles/r02_hbm_traffic.json"}
     r.update(extra)
     return r
+
+
+DUMP_TABLE_BYTES = 48 << 20     # --dump-outputs: the four (sampled) item tables together; all files stay below 64 MB
+
+
+def dump_outputs(out_dir, core, losses):
+    """--dump-outputs DIR: what a caller of the timed path holds after its last step, as float32 .npy files:
+    `losses` (this rank's loss of every timed step, the last one last) and the model, one file per parameter segment
+    of the flat layout for the fp32 parameters (`theta_<segment>`) and the Polyak target (`target_<segment>`).
+    E_in / E_out rows beyond the byte budget are sampled: the same rows in every run (a randperm seeded with 0, sorted)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "losses.npy"), losses.detach().cpu().numpy().astype(np.float32))
+    keep = DUMP_TABLE_BYTES // (4 * core.hyper.d * 4)
+    for prefix, flat in (("theta", core.theta), ("target", core.target)):
+        for name in ("E_in", "E_out", "b_out", "W1", "b1", "W2", "b2"):
+            seg = core.segment(flat, name)
+            if seg.dim() == 2 and seg.shape[0] > keep:
+                rows = torch.randperm(seg.shape[0], generator=torch.Generator().manual_seed(0))[:keep].sort().values
+                seg = seg.index_select(0, rows.to(seg.device))
+            np.save(os.path.join(out_dir, f"{prefix}_{name}.npy"), seg.cpu().numpy().astype(np.float32))
 
 
 
@@ -333,6 +372,10 @@ def main():
     host_issue_ms_per_step = 1e3 * issue_s[0] / max(args.steps, 1)
     barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs:
+        core.sync_full_state()          # the row-sharded optimizer's masters to every rank (a collective; else a no-op)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, core, loss_buf[args.warmup: args.warmup + args.steps])
     phases_timed = N.prof_read() if not args.no_prof else {}
     N.check(lib.cqlrec_prof_enable(0), "prof_enable")
     N.check(lib.cqlrec_prof_select(0xFFFFFFFF), "prof_select")

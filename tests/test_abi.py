@@ -102,12 +102,16 @@ def test_host_layer_under_address_sanitizer():
     """SURVEY 5 / VERDICT r2 missing #6: the host C++ side of the library (argument checks, error plumbing, size, split and
     layout arithmetic of every entry point) built with -fsanitize=address and driven without a GPU
     (replay_cql_amd/build.py::build_asan, tests/asan/host_driver.cpp: host-only objects, no device code -- GPU ASan is
-    not available on the pool).  Pass = exit code 0, the driver's "ok", no AddressSanitizer report."""
+    not used).  Pass = exit code 0, the driver's "ok", no AddressSanitizer report.  Leaks made inside
+    the ROCm runtime itself, on a machine with a GPU, are suppressed (tests/asan/lsan.supp); leaks of our own code are not."""
     import subprocess
     from replay_cql_amd import build as B
     exe = B.build_asan()
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:halt_on_error=1:verbosity=1", HIP_VISIBLE_DEVICES="")
+    supp = ROOT / "tests" / "asan" / "lsan.supp"
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:halt_on_error=1:verbosity=1", HIP_VISIBLE_DEVICES="",
+               LSAN_OPTIONS=f"suppressions={supp}:print_suppressions=1")
     r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300, env=env)
     assert "AddressSanitizer Init done" in r.stderr, "the driver is not an ASan build"
+    assert "LeakSanitizer: checking for leaks" in r.stderr, "the leak check did not run"
     assert r.returncode == 0 and "host_driver: ok" in r.stdout, r.stderr[-3000:]
     assert "ERROR: AddressSanitizer" not in r.stderr and "ERROR: LeakSanitizer" not in r.stderr, r.stderr[-3000:]

@@ -7,15 +7,15 @@ out=gpurun_out/r03
 mkdir -p $out
 export TMPDIR=/tmp
 echo "[r03] bench cfg3 (driver flags and defaults)"
-python bench.py --steps 20 --warmup 5 > $out/bench_cfg3_20_5.json 2> $out/bench_cfg3_20_5.err || exit 1
-python bench.py > $out/bench_cfg3.json 2> $out/bench_cfg3.err || exit 1
+python bench.py --full --steps 20 --warmup 5 > $out/bench_cfg3_20_5.json 2> $out/bench_cfg3_20_5.err || exit 1
+python bench.py --full > $out/bench_cfg3.json 2> $out/bench_cfg3.err || exit 1
 echo "[r03] bench other configs"
 for c in cfg1 cfg2 cfg5shard; do
-  python bench.py --config $c --steps 50 --warmup 5 > $out/bench_$c.json 2> $out/bench_$c.err || exit 1
+  python bench.py --full --config $c --steps 50 --warmup 5 > $out/bench_$c.json 2> $out/bench_$c.err || exit 1
 done
-python bench.py --batch 16384 --steps 50 --warmup 10 --no-topk --no-cpu-baseline > $out/bench_cfg3_B16384.json 2> $out/bench_B16384.err || exit 1
+python bench.py --full --batch 16384 --steps 50 --warmup 10 --no-topk --no-cpu-baseline > $out/bench_cfg3_B16384.json 2> $out/bench_B16384.err || exit 1
 echo "[r03] rocprofv3 kernel stats of the bench command"
-(cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $root/$out/kt -- python3 $root/bench.py --steps 50 --warmup 10 --no-cpu-baseline) > $out/bench_under_rocprof.json 2> $out/kt.err || { tail -5 $out/kt.err; exit 1; }
+(cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $root/$out/kt -- python3 $root/bench.py --full --steps 50 --warmup 10 --no-cpu-baseline) > $out/bench_under_rocprof.json 2> $out/kt.err || { tail -5 $out/kt.err; exit 1; }
 cp $(find $out/kt -name "*kernel_stats.csv" | head -1) $out/kernel_stats.csv
 rm -rf $out/kt
 echo "[r03] PMC passes, d = 128 (cfg3 shape)"
