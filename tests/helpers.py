@@ -78,6 +78,205 @@ def qhead_inputs(rows, Nn, d, dyadic, seed):
     return O.bf16_round(H), O.bf16_round(E), b
 
 
+# ---- row-wise check of the softmax part of the Q-head gradients ------------------------------------------------------
+# K of the row check.  tests/test_qhead_grad_rows_cpu.py is what justifies it (GPU-like roundings accepted, every listed
+# fault rejected): change it there or nowhere.
+ROWS_K = 4.0
+ROWS_TINY = 1e-30             # absolute floor: rows whose every probability underflows fp32
+_U32 = 2.0 ** -24             # fp32 unit roundoff
+_BF16_SD = 2.0 ** -9          # standard deviation of the relative bf16 (RNE) rounding error of one P element
+_T_SHIFT = 2.0 ** 40          # P is scaled by this before squaring in fp32: P^2 of P down to 1e-31 stays normal
+
+
+class SoftmaxGradRef:
+    """Dense softmax term of the Q-head gradients in float64 and its rounding-noise scale, UNSCALED (times `scale` gives
+    the gradient).  Built by softmax_grad_reference; a test that checks several outputs of the same operands reuses it."""
+
+    def __init__(self, scale, n_states, n_items):
+        self.scale, self.n_states, self.n_items = float(scale), n_states, n_items
+        self.dE = self.tE = self.cE = self.db = self.tb = self.dH = self.tH = self.cH = None
+        self.arg = 0.0
+
+
+def softmax_grad_reference(hb, lse, E_b, b_out, scale, items=True, states=True, chunk=None) -> SoftmaxGradRef:
+    """P = exp(hb E_b^T + b_out - lse) in float64 from the kernels' own bf16 operands and the kernels' own lse, one item
+    chunk at a time (B x chunk float64 score block: 64 MB), and per output element
+        dense        dE[j] = sum_b P[b,j] hb[b],   db[j] = sum_b P[b,j],   dH[b] = sum_j P[b,j] E_b[j]
+        t            sum of the squared terms (P x)^2, times 2^80         } float32: they only set
+        c            sum of (bf16(P) - P) x, P rounded at the true scale  } the tolerance
+    See softmax_grad_rows for how t becomes the noise scale."""
+    H = np.asarray(hb, dtype=np.float32).astype(np.float64)
+    E = np.asarray(E_b, dtype=np.float32)
+    bo = np.asarray(b_out, dtype=np.float64)
+    ls = np.asarray(lse, dtype=np.float64)
+    B, d = H.shape
+    Nn = E.shape[0]
+    ref = SoftmaxGradRef(scale, B, Nn)
+    if chunk is None:
+        chunk = max(256, (1 << 23) // B // 256 * 256)
+    H2 = (H * H).astype(np.float32)
+    H32 = H.astype(np.float32)
+    if items:
+        ref.dE, ref.tE, ref.cE = np.zeros((Nn, d)), np.zeros((Nn, d), np.float32), np.zeros((Nn, d), np.float32)
+        ref.db, ref.tb = np.zeros(Nn), np.zeros(Nn)
+    if states:
+        ref.dH, ref.tH, ref.cH = np.zeros((B, d)), np.zeros((B, d), np.float32), np.zeros((B, d), np.float32)
+    amax = 0.0
+    for lo in range(0, Nn, chunk):
+        hi = min(Nn, lo + chunk)
+        Ec = E[lo:hi].astype(np.float64)
+        Z = H @ Ec.T
+        Z += bo[lo:hi]
+        amax = max(amax, float(np.abs(Z).max()))
+        Z -= ls[:, None]
+        P = np.exp(Z, out=Z)
+        Ps = P * _T_SHIFT
+        P2 = (Ps * Ps).astype(np.float32)
+        P32 = P.astype(np.float32)
+        u = P32.view(np.uint32)
+        Cd = ((u + np.uint32(0x7FFF) + ((u >> 16) & np.uint32(1))) & np.uint32(0xFFFF0000)).view(np.float32) - P32
+        if items:
+            ref.dE[lo:hi] = P.T @ H
+            ref.tE[lo:hi] = P2.T @ H2
+            ref.cE[lo:hi] = Cd.T @ H32
+            ref.db[lo:hi] = P.sum(0)
+            ref.tb[lo:hi] = P2.sum(0, dtype=np.float64)
+        if states:
+            ref.dH += P @ Ec
+            ref.tH += P2 @ (Ec * Ec).astype(np.float32)
+            ref.cH += Cd @ E[lo:hi]
+        del Z, P, Ps, P2, P32, Cd
+    ref.arg = amax + float(np.abs(ls).max())
+    return ref
+
+
+def _fp32_coef(n_terms, arg):
+    # relative fp32 error of a sum of n_terms softmax terms (see softmax_grad_rows): accumulation + exponent argument
+    return _U32 * (np.sqrt(n_terms) + 2.0 * arg + 4.0)
+
+
+def _row_verdict(name, err, sig, K, group_sizes, out, offset=0):
+    """err, sig: [rows, width] (or [rows]) of rows offset, offset + 1, ...  Keeps the worst ratio in out[name]; returns
+    the failure line (empty list: every row passes)."""
+    err = err.reshape(err.shape[0], -1)
+    sig = sig.reshape(sig.shape[0], -1)
+    en = np.sqrt(np.einsum("ij,ij->i", err, err))
+    sn = np.sqrt(np.einsum("ij,ij->i", sig, sig))
+    ratio = en / (sn + ROWS_TINY / K)
+    out[name] = max(out.get(name, 0.0), float(ratio.max(initial=0.0)))
+    bad = np.nonzero(en > K * sn + ROWS_TINY)[0]
+    if bad.size == 0:
+        return []
+    worst = bad[np.argsort(-ratio[bad])][:6]
+    rows = ", ".join(f"{offset + int(r)} (" + " ".join(f"/{g}:{(offset + int(r)) // g}" for g in group_sizes) +
+                     f" err/sigma {ratio[r]:.3g})" for r in worst)
+    return [f"{name}: {bad.size} of {err.shape[0]} rows over K = {K} sigma; worst: {rows}"]
+
+
+def softmax_grad_rows(hb, lse, E_b, b_out, scale, g_E_out=None, g_b_out=None, dH=None, coef=None, act=None,
+                      ref=None, K=ROWS_K, block=16384):
+    """Row-by-row check of the DENSE (softmax) term of the Q-head gradients that the kernels output:
+        g_E_out[j] = scale sum_b bf16(P[b,j]) hb[b]   (+ sum_{b: act[b]=j} coef[b] hb[b])
+        g_b_out[j] = scale sum_b P[b,j]               (+ sum_{b: act[b]=j} coef[b])
+        dH[b]      = scale sum_j bf16(P[b,j]) E_b[j]  (+ coef[b] E_b[act[b]])
+    with P = exp(hb E_b^T + b_out - lse).  Every item row of g_E_out / g_b_out and every state row of dH is compared
+    on its own, so a fault in a few rows cannot hide under the norm of the whole tensor (where the one-hot term
+    dominates).  With (coef, act) the one-hot term is subtracted first, in float64.  Raises AssertionError naming the
+    worst rows (with their 256- and 128-item group / 64- and 32-state stage indices); returns {output: worst err/sigma}.
+
+    Noise model, per output element y = scale sum_k P_k x_k (k: states for the item side, items for dH; x = hb or E_b):
+    * bf16 rounding of P.  The kernels round P to bf16 (RNE) before the product MFMA: qde2 / qde3 / qde_kernel and the
+      QM_BWD_* modes of the skeleton at the true scale (exp(S + b - lse)); the fused forward (qfwd2 / qfwd3 and QM_LSE_DH)
+      relative to a reference m of its own (exp(S + b - m), a per-slice maximum or a running one), rescaled later by
+      exp(m - lse).  bf16 keeps its relative precision at any scale in the fp32 exponent range, so in both cases
+      bf16(P) = P (1 + e) with |e| <= 2^-8 and e spread over the ulp: standard deviation ~2^-9 of the value (between
+      2^-9.8 and 2^-8.8 depending on the position in the binade).  Where the P_k of a sum are spread over many bf16
+      ulps, the e_k are independent: 2^-9 sqrt(sum_k (P_k x_k)^2).  Where they are not -- P[b, j] of one item is
+      nearly the same for every state when the item's scores hardly depend on the state (small embeddings, as at
+      initialisation) -- the e_k are nearly EQUAL and add up coherently, to about e |y|: the random term misses that by a
+      factor up to sqrt(n).  The coherent part is taken from the rounding at the true scale, computed exactly:
+      c = sum_k (bf16(P_k) - P_k) x_k.  (At the true scale that is what the kernel's rounding gives, up to rare flips of
+      elements within the fp32 error of a rounding midpoint; at a shifted scale the kernel's e_k differ from those of c
+      but are random to the same degree.)  So
+          sigma_bf16 = 2^-9 sqrt(sum_k (P_k x_k)^2) + |c|.
+      g_b_out has no such term: every kernel sums the fp32 P, before the conversion.
+    * fp32 arithmetic.  (a) The sums: an fp32 chain of n terms with partial sums s_i errs by about
+      u sqrt(sum_i s_i^2) <= u sqrt(n) (|y| + sqrt(sum_k (P_k x_k)^2)) (coherent part + random-walk part; u = 2^-24);
+      slabs, cut ranges and MFMA blocks only shorten the chains.  (b) The exponent: P is exp2 of an fp32 argument
+      (S + b) log2e - lse log2e formed from fp32 roundings of magnitude <= `arg` (the largest |S + b| plus the largest
+      |lse|; for qde2 / qde3 the -lse log2e of the ABI is converted back to natural units, for the fused forward the
+      weights exp(m - lse) add one more such argument), and v_exp_f32 adds ~1 ulp: relative P error <= u (2 arg + 4),
+      bounded like (a).  Together
+          sigma_fp32 = u (sqrt(n) + 2 arg + 4) (|y| + sqrt(sum_k (P_k x_k)^2)).
+    * one-hot subtraction: the kernel's fp32 total was rounded after each of the cnt one-hot additions (and the final
+      store): u (cnt + 2) (sum |one-hot terms| + |y|).
+    The check is ||err_row|| <= K ||sigma_row|| + 1e-30 with sigma = scale (sigma_bf16 + sigma_fp32) (+ one-hot term).
+    (A coherent sum at a shifted scale whose true-scale rounding happens to cancel, |c| ~ 0, is not covered: it needs
+    a state whose P[b, :] all sit within one bf16 ulp of each other, which the bias spread of every case here rules out.)
+    The reference shares the kernels' bf16 operands and lse, so nothing else separates the two."""
+    if ref is None:
+        ref = softmax_grad_reference(hb, lse, E_b, b_out, scale, items=g_E_out is not None or g_b_out is not None,
+                                     states=dH is not None)
+    sc = ref.scale
+    B, Nn = ref.n_states, ref.n_items
+    H = np.asarray(hb, dtype=np.float32).astype(np.float64)
+    E = np.asarray(E_b, dtype=np.float32)
+    if coef is not None:
+        coef = np.asarray(coef, dtype=np.float32).astype(np.float64)
+        act = np.asarray(act, dtype=np.int64)
+        ua, inv = np.unique(act, return_inverse=True)
+        cnt = np.bincount(inv, minlength=ua.size)
+    report, fails = {}, []
+    if g_E_out is not None:
+        c_item = _fp32_coef(B, ref.arg)
+        got = np.array(g_E_out, dtype=np.float64).reshape(Nn, -1)
+        extra = None
+        if coef is not None:
+            oh = np.zeros((ua.size, H.shape[1]))
+            oha = np.zeros_like(oh)
+            np.add.at(oh, inv, coef[:, None] * H)
+            np.add.at(oha, inv, np.abs(coef[:, None] * H))
+            got[ua] -= oh
+            extra = (ua, cnt, oha)
+        for lo in range(0, Nn, block):
+            hi = min(Nn, lo + block)
+            y = sc * ref.dE[lo:hi]
+            t = sc / _T_SHIFT * np.sqrt(ref.tE[lo:hi].astype(np.float64))
+            sig = _BF16_SD * t + sc * np.abs(ref.cE[lo:hi]) + c_item * (np.abs(y) + t)
+            if extra is not None:
+                m = (extra[0] >= lo) & (extra[0] < hi)
+                r = extra[0][m] - lo
+                sig[r] += _U32 * (extra[1][m] + 2)[:, None] * (extra[2][m] + np.abs(y[r]))
+            fails += _row_verdict("g_E_out", got[lo:hi] - y, sig, K, (256, 128), report, lo)
+    if g_b_out is not None:
+        c_item = _fp32_coef(B, ref.arg)
+        got = np.array(g_b_out, dtype=np.float64).reshape(Nn)
+        y = sc * ref.db
+        sig = c_item * (np.abs(y) + sc / _T_SHIFT * np.sqrt(ref.tb))
+        if coef is not None:
+            oh = np.zeros(ua.size)
+            oha = np.zeros(ua.size)
+            np.add.at(oh, inv, coef)
+            np.add.at(oha, inv, np.abs(coef))
+            got[ua] -= oh
+            sig[ua] += _U32 * (cnt + 2) * (oha + np.abs(y[ua]))
+        fails += _row_verdict("g_b_out", got - y, sig, K, (256, 128), report)
+    if dH is not None:
+        c_state = _fp32_coef(Nn, ref.arg)
+        got = np.array(dH, dtype=np.float64).reshape(B, -1)
+        y = sc * ref.dH
+        t = sc / _T_SHIFT * np.sqrt(ref.tH.astype(np.float64))
+        sig = _BF16_SD * t + sc * np.abs(ref.cH) + c_state * (np.abs(y) + t)
+        if coef is not None:
+            oh = coef[:, None] * E[act].astype(np.float64)
+            got -= oh
+            sig += _U32 * 2.0 * (np.abs(oh) + np.abs(y))
+        fails += _row_verdict("dH", got - y, sig, K, (64, 32), report)
+    if fails:
+        raise AssertionError("softmax gradient rows off: " + "; ".join(fails))
+    return report
+
+
 def topk_rule_violations(idx, val, cnt, Q, k, set_tol=1e-4, val_tol=1e-3):
     """P3 for a block of top-k lists against the reference score matrix Q (rows = the same users, inadmissible items at
     -inf), PER ROW: the count of admissible items, descending order, every reported score within val_tol of the

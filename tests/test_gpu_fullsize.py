@@ -15,8 +15,8 @@ from replay_cql_amd import _native as N
 from replay_cql_amd.core import CQLCore, CQLHyper
 from replay_cql_amd.data import synth_log_device
 
-from helpers import (DEV, bf16_dev, bf16_to_np, dev, ptr, qhead_inputs, rel_err, stream, sync, topk_case,
-                     ws_bytes_tensor)
+from helpers import (DEV, bf16_dev, bf16_to_np, dev, ptr, qhead_inputs, rel_err, softmax_grad_rows, stream, sync,
+                     topk_case, ws_bytes_tensor)
 
 pytestmark = pytest.mark.gpu
 
@@ -90,6 +90,13 @@ def test_published_shape_step_matches_oracle(name, users_total, Nn, d, B, L, sha
     for nm in SEGS:
         mask[lay.off[nm]: lay.off[nm] + int(np.prod(lay.shape(nm)))] = False
     assert np.all(g[mask] == 0) and np.all(lay.view(g, "E_in")[Nn] == 0)      # padding / PAD row: no gradient
+    # the softmax part of the Q-head gradients row by row (at these shapes it is 2-9 % of the g_E_out norm and < 1 % of
+    # the dH norm: the normwise bounds above cannot see it), from the step's own states, lse, coef and actions
+    rep = softmax_grad_rows(bf16_to_np(v["hb_s"]), v["lse"].cpu().numpy(), lay.view(O.shadow(m.theta), "E_out"),
+                            lay.view(m.theta, "b_out"), np.float32(1.0 / B), g_E_out=lay.view(g, "E_out"),
+                            g_b_out=lay.view(g, "b_out"), dH=v["dH"].cpu().numpy(), coef=v["coef"].cpu().numpy(),
+                            act=v["act"].cpu().numpy())
+    print(f"ROWCHECK step {name} " + " ".join(f"{k}={x:.3f}" for k, x in rep.items()))
     # ---- Adam + Polyak
     core.apply_update()
     with np.errstate(all="ignore"):

@@ -6,7 +6,7 @@ import torch
 from oracle import cql_oracle as O
 from replay_cql_amd.core import CQLCore, CQLHyper
 
-from helpers import DEV, bf16_to_np, rel_err, small_log
+from helpers import DEV, bf16_to_np, rel_err, small_log, softmax_grad_rows
 
 pytestmark = pytest.mark.gpu
 
@@ -66,6 +66,13 @@ def test_step_intermediates_and_grads(U, Nn, d, B, L):
     for nm in ("E_in", "E_out", "b_out", "W1", "b1", "W2", "b2"):
         mask[lay.off[nm]: lay.off[nm] + int(np.prod(lay.shape(nm)))] = False
     assert np.all(g[mask] == 0) and np.all(lay.view(g, "E_in")[Nn] == 0)
+    # the softmax part of the Q-head gradients row by row, from the step's own states, lse, coef and actions (the
+    # one-hot term dominates the norms above)
+    rep = softmax_grad_rows(bf16_to_np(v["hb_s"]), v["lse"].cpu().numpy(), lay.view(O.shadow(m.theta), "E_out"),
+                            lay.view(m.theta, "b_out"), np.float32(1.0 / B), g_E_out=lay.view(g, "E_out"),
+                            g_b_out=lay.view(g, "b_out"), dH=v["dH"].cpu().numpy(), coef=v["coef"].cpu().numpy(),
+                            act=v["act"].cpu().numpy())
+    print(f"ROWCHECK step B={B} N={Nn} d={d} " + " ".join(f"{k}={x:.3f}" for k, x in rep.items()))
 
 
 def test_dyadic_forward_bit_exact():
@@ -101,11 +108,8 @@ def test_training_trajectory(U, Nn, d, B, L, steps):
     assert np.array_equal(bf16_to_np(core.theta_b), O.bf16_round(th))
 
 
-def test_pipelined_steps_match_step_by_step():
-    """cqlrec_train_steps (Adam halves under the backward, next prologue under the item-side Adam, double-buffered
-    step vectors) computes the same steps as fwd_bwd + update one at a time in strict program order."""
+def _pipelined_vs_step_by_step(U, Nn, d, B, L, steps):
     from replay_cql_amd import _native as N
-    U, Nn, d, B, L, steps = 300, 1000, 128, 256, 8, 7
     _, a, _ = _make(U, Nn, d, B, L)
     _, b, _ = _make(U, Nn, d, B, L)
     la = torch.zeros(steps, device=DEV)
@@ -132,6 +136,26 @@ def test_pipelined_steps_match_step_by_step():
     v = a.views(steps - 1)
     pos = O.sample_positions(11, steps - 1, 0, B, int(a._csr[0][-1]))
     assert np.array_equal(v["tpos"].cpu().numpy(), O.positions_to_transitions(pos, a._csr[0].cpu().numpy())[1])
+
+
+def test_pipelined_steps_match_step_by_step():
+    """cqlrec_train_steps (Adam halves under the backward, next prologue under the item-side Adam, double-buffered
+    step vectors) computes the same steps as fwd_bwd + update one at a time in strict program order."""
+    _pipelined_vs_step_by_step(300, 1000, 128, 256, 8, 7)
+
+
+# More shapes of the same comparison.  The pipelined driver adds the cut pieces of the item-side kernel inside Adam
+# (CqlAdamFix); step by step, cql_qde_fixup_deferred adds them to the gradient, which the row checks of
+# test_step_intermediates_and_grads / test_published_shape_step_matches_oracle hold to the dense reference.  Bit
+# equality here carries that guarantee over to the Adam-fused fix-up.  (W = G x T stage-units, grid = min(W, 256).)
+#   U    N      d    B     form             G x T = W       cut
+#   300  5003   256  256   qde3             40 x 8 = 320    yes
+#   300  2000   64   128   qde_kernel<64>   8 x 2 = 16      no
+#   300  20011  128  1024  qde2             79 x 16 = 1264  yes (stream-K)
+@pytest.mark.parametrize("U,Nn,d,B,L,steps", [(300, 5003, 256, 256, 8, 5), (300, 2000, 64, 128, 8, 5),
+                                               (300, 20011, 128, 1024, 8, 5)])
+def test_pipelined_steps_match_step_by_step_more_shapes(U, Nn, d, B, L, steps):
+    _pipelined_vs_step_by_step(U, Nn, d, B, L, steps)
 
 
 @pytest.mark.parametrize("U,Nn,d,B,L", [(300, 1000, 128, 256, 8), (200, 66000, 64, 128, 6),
