@@ -865,20 +865,10 @@ extern "C" int cqlrec_adam_ema(float* theta, float* grads, float* m, float* v, f
   const int64_t n4 = n / 4;
   int blocks = (int)((n4 + 255) / 256);
   if (blocks > 8192) blocks = 8192;
-  static int nt = -1;
-  if (nt < 0) {
-    const char* e = getenv("CQL_ADAM_NT");
-    nt = (e && *e == '0') ? 0 : 1;
-  }
   CqlProfScope prof(CQLREC_PH_ADAM, (hipStream_t)stream);
-  if (nt)
-    hipLaunchKernelGGL(adam_ema_kernel<true>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (float4*)theta,
-                       (float4*)grads, (float4*)m, (float4*)v, (float4*)target, (uint2*)theta_b, (uint2*)target_b, n4,
-                       step_size, sqrt_bc2, beta1, beta2, eps, tau, zero_grads);
-  else
-    hipLaunchKernelGGL(adam_ema_kernel<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (float4*)theta,
-                       (float4*)grads, (float4*)m, (float4*)v, (float4*)target, (uint2*)theta_b, (uint2*)target_b, n4,
-                       step_size, sqrt_bc2, beta1, beta2, eps, tau, zero_grads);
+  hipLaunchKernelGGL(adam_ema_kernel<true>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (float4*)theta,
+                     (float4*)grads, (float4*)m, (float4*)v, (float4*)target, (uint2*)theta_b, (uint2*)target_b, n4,
+                     step_size, sqrt_bc2, beta1, beta2, eps, tau, zero_grads);
   CQL_LAUNCH_CHECK("adam_ema");
   return CQLREC_OK;
 }

@@ -1,5 +1,5 @@
 // Full-catalog Q-head on bf16 MFMA (v_mfma_f32_32x32x16_bf16), fused with its reductions so that the
-// rows x N score matrix never reaches HBM.  One streaming skeleton serves five modes:
+// rows x N score matrix never reaches HBM.  One streaming skeleton serves these modes:
 //
 //   owner entity  = rows whose fragments stay in registers for the whole kernel (MFMA B operand, on the lane)
 //   streamed entity = rows that flow HBM -> LDS (XOR-swizzled, double-buffered) and are the MFMA A operand
@@ -7,8 +7,8 @@
 //   LSE / ARGMAX / TILEMAX : owner = states, streamed = items.   S[item][state] = E_out_b[item] . H_b[state] + b[item]
 //        the per-state reduction over items is in-lane (16 registers) + one lane^32 exchange at the end.
 //   BWD_DH : owner = states, streamed = items.   P = exp2(S*log2e - lse*log2e);  dH^T[f][state] += E_out_b^T P
-//   BWD_DE : owner = items,  streamed = states.  P likewise;                     dE^T[f][item]  += H_b^T P
-//        In both backward modes the 32x32 accumulator of S is converted to bf16 in registers and fed straight back
+//   LSE_DH : the forward logsumexp and the softmax-weighted item sum (P relative to a running reference) in one pass
+//        In the two-MFMA modes the 32x32 accumulator of S is converted to bf16 in registers and fed straight back
 //        as the B operand of the second MFMA (k-order = accumulator row order); the A operand is the transposed
 //        read (ds_read_b64_tr_b16) of the very tile already in LDS -- no second copy, no P in LDS or HBM.
 //
@@ -16,11 +16,6 @@
 // (deterministic order).  blockIdx % nsplit = slice, so the blocks of one XCD (blockIdx % 8) share few slices.
 #include <stdlib.h>
 #include "qhead_internal.h"
-
-static int qs_env_int(const char* name, int dflt) {
-  const char* v = getenv(name);
-  return (v && *v) ? atoi(v) : dflt;
-}
 
 template <int D>
 struct QCfg {
@@ -98,7 +93,7 @@ template <int D, int SPW, int MODE, int NBUF, int MINW>
 __global__ __launch_bounds__(256, MINW) void qstream_kernel(QArgs a) {
   using C = QCfg<D>;
   constexpr bool FUSED = (MODE == QM_LSE_DH);          // forward LSE + softmax-weighted sum, running reference
-  constexpr bool BWD = (MODE == QM_BWD_DH || MODE == QM_BWD_DE || FUSED);   // modes with the second MFMA
+  constexpr bool BWD = (MODE == QM_BWD_DH || FUSED);   // modes with the second MFMA
   constexpr int FT = D / 32;
   constexpr int PD = NBUF - 1;               // prefetch distance in stages
   constexpr int VPS = C::LPS + 1;            // vmcnt units per stage per wave (tile pieces + scalar strip)
@@ -119,7 +114,7 @@ __global__ __launch_bounds__(256, MINW) void qstream_kernel(QArgs a) {
 
   // ---- resident fragments ---------------------------------------------------------------------------------
   bf16x8 rf[SPW][C::KS];
-  float rs[SPW];  // per-owner scalar (BWD_DH: -lse*log2e of the state; BWD_DE: bias of the item)
+  float rs[SPW];  // per-owner scalar (BWD_DH: -lse*log2e of the state)
 #pragma unroll
   for (int g = 0; g < SPW; ++g) {
     int64_t row = res0 + g * 32 + r;
@@ -151,7 +146,7 @@ __global__ __launch_bounds__(256, MINW) void qstream_kernel(QArgs a) {
 #pragma unroll
   for (int g = 0; g < SPW; ++g) {
     st_a[g] = NEG_INF;      // running max (LSE, ARGMAX, TILEMAX group max)
-    st_b[g] = 0.f;          // running sum (LSE) / column sum of P (BWD_DE)
+    st_b[g] = 0.f;          // running sum (LSE)
     st_i[g] = 0x7FFFFFFF;   // argmax
   }
   // QM_TOPK: per 32-user group the list of the QS_TOPK_K best admissible candidates of THIS lane's half of every tile
@@ -287,12 +282,7 @@ __global__ __launch_bounds__(256, MINW) void qstream_kernel(QArgs a) {
       f32x16 acc[SPW];
 #pragma unroll
       for (int g = 0; g < SPW; ++g) {
-        if constexpr (MODE == QM_BWD_DE) {
-#pragma unroll
-          for (int i = 0; i < 16; ++i) acc[g][i] = rs[g];
-        } else {
-          acc[g] = sv;
-        }
+        acc[g] = sv;
       }
       {
         bf16x8 af[C::KS];
@@ -314,12 +304,8 @@ __global__ __launch_bounds__(256, MINW) void qstream_kernel(QArgs a) {
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
           const bool ok = tile_row0 + mfma_row(i, h) < s_end;
-          if constexpr (MODE == QM_BWD_DE) {
-            sv[i] = ok ? sv[i] : NEG_INF;
-          } else {
 #pragma unroll
-            for (int g = 0; g < SPW; ++g) acc[g][i] = ok ? acc[g][i] : NEG_INF;
-          }
+          for (int g = 0; g < SPW; ++g) acc[g][i] = ok ? acc[g][i] : NEG_INF;
         }
       }
 
@@ -438,17 +424,8 @@ __global__ __launch_bounds__(256, MINW) void qstream_kernel(QArgs a) {
           }
           float p[16];
 #pragma unroll
-          for (int i = 0; i < 16; ++i) {
-            const float off = (MODE == QM_BWD_DE) ? sv[i] : rs[g];
-            p[i] = fast_exp2(fmaf(acc[g][i], CQL_LOG2E, off));
-          }
+          for (int i = 0; i < 16; ++i) p[i] = fast_exp2(fmaf(acc[g][i], CQL_LOG2E, rs[g]));
           if constexpr (FUSED) {
-            float cs = 0.f;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) cs += p[i];
-            st_b[g] += cs;
-          }
-          if constexpr (MODE == QM_BWD_DE) {
             float cs = 0.f;
 #pragma unroll
             for (int i = 0; i < 16; ++i) cs += p[i];
@@ -528,13 +505,6 @@ __global__ __launch_bounds__(256, MINW) void qstream_kernel(QArgs a) {
             *pd = o;
           }
       }
-      if constexpr (MODE == QM_BWD_DE) {
-        const float cs = st_b[g] + __shfl_xor(st_b[g], 32);
-        if (ok && h == 0) {
-          if (a.out) a.out_cs[row] = a.accumulate ? a.out_cs[row] + sc * cs : sc * cs;
-          else a.slab_cs[pidx] = cs;
-        }
-      }
       if constexpr (FUSED) {   // (reference, sum relative to it): what qhead_finalize_lse_kernel merges
         const float ls = st_b[g] + __shfl_xor(st_b[g], 32);
         if (ok && h == 0) {
@@ -549,11 +519,6 @@ __global__ __launch_bounds__(256, MINW) void qstream_kernel(QArgs a) {
 // =============================================================================================================
 // split selection + launch
 // =============================================================================================================
-int qs_spw_fwd(int d) {
-  static const int v = qs_env_int("CQL_QS_SPW_FWD", QS_SPW_FWD);
-  return (v == 4 && d <= 128) ? 4 : 2;
-}
-
 QSplit qs_choose_split(int64_t n_str, int64_t n_res, int spw, int unit_rows, int target) {
   QSplit s;
   s.rblks = (n_res + 128 * spw - 1) / (128 * spw);
@@ -589,27 +554,22 @@ template <int D, int SPW, int MODE>
 static void qs_launch_d(const QArgs& a, int64_t rblks, hipStream_t s) {
   // ring depth: 3 stages for the single-MFMA forward modes, 2 for the two-MFMA modes (measured: -3..-6 % there, +9 %
   // on ARGMAX with 2)
-  constexpr int NB = (MODE == QM_BWD_DH || MODE == QM_BWD_DE || MODE == QM_LSE_DH) ? QS_NBUF_BWD : QS_NBUF;
+  constexpr int NB = (MODE == QM_BWD_DH || MODE == QM_LSE_DH) ? QS_NBUF_BWD : QS_NBUF;
   qs_launch_n<D, SPW, MODE, NB, (D == 256 ? 1 : 2)>(a, rblks, s);
 }
 
 template <int MODE, int SPW>
 static int qs_launch_mode(const QArgs& a, int d, int64_t rblks, hipStream_t s) {
-  if constexpr (SPW == 4) {   // 128 owners per wave: d <= 128 only (register budget)
-    if (d == 64) qs_launch_d<64, SPW, MODE>(a, rblks, s);
-    else qs_launch_d<128, SPW, MODE>(a, rblks, s);
-  } else {
-    if (d == 64) qs_launch_d<64, SPW, MODE>(a, rblks, s);
-    else if (d == 128) qs_launch_d<128, SPW, MODE>(a, rblks, s);
-    else qs_launch_d<256, SPW, MODE>(a, rblks, s);
-  }
+  if (d == 64) qs_launch_d<64, SPW, MODE>(a, rblks, s);
+  else if (d == 128) qs_launch_d<128, SPW, MODE>(a, rblks, s);
+  else qs_launch_d<256, SPW, MODE>(a, rblks, s);
   return 0;
 }
 
 static int qs_launch_switch(int mode, const QArgs& a, int d, int64_t rblks, hipStream_t s);
 int qs_launch(int mode, const QArgs& a, int d, int64_t rblks, hipStream_t s) {
   static const int phase_of[9] = {0, CQLREC_PH_QHEAD_LSE, CQLREC_PH_QHEAD_ARGMAX, CQLREC_PH_TOPK_TILEMAX,
-                                  CQLREC_PH_QHEAD_BWD_DH, CQLREC_PH_QHEAD_BWD_DE, CQLREC_PH_QHEAD_LSE,
+                                  CQLREC_PH_QHEAD_BWD_DH, 0, CQLREC_PH_QHEAD_LSE,
                                   CQLREC_PH_TOPK_TILEMAX, CQLREC_PH_TOPK_TILEMAX};
   CqlProfScope prof(phase_of[mode], s);
   return qs_launch_switch(mode, a, d, rblks, s);
@@ -620,19 +580,12 @@ static int qs_launch_quiet(int mode, const QArgs& a, int d, int64_t rblks, hipSt
 }
 static int qs_launch_switch(int mode, const QArgs& a, int d, int64_t rblks, hipStream_t s) {
   switch (mode) {
-    case QM_LSE:
-      if (qs_spw_fwd(d) == 4) return qs_launch_mode<QM_LSE, 4>(a, d, rblks, s);
-      return qs_launch_mode<QM_LSE, 2>(a, d, rblks, s);
-    case QM_ARGMAX:
-      if (qs_spw_fwd(d) == 4) return qs_launch_mode<QM_ARGMAX, 4>(a, d, rblks, s);
-      return qs_launch_mode<QM_ARGMAX, 2>(a, d, rblks, s);
-    case QM_TILEMAX:
-      if (qs_spw_fwd(d) == 4) return qs_launch_mode<QM_TILEMAX, 4>(a, d, rblks, s);
-      return qs_launch_mode<QM_TILEMAX, 2>(a, d, rblks, s);
+    case QM_LSE: return qs_launch_mode<QM_LSE, QS_SPW_FWD>(a, d, rblks, s);
+    case QM_ARGMAX: return qs_launch_mode<QM_ARGMAX, QS_SPW_FWD>(a, d, rblks, s);
+    case QM_TILEMAX: return qs_launch_mode<QM_TILEMAX, QS_SPW_FWD>(a, d, rblks, s);
     case QM_TOPK: return qs_launch_mode<QM_TOPK, 2>(a, d, rblks, s);
     case QM_TOPK10: return qs_launch_mode<QM_TOPK10, 2>(a, d, rblks, s);
     case QM_BWD_DH: return qs_launch_mode<QM_BWD_DH, QS_SPW_BWD>(a, d, rblks, s);
-    case QM_BWD_DE: return qs_launch_mode<QM_BWD_DE, QS_SPW_BWD>(a, d, rblks, s);
     case QM_LSE_DH: return qs_launch_mode<QM_LSE_DH, QS_SPW_BWD>(a, d, rblks, s);
   }
   return -1;
@@ -724,16 +677,13 @@ __global__ __launch_bounds__(64) void qhead_argmax_resolve_kernel(const float* _
 }
 
 // dst[row][f] = scale * sum_split slab[split][row][f]  (+ coef[row] * E_b[act[row]][f] when coef != NULL)
-// cs_dst[row]  = scale * sum_split slab_cs[split][row]                           (when slab_cs != NULL)
 template <int D>
-__global__ __launch_bounds__(256) void qhead_bwd_reduce_kernel(const float* __restrict__ slab,
-                                                               const float* __restrict__ slab_cs, int nsplit,
+__global__ __launch_bounds__(256) void qhead_bwd_reduce_kernel(const float* __restrict__ slab, int nsplit,
                                                                int64_t rows, float scale,
                                                                const float* __restrict__ coef,
                                                                const int32_t* __restrict__ act,
                                                                const uint16_t* __restrict__ E_b,
-                                                               float* __restrict__ dst, float* __restrict__ cs_dst,
-                                                               int accumulate) {
+                                                               float* __restrict__ dst) {
   constexpr int V = D / 4;  // float4 per row
   const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= rows * V) return;
@@ -759,16 +709,7 @@ __global__ __launch_bounds__(256) void qhead_bwd_reduce_kernel(const float* __re
     s.z = fmaf(cf, __uint_as_float(e.y << 16), s.z);
     s.w = fmaf(cf, __uint_as_float(e.y & 0xFFFF0000u), s.w);
   }
-  if (accumulate) {
-    const float4 old = *reinterpret_cast<const float4*>(dst + row * D + c * 4);
-    s.x += old.x; s.y += old.y; s.z += old.z; s.w += old.w;
-  }
   *reinterpret_cast<float4*>(dst + row * D + c * 4) = s;
-  if (slab_cs && c == 0) {
-    float t = 0.f;
-    for (int k = 0; k < nsplit; ++k) t += slab_cs[(int64_t)k * rows + row];
-    cs_dst[row] = accumulate ? cs_dst[row] + t * scale : t * scale;
-  }
 }
 
 // dH from the fused forward's slabs:  dst[row][f] = scale * sum_k slab[k][row][f] * exp(m[k][row] - lse[row])
@@ -841,25 +782,18 @@ static inline int64_t align256(int64_t x) { return (x + 255) / 256 * 256; }
 
 extern "C" int64_t cqlrec_qhead_ws_bytes(int64_t rows, int64_t n_items, int32_t d) {
   (void)d;
-  const QSplit sp = qs_choose_split(n_items, rows, qs_spw_fwd(d), QS_TI, QS_TARGET_BLOCKS);
+  const QSplit sp = qs_choose_split(n_items, rows, QS_SPW_FWD, QS_TI, QS_TARGET_BLOCKS);
   return 3 * align256((int64_t)sp.nsplit * rows * 4) + 256;
 }
 
 static int qhead_fwd_impl(const uint16_t* H_b, int64_t rows, const uint16_t* E_out_b, const float* b_out, int64_t n_items,
                          int32_t d, int32_t mode, void* ws, int64_t ws_bytes, float* out_val, int32_t* out_idx,
-                         float* out_nlse2, cqlrec_stream stream, int form);
+                         float* out_nlse2, cqlrec_stream stream, bool skeleton);
 extern "C" int cqlrec_qhead_fwd(const uint16_t* H_b, int64_t rows, const uint16_t* E_out_b, const float* b_out,
                                 int64_t n_items, int32_t d, int32_t mode, void* ws, int64_t ws_bytes, float* out_val,
                                 int32_t* out_idx, float* out_nlse2, cqlrec_stream stream) {
-  return qhead_fwd_impl(H_b, rows, E_out_b, b_out, n_items, d, mode, ws, ws_bytes, out_val, out_idx, out_nlse2, stream, 0);
-}
-// ARGMAX with 32 states per wave and at most 128 registers (d = 128): slower on its own than the 64-state form, but its
-// waves fit beside qfwd2_kernel's on a SIMD (that kernel leaves 136 of the 512 registers per lane and 127 KiB of LDS), so
-// the step driver launches the two passes together and this one's MFMAs run in the issue gaps of the other.
-int cql_qhead_argmax_beside(const uint16_t* H_b, int64_t rows, const uint16_t* E_out_b, const float* b_out, int64_t n_items,
-                            int32_t d, void* ws, int64_t ws_bytes, float* out_val, int32_t* out_idx, hipStream_t stream) {
-  return qhead_fwd_impl(H_b, rows, E_out_b, b_out, n_items, d, CQLREC_QHEAD_ARGMAX, ws, ws_bytes, out_val, out_idx, nullptr,
-                        (cqlrec_stream)stream, d == 128 ? 1 : 0);
+  return qhead_fwd_impl(H_b, rows, E_out_b, b_out, n_items, d, mode, ws, ws_bytes, out_val, out_idx, out_nlse2, stream,
+                        false);
 }
 // ARGMAX as the training step launches it, on the branch stream WHILE the fused forward of the other branch runs.  d = 128:
 // the two-waves-per-SIMD form of the skeleton -- one of its waves (<= 128 registers) fits beside a wave of qfwd2_kernel (368)
@@ -868,21 +802,19 @@ int cql_qhead_argmax_beside(const uint16_t* H_b, int64_t rows, const uint16_t* E
 // d = 256: nothing fits beside qfwd3_kernel anyway; qargmax2_kernel (1.59 instead of 2.02 ms; cfg5shard step -10 %).
 int cql_qhead_argmax_step(const uint16_t* H_b, int64_t rows, const uint16_t* E_out_b, const float* b_out, int64_t n_items,
                           int32_t d, void* ws, int64_t ws_bytes, float* out_val, int32_t* out_idx, hipStream_t stream) {
-  static const int force2 = getenv("CQL_QARGMAX2") && getenv("CQL_QARGMAX2")[0] == '2';      // A/B: the new kernel in the step too
   return qhead_fwd_impl(H_b, rows, E_out_b, b_out, n_items, d, CQLREC_QHEAD_ARGMAX, ws, ws_bytes, out_val, out_idx, nullptr,
-                        (cqlrec_stream)stream, (d == 128 && !force2) ? 2 : 0);
+                        (cqlrec_stream)stream, d == 128);
 }
+// skeleton: ARGMAX in the skeleton's 64-state form even where qargmax2_kernel (the fastest form on its own) is supported
 static int qhead_fwd_impl(const uint16_t* H_b, int64_t rows, const uint16_t* E_out_b, const float* b_out, int64_t n_items,
                          int32_t d, int32_t mode, void* ws, int64_t ws_bytes, float* out_val, int32_t* out_idx,
-                         float* out_nlse2, cqlrec_stream stream, int form) {
-  const bool small_waves = form == 1;          // 0: the fastest form on its own; 1: small waves; 2: the skeleton's 64-state form
+                         float* out_nlse2, cqlrec_stream stream, bool skeleton) {
   CQL_REQUIRE(H_b && E_out_b && b_out && ws && out_val, "qhead_fwd: NULL pointer");
   CQL_REQUIRE(d == 64 || d == 128 || d == 256, "qhead_fwd: d=%d unsupported", d);
   CQL_REQUIRE(rows > 0 && n_items > 0, "qhead_fwd: rows=%lld n_items=%lld", (long long)rows, (long long)n_items);
   CQL_REQUIRE(mode == CQLREC_QHEAD_LSE || mode == CQLREC_QHEAD_ARGMAX, "qhead_fwd: bad mode %d", mode);
   CQL_REQUIRE(ws_bytes >= cqlrec_qhead_ws_bytes(rows, n_items, d), "qhead_fwd: workspace too small");
-  const QSplit sp = small_waves ? qs_choose_split(n_items, rows, 1, QS_TI, 256)
-                                : qs_choose_split(n_items, rows, qs_spw_fwd(d), QS_TI, QS_TARGET_BLOCKS);
+  const QSplit sp = qs_choose_split(n_items, rows, QS_SPW_FWD, QS_TI, QS_TARGET_BLOCKS);
   const int64_t seg = align256((int64_t)sp.nsplit * rows * 4);
   QArgs a = {};
   a.res = H_b;
@@ -905,10 +837,7 @@ static int qhead_fwd_impl(const uint16_t* H_b, int64_t rows, const uint16_t* E_o
     hipLaunchKernelGGL(qhead_finalize_lse_kernel, dim3(cql_ceil_div(rows, thr)), dim3(thr), 0, s, a.part_a, a.part_b,
                        a.nsplit, rows, out_val, out_nlse2);
   } else {
-    if (small_waves) {
-      CqlProfScope prof(CQLREC_PH_QHEAD_ARGMAX, s);
-      qs_launch_n<128, 1, QM_ARGMAX, QS_NBUF, 4>(a, sp.rblks, s);
-    } else if (form == 0 && cql_qargmax2_supported(d, n_items)) {
+    if (!skeleton && cql_qargmax2_supported(d, n_items)) {
       // one wave per SIMD, software-pipelined (qhead_argmax2.hip); fewer, longer slices than the generic form: the partials
       // fit the workspace carved above (same [slice][row] layout, fewer slices)
       int ns2;
@@ -939,6 +868,7 @@ extern "C" int64_t cqlrec_qhead_bwd_ws_bytes(int64_t batch, int64_t n_items, int
   const QSplit s1 = qs_choose_split(n_items, batch, QS_SPW_BWD, QS_TI, QS_TARGET_BLOCKS_BWD);
   const QSplit s2 = qs_choose_split(batch, n_items, QS_SPW_BWD, QS_TI, QS_TARGET_BLOCKS_BWD);
   const int64_t a1 = align256((int64_t)s1.nsplit * batch * d * 4);
+  // a2: the slabs of the retired skeleton form of the item-side backward, still counted so that the size stays as it was
   const int64_t a2 = align256((int64_t)s2.nsplit * n_items * d * 4) + align256((int64_t)s2.nsplit * n_items * 4);
   const int64_t a3 = cql_qde_ws_bytes(batch, n_items, d);
   const int64_t m = (a1 > a2 ? a1 : a2);
@@ -972,92 +902,37 @@ extern "C" int cqlrec_qhead_bwd_states(const uint16_t* H_b, const float* nlse2, 
   const int64_t n4 = batch * (d / 4);
   dim3 grid(cql_ceil_div(n4, 256)), block(256);
 #define RED_DH(DD)                                                                                                  \
-  hipLaunchKernelGGL(qhead_bwd_reduce_kernel<DD>, grid, block, 0, s, a.slab, (const float*)nullptr, a.nsplit, batch, \
-                     scale, coef, act, E_out_b, dH, (float*)nullptr, 0)
+  hipLaunchKernelGGL(qhead_bwd_reduce_kernel<DD>, grid, block, 0, s, a.slab, a.nsplit, batch, scale, coef, act, E_out_b, \
+                     dH)
   if (d == 64) RED_DH(64); else if (d == 128) RED_DH(128); else RED_DH(256);
 #undef RED_DH
   CQL_LAUNCH_CHECK("qhead_bwd_states");
   return CQLREC_OK;
 }
 
-// g_E_out / g_b_out only (owner = items, streamed = states)
-// sparse_first: scatter the one-hot part first and let the streaming kernel accumulate (callers with zeroed gradients);
-// [item_lo, item_hi): item rows handled by this call (the scatter, when requested, always covers every item).
+// g_E_out / g_b_out only: the persistent, statically balanced kernel of qhead_de.hip, then (do_sparse) the one-hot
+// scatter on top of its rows
 static int qhead_bwd_items_impl(const uint16_t* H_b, const float* nlse2, const float* coef, const int32_t* act,
                                int64_t batch, const uint16_t* E_out_b, const float* b_out, int64_t n_items, int32_t d,
                                float scale, void* ws, int64_t ws_bytes, float* g_E_out, float* g_b_out,
-                               cqlrec_stream stream, bool sparse_first, bool do_sparse = true, int64_t item_lo = 0,
-                               int64_t item_hi = -1, CqlAdamFix* defer = nullptr, const float* nlse_nat = nullptr) {
+                               cqlrec_stream stream, bool do_sparse, CqlAdamFix* defer = nullptr,
+                               const float* nlse_nat = nullptr) {
   if (defer) defer->valid = 0;
-  if (item_hi < 0) item_hi = n_items;
-  CQL_REQUIRE(item_lo >= 0 && item_lo < item_hi && item_hi <= n_items, "qhead_bwd_items: bad item range");
   CQL_REQUIRE(H_b && nlse2 && coef && act && E_out_b && b_out && ws && g_E_out && g_b_out, "qhead_bwd_items: NULL pointer");
   CQL_REQUIRE(d == 64 || d == 128 || d == 256, "qhead_bwd_items: d=%d unsupported", d);
   CQL_REQUIRE(batch > 0 && n_items > 0, "qhead_bwd_items: batch=%lld n_items=%lld", (long long)batch, (long long)n_items);
   CQL_REQUIRE(ws_bytes >= cqlrec_qhead_bwd_ws_bytes(batch, n_items, d), "qhead_bwd_items: workspace too small");
   hipStream_t s = (hipStream_t)stream;
-  dim3 block(256);
-  auto launch_sparse = [&]() {
+  const int rc = cql_qde_launch(H_b, nlse2, batch, E_out_b, b_out, n_items, d, scale, ws, ws_bytes, g_E_out, g_b_out, 0, s,
+                                defer, nlse_nat);
+  if (rc != CQLREC_OK) return rc;
+  if (do_sparse) {
     CqlProfScope prof(CQLREC_PH_QHEAD_SMALL, s);
-    dim3 g2(cql_ceil_div(batch, 4));
+    dim3 g2(cql_ceil_div(batch, 4)), block(256);
 #define SP_DE(DD) hipLaunchKernelGGL(qhead_bwd_sparse_kernel<DD>, g2, block, 0, s, coef, act, H_b, batch, g_E_out, g_b_out)
     if (d == 64) SP_DE(64); else if (d == 128) SP_DE(128); else SP_DE(256);
 #undef SP_DE
-  };
-  if (sparse_first && do_sparse) launch_sparse();
-  // Large catalogues: one block per 128 items streams every state and writes its rows directly (no cross-block
-  // sum).  Small catalogues: the state axis is split too, slabs are summed by the small reduce kernel.  (A third
-  // variant -- a whole number of resident "rounds" first, the remainder with split states -- measured no faster:
-  // the step driver instead runs this kernel concurrently with the state-side kernel, which fills the idle CUs of
-  // the last round.)
-  auto launch_range = [&](int64_t row0, int64_t count, bool allow_direct) {
-    const QSplit sp = (allow_direct)
-                          ? qs_choose_split(batch, count, QS_SPW_BWD, QS_TI, 1)
-                          : qs_choose_split(batch, count, QS_SPW_BWD, QS_TI, QS_TARGET_BLOCKS_BWD);
-    QArgs a = {};
-    a.res = E_out_b + row0 * d;
-    a.n_res = count;
-    a.str = H_b;
-    a.n_str = batch;
-    a.str_scalar = nlse2;
-    a.res_scalar = b_out + row0;
-    a.nsplit = sp.nsplit;
-    a.split_rows = sp.split_rows;
-    a.slab = (float*)ws;
-    a.slab_cs = (float*)((char*)ws + align256((int64_t)sp.nsplit * count * d * 4));
-    a.tg = 1;
-    const bool direct = (sp.nsplit == 1);
-    if (direct) {   // one slice: the kernel scales and writes g_E_out / g_b_out itself
-      a.out = g_E_out + row0 * d;
-      a.out_cs = g_b_out + row0;
-      a.scale = scale;
-      a.accumulate = sparse_first ? 1 : 0;
-    }
-    qs_launch(QM_BWD_DE, a, d, sp.rblks, s);
-    if (!direct) {
-      CqlProfScope prof(CQLREC_PH_QHEAD_SMALL, s);
-      const int64_t n4 = count * (d / 4);
-      dim3 grid(cql_ceil_div(n4, 256));
-#define RED_DE(DD)                                                                                            \
-  hipLaunchKernelGGL(qhead_bwd_reduce_kernel<DD>, grid, block, 0, s, a.slab, a.slab_cs, a.nsplit, count, scale, \
-                     (const float*)nullptr, (const int32_t*)nullptr, (const uint16_t*)nullptr,                 \
-                     g_E_out + row0 * d, g_b_out + row0, sparse_first ? 1 : 0)
-      if (d == 64) RED_DE(64); else if (d == 128) RED_DE(128); else RED_DE(256);
-#undef RED_DE
-    }
-  };
-  // default: the persistent, statically balanced kernel of qhead_de.hip; CQL_QDE=0 selects the generic skeleton (A/B)
-  static const bool use_qde = !(getenv("CQL_QDE") && getenv("CQL_QDE")[0] == '0');
-  if (use_qde) {
-    const int rc = cql_qde_launch(H_b, nlse2, batch, E_out_b + item_lo * d, b_out + item_lo, item_hi - item_lo, d, scale,
-                                  ws, ws_bytes, g_E_out + item_lo * d, g_b_out + item_lo, sparse_first ? 1 : 0, s,
-                                  (item_lo == 0 && item_hi == n_items) ? defer : nullptr, nlse_nat);
-    if (rc != CQLREC_OK) return rc;
-  } else {
-    const int64_t rblks_all = (n_items + 127) / 128;
-    launch_range(item_lo, item_hi - item_lo, rblks_all >= QS_TARGET_BLOCKS_BWD);
   }
-  if (!sparse_first && do_sparse) launch_sparse();
   CQL_LAUNCH_CHECK("qhead_bwd_items");
   return CQLREC_OK;
 }
@@ -1067,7 +942,7 @@ extern "C" int cqlrec_qhead_bwd_items(const uint16_t* H_b, const float* nlse2, c
                                       int32_t d, float scale, void* ws, int64_t ws_bytes, float* g_E_out,
                                       float* g_b_out, cqlrec_stream stream) {
   return qhead_bwd_items_impl(H_b, nlse2, coef, act, batch, E_out_b, b_out, n_items, d, scale, ws, ws_bytes, g_E_out,
-                              g_b_out, stream, false);
+                              g_b_out, stream, true);
 }
 
 // ---- fused forward (training): lse + slabs of the softmax-weighted item sum; see qhead_internal.h ---------------
@@ -1202,15 +1077,7 @@ int cql_qhead_bwd_items_long(const uint16_t* H_b, const float* nlse2, const floa
                              int64_t ws_bytes, float* g_E_out, float* g_b_out, hipStream_t stream, CqlAdamFix* defer,
                              const float* nlse_nat) {
   return qhead_bwd_items_impl(H_b, nlse2, coef, act, batch, E_out_b, b_out, n_items, d, scale, ws, ws_bytes, g_E_out,
-                              g_b_out, (cqlrec_stream)stream, false, false, 0, -1, defer, nlse_nat);
-}
-
-int cql_qhead_bwd_items_acc(const uint16_t* H_b, const float* nlse2, const float* coef, const int32_t* act, int64_t batch,
-                            const uint16_t* E_out_b, const float* b_out, int64_t n_items, int32_t d, float scale, void* ws,
-                            int64_t ws_bytes, float* g_E_out, float* g_b_out, hipStream_t stream, int do_sparse,
-                            int64_t item_lo, int64_t item_hi, CqlAdamFix* defer, const float* nlse_nat) {
-  return qhead_bwd_items_impl(H_b, nlse2, coef, act, batch, E_out_b, b_out, n_items, d, scale, ws, ws_bytes, g_E_out,
-                              g_b_out, (cqlrec_stream)stream, true, do_sparse != 0, item_lo, item_hi, defer, nlse_nat);
+                              g_b_out, (cqlrec_stream)stream, false, defer, nlse_nat);
 }
 
 extern "C" int cqlrec_qhead_bwd(const uint16_t* H_b, const float* nlse2, const float* coef, const int32_t* act,

@@ -271,8 +271,7 @@ __global__ __launch_bounds__(256, 1) void qargmax2_kernel(QArgmax2Args a) {
 // host side
 // =============================================================================================================
 bool cql_qargmax2_supported(int d, int64_t n_items) {
-  static const int off = getenv("CQL_QARGMAX2") && getenv("CQL_QARGMAX2")[0] == '0';
-  return !off && (d == 128 || d == 256) && n_items * (2 * d) < (1ll << 31);
+  return (d == 128 || d == 256) && n_items * (2 * d) < (1ll << 31);
 }
 
 // slices for ONE block per CU (256 states per block); at least eight stages per slice

@@ -1,5 +1,6 @@
 // Item-side backward of the Q-head (row a6: g_E_out, g_b_out), the longest kernel of the training step, as a kernel of
-// its own: a PERSISTENT, statically balanced ("stream-K") version of the BWD_DE mode of qhead.hip.
+// its own: a PERSISTENT, statically balanced ("stream-K") version of the BWD_DE mode that the generic streaming skeleton
+// of qhead.hip had (retired since: this kernel replaced it).
 //
 //   dE^T[f][item] = sum_state H_b^T[f][state] * bf16(P[state][item]),   P = exp2((S + b_item) log2e - lse_state log2e)
 //   S[state][item] = <H_b[state], E_out_b[item]>        (recomputed: the B x N score matrix never exists)
@@ -338,20 +339,16 @@ static int de_env_int(const char* name, int dflt) {
 }
 // block shape: 8 waves (256 items per group, ONE block per CU, both waves of a SIMD stream the same tiles: half the LDS
 // fill traffic and half the LDS-DMA instructions per MFMA of the 4-wave form) unless the register budget forbids two
-// waves per SIMD (d = 256)
-static int de_waves(int d) {
-  static const int w = de_env_int("CQL_QDE_WAVES", 8);
-  return (d == 256 || w != 8) ? 4 : 8;
-}
-// form 2 (64 items per wave, one wave per SIMD, in-wave pipeline: qhead_de2.hip) for d = 128 unless CQL_QDE2=0
-static bool de_form2(int d, int64_t batch) {
-  static const int on = de_env_int("CQL_QDE2", 1);
-  return on != 0 && d == 128 && batch % 64 == 0;
-}
+// waves per SIMD (d = 256).  Form 2 has the same 256-item groups.
+static constexpr int de_waves(int d) { return d == 256 ? 4 : 8; }
+// LDS stage buffers of qde_kernel (prefetch distance 1 stage)
+#define QDE_NBUF 2
+// form 2 (64 items per wave, one wave per SIMD, in-wave pipeline: qhead_de2.hip) for d = 128
+static bool de_form2(int d, int64_t batch) { return d == 128 && batch % 64 == 0; }
+// one persistent block per CU (fewer when there are fewer stage-units than CUs)
 static int de_grid(int64_t n_items, int64_t batch, int d) {
-  const int ti = (d == 256) ? 32 : 64, items = de_form2(d, batch) ? 256 : 32 * de_waves(d);
+  const int ti = (d == 256) ? 32 : 64, items = 32 * de_waves(d);
   const int64_t G = (n_items + items - 1) / items, T = (batch + ti - 1) / ti;
-  static const int per_cu = de_env_int("CQL_QDE_BLOCKS_PER_CU", 0);
   static const int n_cu = [] {
     int dev = 0, n = 0;
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
@@ -359,9 +356,8 @@ static int de_grid(int64_t n_items, int64_t batch, int d) {
       n = 256;
     return n;
   }();
-  int64_t slots = (int64_t)n_cu * (per_cu > 0 && !de_form2(d, batch) ? per_cu : (d == 256 || de_form2(d, batch) || de_waves(d) == 8 ? 1 : 2));
   const int64_t W = G * T;
-  return (int)(W < slots ? W : slots);
+  return (int)(W < n_cu ? W : n_cu);
 }
 
 int64_t cql_qde_ws_bytes(int64_t batch, int64_t n_items, int32_t d) {
@@ -381,19 +377,8 @@ static void qde_launch_n(const QDeArgs& a, int grid, hipStream_t s) {
   hipLaunchKernelGGL((qde_kernel<D, NBUF, WAVES>), dim3(grid), dim3(64 * WAVES), smem, s, a);
 }
 template <int D>
-static void qde_launch_d(const QDeArgs& a, int grid, int nbuf, int waves, hipStream_t s) {
-  if constexpr (D != 256) {
-    if (waves == 8) {
-      if (nbuf == 3) qde_launch_n<D, 3, 8>(a, grid, s); else qde_launch_n<D, 2, 8>(a, grid, s);
-      return;
-    }
-  }
-  if (nbuf == 3) qde_launch_n<D, 3, 4>(a, grid, s); else qde_launch_n<D, 2, 4>(a, grid, s);
-}
-template <int D>
-static void qde_fixup_d(const QDeArgs& a, int grid, int waves, hipStream_t s) {
-  if (waves == 8) hipLaunchKernelGGL((qde_fixup_kernel<D, 256>), dim3(a.G), dim3(256), 0, s, a, grid);
-  else hipLaunchKernelGGL((qde_fixup_kernel<D, 128>), dim3(a.G), dim3(256), 0, s, a, grid);
+static void qde_fixup_d(const QDeArgs& a, int grid, hipStream_t s) {
+  hipLaunchKernelGGL((qde_fixup_kernel<D, 32 * de_waves(D)>), dim3(a.G), dim3(256), 0, s, a, grid);
 }
 
 // g_E_out / g_b_out rows [0, n_items) of this call: out (+)= scale * dE (accumulate: on top of what is there)
@@ -404,7 +389,7 @@ int cql_qde_launch(const uint16_t* H_b, const float* nlse2, int64_t batch, const
   CQL_REQUIRE(ws_bytes >= cql_qde_ws_bytes(batch, n_items, d), "qde: workspace too small");
   CQL_REQUIRE(batch * 2 * d < (1ll << 31), "qde: batch=%lld too large for one buffer descriptor", (long long)batch);
   const bool form2 = de_form2(d, batch);
-  const int ti = (d == 256) ? 32 : 64, waves = form2 ? 8 : de_waves(d), items = form2 ? 256 : 32 * waves;
+  const int ti = (d == 256) ? 32 : 64, items = 32 * de_waves(d);
   QDeArgs a = {};
   a.H_b = H_b;
   a.nlse2 = nlse2;
@@ -421,7 +406,6 @@ int cql_qde_launch(const uint16_t* H_b, const float* nlse2, int64_t batch, const
   const int grid = de_grid(n_items, batch, d);
   a.slab = (float*)ws;
   a.slab_cs = (float*)((char*)ws + de_align256((int64_t)grid * items * d * 4));
-  static const int nbuf = de_env_int("CQL_QDE_NBUF", 2);
   static const int want_stamps = de_env_int("CQL_QDE_STAMPS", 0);     // diagnostic: in-kernel clock, synchronises
   unsigned long long* stamps_dev = (unsigned long long*)((char*)a.slab_cs + de_align256((int64_t)grid * items * 4) +
                                                          de_align256(batch * 4));
@@ -443,9 +427,9 @@ int cql_qde_launch(const uint16_t* H_b, const float* nlse2, int64_t batch, const
     if (rc != CQLREC_OK) return rc;
   } else {
     CqlProfScope prof(CQLREC_PH_QHEAD_BWD_DE, s);
-    if (d == 64) qde_launch_d<64>(a, grid, nbuf, waves, s);
-    else if (d == 128) qde_launch_d<128>(a, grid, nbuf, waves, s);
-    else qde_launch_d<256>(a, grid, nbuf, waves, s);
+    if (d == 64) qde_launch_n<64, QDE_NBUF, de_waves(64)>(a, grid, s);
+    else if (d == 128) qde_launch_n<128, QDE_NBUF, de_waves(128)>(a, grid, s);
+    else qde_launch_n<256, QDE_NBUF, de_waves(256)>(a, grid, s);
   }
   const int64_t W = (int64_t)a.G * a.T;
   bool cut = false;                    // does some range start inside a group?
@@ -463,9 +447,9 @@ int cql_qde_launch(const uint16_t* H_b, const float* nlse2, int64_t batch, const
     defer->n_items = n_items;
   } else if (cut) {
     CqlProfScope prof(CQLREC_PH_QHEAD_SMALL, s);
-    if (d == 64) qde_fixup_d<64>(a, grid, waves, s);
-    else if (d == 128) qde_fixup_d<128>(a, grid, waves, s);
-    else qde_fixup_d<256>(a, grid, waves, s);
+    if (d == 64) qde_fixup_d<64>(a, grid, s);
+    else if (d == 128) qde_fixup_d<128>(a, grid, s);
+    else qde_fixup_d<256>(a, grid, s);
   }
   CQL_LAUNCH_CHECK("qde");
   if (want_stamps) {      // median over blocks of shader ticks / 100 MHz ticks (MI355X_MICROARCH.md, DVFS give-back item 6)
@@ -515,10 +499,9 @@ int cql_qde_fixup_deferred(const CqlAdamFix& f, float* out, float* out_cs, hipSt
   a.G = f.G;
   a.T = f.T;
   CqlProfScope prof(CQLREC_PH_QHEAD_SMALL, s);
-  const int waves = f.items / 32;
-  if (f.D == 64) qde_fixup_d<64>(a, f.nblk, waves, s);
-  else if (f.D == 128) qde_fixup_d<128>(a, f.nblk, waves, s);
-  else qde_fixup_d<256>(a, f.nblk, waves, s);
+  if (f.D == 64) qde_fixup_d<64>(a, f.nblk, s);
+  else if (f.D == 128) qde_fixup_d<128>(a, f.nblk, s);
+  else qde_fixup_d<256>(a, f.nblk, s);
   CQL_LAUNCH_CHECK("qde fix-up");
   return CQLREC_OK;
 }

@@ -323,8 +323,7 @@ __global__ __launch_bounds__(256, 1) void qde3_kernel(QDeArgs a) {
 // host side
 // =============================================================================================================
 bool cql_qde3_supported(int d, int64_t batch) {
-  static const int off = getenv("CQL_QDE3") && getenv("CQL_QDE3")[0] == '0';
-  return !off && d == 256 && batch % 32 == 0;
+  return d == 256 && batch % 32 == 0;
 }
 
 // rows [0, n_items): `a` prepared by cql_qde_launch (G, T for 128-item groups and 32-state stages; nlse2 = -lse in

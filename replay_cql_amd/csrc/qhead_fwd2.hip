@@ -409,8 +409,7 @@ __global__ __launch_bounds__(256, 1) void qfwd2_kernel(QFwd2Args a) {
 // host side
 // =============================================================================================================
 bool cql_qfwd2_supported(int d, int64_t n_items) {
-  static const int off = getenv("CQL_QFWD2") && getenv("CQL_QFWD2")[0] == '0';
-  return !off && d == 128 && n_items * 256 < (1ll << 31);
+  return d == 128 && n_items * 256 < (1ll << 31);
 }
 
 int cql_qfwd2_run(const QFwd2Args& a, int d, hipStream_t s) {

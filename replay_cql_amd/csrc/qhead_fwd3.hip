@@ -336,8 +336,7 @@ __global__ __launch_bounds__(256, 1) void qfwd3_kernel(QFwd2Args a) {
 // host side
 // =============================================================================================================
 bool cql_qfwd3_supported(int d, int64_t n_items) {
-  static const int off = getenv("CQL_QFWD3") && getenv("CQL_QFWD3")[0] == '0';
-  return !off && d == 256 && n_items * 512 < (1ll << 31);
+  return d == 256 && n_items * 512 < (1ll << 31);
 }
 
 int cql_qfwd3_run(const QFwd2Args& a, int d, hipStream_t s) {

@@ -6,7 +6,6 @@
 #define QM_ARGMAX 2
 #define QM_TILEMAX 3
 #define QM_BWD_DH 4
-#define QM_BWD_DE 5
 #define QM_LSE_DH 6         // forward logsumexp AND the softmax-weighted item sum (the soft part of dH) in one pass
 #define QM_TOPK 7           // running top-k (k <= 16) per user in the epilogue: no score or group maximum leaves the chip
 #define QM_TOPK10 8         // the same with only 10 of the 16 list entries kept sorted (k <= 10; see qtopk4_kernel's KC)
@@ -23,7 +22,7 @@
 #define QS_NBUF 3             // LDS stage buffers (prefetch distance NBUF-1 stages), forward modes
 #endif
 #ifndef QS_NBUF_BWD
-#define QS_NBUF_BWD 2         // ... two-MFMA modes (BWD_DH, BWD_DE, LSE_DH)
+#define QS_NBUF_BWD 2         // ... two-MFMA modes (BWD_DH, LSE_DH)
 #endif
 
 struct QArgs {
@@ -31,8 +30,8 @@ struct QArgs {
   int64_t n_res;
   const uint16_t* str;       // streamed rows [n_str x D] bf16
   int64_t n_str;
-  const float* str_scalar;   // per streamed row: bias (fwd, BWD_DH) / -lse*log2e (BWD_DE)
-  const float* res_scalar;   // per owner row:    -lse*log2e (BWD_DH) / bias (BWD_DE)
+  const float* str_scalar;   // per streamed row: bias
+  const float* res_scalar;   // per owner row:    -lse*log2e (BWD_DH)
   int nsplit;
   int64_t split_rows;        // streamed rows per slice (multiple of QS_TI and of 32*tg)
   float* part_a;             // [nsplit][n_res]  running max
@@ -41,12 +40,11 @@ struct QArgs {
   float* tilemax;            // [ngroups][n_res] (TILEMAX)
   int tg;                    // 32-row tiles per tile group (TILEMAX)
   float* slab;               // [nsplit][n_res][D] (backward)
-  float* slab_cs;            // [nsplit][n_res]    (BWD_DE column sums of P)
-  // direct output (backward, nsplit == 1): out[row][D] = scale * y, out_cs[row] = scale * colsum; no slab round trip
+  // direct output of the two-MFMA modes (out[row][D] = scale * y, no slab round trip): no launch sets it any more, the
+  // epilogue still reads it (NULL)
   float* out;
-  float* out_cs;
   float scale;
-  int accumulate;            // direct output adds to out / out_cs instead of overwriting (rows are block-owned: no atomics)
+  int accumulate;            // direct output adds to out instead of overwriting
   // QM_TOPK: per (slice, user, lane half) the QS_TOPK_K best admissible candidates as sortable 64-bit keys
   // (order-preserving score bits << 32 | ~candidate row), best first, 0 = none
   const int* guard;                // QM_LSE_DH as a fall-back launch: every block returns at once unless *guard != 0
@@ -62,11 +60,8 @@ struct QSplit {
   int64_t rblks;
 };
 
-int qs_spw_fwd(int d);
 QSplit qs_choose_split(int64_t n_str, int64_t n_res, int spw, int unit_rows, int target_blocks);
 int qs_launch(int mode, const QArgs& a, int d, int64_t rblks, hipStream_t s);
-// item-side backward for the step driver: the one-hot scatter goes FIRST (into zeroed g_E_out / g_b_out), the streaming
-// kernel then adds its rows -- nothing small is left behind the long kernel on the step's critical path.
 // Fused forward for training ("flash" form): one pass over the catalogue yields, per state, the logsumexp AND
 // sum_j exp(S_j - m) E_out_b[j] relative to a running reference m (slabs in `ws`), so that the state-side backward
 // needs no second pass over the catalogue -- cql_qhead_dh_finish turns the slabs into dH once lse and the TD
@@ -80,12 +75,6 @@ int cql_qhead_fwd_lse_dh_prepare(void* ws, int64_t rows, int64_t n_items, int32_
 int cql_qhead_dh_finish(const void* ws, int64_t rows, int64_t n_items, int32_t d, const float* lse, const float* coef,
                         const int32_t* act, const uint16_t* E_out_b, float scale, float* dH, hipStream_t stream,
                         int part = 0);     // 0: all of dH; 1: the soft part (coef may be NULL); 2: + coef * E_out_b[a] (1 then 2 = 0, bit for bit)
-// do_sparse: issue the scatter in this call; [item_lo, item_hi): item rows the streaming kernel handles in this call.
-int cql_qhead_bwd_items_acc(const uint16_t* H_b, const float* nlse2, const float* coef, const int32_t* act, int64_t batch,
-                            const uint16_t* E_out_b, const float* b_out, int64_t n_items, int32_t d, float scale, void* ws,
-                            int64_t ws_bytes, float* g_E_out, float* g_b_out, hipStream_t stream, int do_sparse,
-                            int64_t item_lo, int64_t item_hi, CqlAdamFix* defer = nullptr, const float* nlse_nat = nullptr);
-
 
 // qhead_de.hip: the item-side backward as a persistent, statically balanced kernel (rows [0, n_items) of E_b / bias / out)
 int64_t cql_qde_ws_bytes(int64_t batch, int64_t n_items, int32_t d);
@@ -135,9 +124,6 @@ bool cql_topk4_lists_on();
 bool cql_topk4_lists_fit(int64_t n_users, int64_t n_cand, int64_t space_bytes);
 int cql_topk4_seen_lists(const int64_t* seen_off, const int32_t* seen_items, const int32_t* seen_rows, int64_t n_users,
                          int64_t n_cand, void* space, int64_t space_bytes, uint32_t* flag, hipStream_t s);
-
-int cql_qhead_argmax_beside(const uint16_t* H_b, int64_t rows, const uint16_t* E_out_b, const float* b_out, int64_t n_items,
-                            int32_t d, void* ws, int64_t ws_bytes, float* out_val, int32_t* out_idx, hipStream_t stream);
 
 int cql_qhead_argmax_step(const uint16_t* H_b, int64_t rows, const uint16_t* E_out_b, const float* b_out, int64_t n_items,
                           int32_t d, void* ws, int64_t ws_bytes, float* out_val, int32_t* out_idx, hipStream_t stream);

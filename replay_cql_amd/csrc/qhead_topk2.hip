@@ -538,8 +538,6 @@ void cql_topk2_split(int64_t n_users, int64_t n_cand, int* nsplit, int64_t* spli
   const int64_t rblks = (n_users + upb - 1) / upb;
   const int64_t stages = (n_cand + 63) / 64;
   int64_t want = (tk2_cus() + rblks - 1) / rblks;
-  static const char* env = getenv("CQL_TOPK2_NSPLIT");
-  if (env) want = atoi(env);
   if (want > stages / 8) want = stages / 8;      // at least eight stages per slice
   if (want > 16) want = 16;
   if (want < 1) want = 1;
@@ -598,8 +596,7 @@ int cql_topk2_run(const QTk2Args& a, int d, hipStream_t s) {
     attr_set = true;
   }
   const int64_t rblks = (a.n_users + 255) / 256;
-  static const bool force16 = getenv("CQL_TOPK4_KC") && atoi(getenv("CQL_TOPK4_KC")) == 16;      // A/B knob (both kernels)
-  if (a.k <= 10 && !force16)
+  if (a.k <= 10)
     hipLaunchKernelGGL((qtopk2_kernel<128, 10>), dim3((unsigned)(rblks * a.nsplit)), dim3(256), smem, s, a);
   else
     hipLaunchKernelGGL((qtopk2_kernel<128, 16>), dim3((unsigned)(rblks * a.nsplit)), dim3(256), smem, s, a);

@@ -696,8 +696,7 @@ int cql_topk4_run(const QTk2Args& a, hipStream_t s) {
   }
   const int64_t rblks = (a.n_users + 511) / 512;
   const dim3 grid((unsigned)(rblks * a.nsplit));
-  static const bool force16 = getenv("CQL_TOPK4_KC") && atoi(getenv("CQL_TOPK4_KC")) == 16;      // A/B knob
-  const bool kc12 = a.k <= 10 && !force16;      // KC = 10
+  const bool kc12 = a.k <= 10;      // KC = 10
   auto launch = [&](const QTk2Args& b, bool lists) {
     if (lists) {
       if (kc12) hipLaunchKernelGGL((qtopk4_kernel<128, true, 10>), grid, dim3(256), smem, s, b);

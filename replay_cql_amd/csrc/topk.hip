@@ -354,7 +354,7 @@ __global__ __launch_bounds__(64) void topk_select_kernel(const uint16_t* __restr
 //     cannot beat tau -- the threshold algorithm in its plain form;
 //   * "the k best of the candidates" is k rounds of wave-wide max over register-held keys, which also leaves them
 //     sorted, so the final ranking is free.
-// Same exactness argument and identical results as topk_select_kernel (tests run both).
+// Same exactness argument and identical results as topk_select_kernel.
 // =============================================================================================================
 #define TKS_MAX_K 16
 #define TKS_CB 512           // candidate capacity in LDS = 8 register slots per lane
@@ -735,10 +735,7 @@ extern "C" int cqlrec_score_topk(const uint16_t* H_b, int64_t n_users, const uin
 
 // does this shape take the on-chip-selection kernel (whose seen bitmap cqlrec_score_topk_phase can build ahead)?
 static bool tk_uses_topk2(int32_t d, int32_t k, int64_t n_cand, const int32_t* item_ids) {
-  static const int fused_off = getenv("CQL_TOPK_FUSED") && getenv("CQL_TOPK_FUSED")[0] == '0';
-  static const int force_generic0 = getenv("CQL_TOPK_GENERIC") ? 1 : 0;
-  static const int tk2_off = getenv("CQL_TOPK2") && getenv("CQL_TOPK2")[0] == '0';
-  return !tk2_off && !fused_off && !force_generic0 && item_ids == nullptr && cql_topk2_supported(d, k, n_cand);
+  return item_ids == nullptr && cql_topk2_supported(d, k, n_cand);
 }
 
 extern "C" int cqlrec_topk_seen_form(const void* ws, int64_t n_users, int64_t n_cand, int32_t d, int32_t k, int32_t* out,
@@ -789,8 +786,6 @@ extern "C" int cqlrec_score_topk_phase(const uint16_t* H_b, int64_t n_users, con
   CQL_REQUIRE(seen_off == nullptr || seen_items != nullptr, "score_topk: seen_items is NULL");
   CQL_REQUIRE(ws_bytes >= cqlrec_topk_ws_bytes(n_users, n_cand, d, k), "score_topk: workspace too small");
   hipStream_t s = (hipStream_t)stream;
-  static const int fused_off = getenv("CQL_TOPK_FUSED") && getenv("CQL_TOPK_FUSED")[0] == '0';   // A/B knob; tests run both
-  static const int force_generic0 = getenv("CQL_TOPK_GENERIC") ? 1 : 0;
   // d = 128: one wave per SIMD, selection on chip (qhead_topk2.hip)
   if (tk_uses_topk2(d, k, n_cand, item_ids)) {
     QTk2Args a2 = {};
@@ -824,7 +819,7 @@ extern "C" int cqlrec_score_topk_phase(const uint16_t* H_b, int64_t n_users, con
     return CQLREC_OK;
   }
   // candidate subsets (item_ids) keep the two-pass form: the bitmap is indexed by candidate row = global item id
-  if (k <= QS_TOPK_K && !fused_off && !force_generic0 && item_ids == nullptr && n_cand < (1ll << 31)) {
+  if (k <= QS_TOPK_K && item_ids == nullptr && n_cand < (1ll << 31)) {
     const QSplit sp = tk_fused_split(n_cand, n_users, d);
     uint32_t* bits = nullptr;
     const int64_t W = tk_bits_words(n_cand);
@@ -864,7 +859,7 @@ extern "C" int cqlrec_score_topk_phase(const uint16_t* H_b, int64_t n_users, con
   float* tm_t = (float*)((char*)ws + align256((int64_t)ngroups * n_users * 4));
   // pass 1
   const int unit = (32 * tg > QS_TI) ? 32 * tg : QS_TI;
-  const QSplit sp = qs_choose_split(n_cand, n_users, qs_spw_fwd(d), unit, QS_TARGET_BLOCKS);
+  const QSplit sp = qs_choose_split(n_cand, n_users, QS_SPW_FWD, unit, QS_TARGET_BLOCKS);
   QArgs a = {};
   a.res = H_b;
   a.n_res = n_users;
@@ -894,8 +889,7 @@ extern "C" int cqlrec_score_topk_phase(const uint16_t* H_b, int64_t n_users, con
   hipLaunchKernelGGL((topk_select_small_kernel<DD, KP>), grid, block, 0, s, H_b, n_users, E_b, b, n_cand, item_ids,  \
                      seen_off, seen_items, seen_rows, (const float*)tm_t, gstride, ngroups, tg, k, out_idx, out_val,  \
                      out_cnt)
-  static const int force_generic = getenv("CQL_TOPK_GENERIC") ? 1 : 0;   // tests run both kernels
-  const bool small_k = (k <= TKS_MAX_K) && !force_generic;
+  const bool small_k = k <= TKS_MAX_K;
 #define TK_BY_KPL(DD)                                                       \
   do {                                                                      \
     if (ngroups <= 1024) { if (small_k) TKS_LAUNCH(DD, 16); else TK_LAUNCH(DD, 16); }      \

@@ -161,7 +161,7 @@ struct SideStream {
   hipStream_t s3 = nullptr;   // sampling + sorts of the NEXT step (cqlrec_train_steps)
   hipEvent_t sorted[2] = {nullptr, nullptr};   // sorted pairs of the step with this parity are in place
   hipEvent_t forked = nullptr, fork2 = nullptr, join2 = nullptr;
-  hipEvent_t loss = nullptr, items = nullptr, dh = nullptr, eout = nullptr, presample = nullptr, adam_in = nullptr, bpro = nullptr, fwd_done = nullptr;
+  hipEvent_t loss = nullptr, items = nullptr, dh = nullptr, eout = nullptr, presample = nullptr, fwd_done = nullptr;
   bool ok = false;
   bool tried = false;
 };
@@ -299,8 +299,6 @@ SideStream& side_stream() {
             hipEventCreateWithFlags(&ss.dh, hipEventDisableTiming) == hipSuccess &&
             hipEventCreateWithFlags(&ss.eout, hipEventDisableTiming) == hipSuccess &&
             hipEventCreateWithFlags(&ss.presample, hipEventDisableTiming) == hipSuccess &&
-            hipEventCreateWithFlags(&ss.adam_in, hipEventDisableTiming) == hipSuccess &&
-            hipEventCreateWithFlags(&ss.bpro, hipEventDisableTiming) == hipSuccess &&
             hipEventCreateWithFlags(&ss.fwd_done, hipEventDisableTiming) == hipSuccess;
   }
   return ss;
@@ -388,10 +386,6 @@ int sample_ahead(const cqlrec_train_ctx* c, uint64_t step, cqlrec_stream stream,
 }
 
 int backward_items_long_impl(const cqlrec_train_ctx* c, uint64_t step, cqlrec_stream stream, CqlAdamFix* fix);
-static bool dh_early() {
-  static const bool v = !(getenv("CQL_DH_EARLY") && getenv("CQL_DH_EARLY")[0] == '0');
-  return v;
-}
 // early_items (a stream) + early_fix: the long item-side kernel of THIS step is launched on that stream as soon as the fused
 // forward has produced -lse (it needs nothing from the loss), see backward_items_impl
 // the loss VALUE of `step` from the terms its forward left (nothing in the step waits for it)
@@ -441,31 +435,12 @@ int forward_impl(const cqlrec_train_ctx* c, uint64_t step, float* loss_out, cqlr
   cqlrec_stream sb = stream;
   const bool par = ss.ok && hipEventRecord(ss.fork2, s) == hipSuccess && hipStreamWaitEvent(ss.s2, ss.fork2, 0) == hipSuccess;
   if (par) sb = (cqlrec_stream)ss.s2;
-  // CQL_ARGMAX_CORUN=1 (d = 128; A/B knob, default off): the two catalogue passes are launched TOGETHER -- the ARGMAX pass
-  // in its small-wave form (cql_qhead_argmax_beside), whose waves fit beside the fused forward's on a SIMD -- with the
-  // prologue of branch B enqueued first and branch A waiting for it in front of its Q-head pass.  Measured: the step
-  // gets 3.5 % SLOWER (0.783 vs 0.757 ms): the fused forward is bound by instruction issue, not by the MFMA pipe, and a
-  // second wave on the SIMD takes issue slots from it.
-  static const bool corun_on = getenv("CQL_ARGMAX_CORUN") && getenv("CQL_ARGMAX_CORUN")[0] == '1';
-  const bool corun = par && d == 128 && corun_on;
-  auto branch_b_prologue = [&]() -> int {
-    CQL_TRY(cqlrec_gather_pool_fwd(p.Ein_b, c->offsets, c->items, w.users, w.tpos, 1, B, W, d, nullptr, w.h0b + Bd, nullptr, sb));
-    CQL_TRY(cqlrec_gather_pool_fwd(p.tEin_b, c->offsets, c->items, w.users, w.tpos, 1, B, W, d, nullptr, w.h0b_t, nullptr, sb));
-    CQL_TRY(cqlrec_encoder_fwd(w.h0b + Bd, p.W1_b, p.b1, p.W2_b, p.b2, B, d, w.zb + Bd, w.hb + Bd, sb));
-    CQL_TRY(cqlrec_encoder_fwd(w.h0b_t, p.tW1_b, p.tb1, p.tW2_b, p.tb2, B, d, w.zb_t, w.hb_t, sb));
-    return CQLREC_OK;
-  };
-  if (corun) {
-    CQL_TRY(branch_b_prologue());
-    CQL_HIP_TRY(hipEventRecord(ss.bpro, ss.s2), "train_step_forward");
-  }
   // ---- branch A
   CQL_TRY(cqlrec_gather_pool_fwd(p.Ein_b, c->offsets, c->items, w.users, w.tpos, 0, B, W, d, w.h0_s, w.h0b, nullptr, stream));
   CQL_TRY(cqlrec_encoder_fwd(w.h0b, p.W1_b, p.b1, p.W2_b, p.b2, B, d, w.zb, w.hb, stream));
   if (g_mark_phase == 2) mark(MK_PROLOGUE, s);
   CQL_TRY(cql_qhead_fwd_lse_dh_prepare(w.ws_qb, B, N, d, s));      // (a 4-byte memset: in front of the wait, not behind it)
   if (eout_ready) CQL_HIP_TRY(hipStreamWaitEvent(s, eout_ready, 0), "train_step_forward");
-  if (corun) CQL_HIP_TRY(hipStreamWaitEvent(s, ss.bpro, 0), "train_step_forward");
   // logsumexp AND the softmax-weighted sum of item rows (the soft part of dH) in ONE pass over the catalogue
   CQL_TRY(cql_qhead_fwd_lse_dh(w.hb, B, p.Eout_b, p.b_out, N, d, w.ws_qb, w.ws_qf_bytes, w.lse, w.nlse2, s, w.nlse_nat, 1));
   if (g_mark_phase == 2) mark(MK_LSE, s);
@@ -474,18 +449,16 @@ int forward_impl(const cqlrec_train_ctx* c, uint64_t step, float* loss_out, cqlr
     CQL_HIP_TRY(hipStreamWaitEvent(early_items, ss.fwd_done, 0), "train_step_forward");
     CQL_TRY(backward_items_long_impl(c, step, (cqlrec_stream)early_items, early_fix));
   }
-  // the part of dH that needs nothing from the loss, off the chain the next prologue waits for (CQL_DH_EARLY=0: A/B)
-  if (dh_early())
-    CQL_TRY(cql_qhead_dh_finish(w.ws_qb, B, N, d, w.lse, nullptr, w.act, p.Eout_b, alpha_scale(c), w.dH, s, 1));
+  // the part of dH that needs nothing from the loss, off the chain the next prologue waits for
+  CQL_TRY(cql_qhead_dh_finish(w.ws_qb, B, N, d, w.lse, nullptr, w.act, p.Eout_b, alpha_scale(c), w.dH, s, 1));
   CQL_TRY(cqlrec_gather_dot(w.hb, p.Eout_b, p.b_out, w.act, B, d, w.q_a, stream));
   // ---- branch B
-  if (!corun) CQL_TRY(branch_b_prologue());
+  CQL_TRY(cqlrec_gather_pool_fwd(p.Ein_b, c->offsets, c->items, w.users, w.tpos, 1, B, W, d, nullptr, w.h0b + Bd, nullptr, sb));
+  CQL_TRY(cqlrec_gather_pool_fwd(p.tEin_b, c->offsets, c->items, w.users, w.tpos, 1, B, W, d, nullptr, w.h0b_t, nullptr, sb));
+  CQL_TRY(cqlrec_encoder_fwd(w.h0b + Bd, p.W1_b, p.b1, p.W2_b, p.b2, B, d, w.zb + Bd, w.hb + Bd, sb));
+  CQL_TRY(cqlrec_encoder_fwd(w.h0b_t, p.tW1_b, p.tb1, p.tW2_b, p.tb2, B, d, w.zb_t, w.hb_t, sb));
   if (eout_ready && par) CQL_HIP_TRY(hipStreamWaitEvent(ss.s2, eout_ready, 0), "train_step_forward");
-  if (corun)
-    CQL_TRY(cql_qhead_argmax_beside(w.hb + Bd, B, p.Eout_b, p.b_out, N, d, w.ws_q2, w.ws_q_bytes, w.maxv, w.a_star,
-                                    (hipStream_t)sb));
-  else
-    CQL_TRY(cql_qhead_argmax_step(w.hb + Bd, B, p.Eout_b, p.b_out, N, d, w.ws_q2, w.ws_q_bytes, w.maxv, w.a_star, (hipStream_t)sb));
+  CQL_TRY(cql_qhead_argmax_step(w.hb + Bd, B, p.Eout_b, p.b_out, N, d, w.ws_q2, w.ws_q_bytes, w.maxv, w.a_star, (hipStream_t)sb));
   CQL_TRY(cqlrec_gather_dot(w.hb_t, p.tEout_b, p.tb_out, w.a_star, B, d, w.q_targ, sb));
   if (par && (hipEventRecord(ss.join2, ss.s2) != hipSuccess || hipStreamWaitEvent(s, ss.join2, 0) != hipSuccess)) {
     cql_set_error("train_step_forward: joining the forward branches failed");
@@ -508,10 +481,6 @@ int forward_impl(const cqlrec_train_ctx* c, uint64_t step, float* loss_out, cqlr
 //     launches it as soon as the fused forward has finished, under the rest of the forward and the loss),
 // (2) the one-hot part -- the only part that needs the loss's coefficients -- is added as a segmented sum,
 // (3) the cut pieces: fix-up launch here, or left to the item-side optimizer (CqlAdamFix).
-static bool onehot_atomic() {
-  static const bool v = getenv("CQL_ONEHOT_ATOMIC") && getenv("CQL_ONEHOT_ATOMIC")[0] == '1';   // A/B knob: old order, float atomics
-  return v;
-}
 int backward_items_long_impl(const cqlrec_train_ctx* c, uint64_t step, cqlrec_stream stream, CqlAdamFix* fix) {
   const cqlrec_layout& L = c->layout;
   const int32_t B = c->batch, d = L.d;
@@ -534,14 +503,6 @@ int backward_items_onehot_impl(const cqlrec_train_ctx* c, uint64_t step, cqlrec_
 // all three in program order; defer: leave (3) to the caller's optimizer launch
 int backward_items_impl(const cqlrec_train_ctx* c, uint64_t step, cqlrec_stream stream, CqlAdamFix* defer = nullptr) {
   const cqlrec_layout& L = c->layout;
-  if (onehot_atomic()) {
-    const int32_t B = c->batch, d = L.d;
-    StepWs w = carve_step(c->ws, B, L.n_items, d, c->window, step);
-    const StepPtrs p = step_ptrs(c);
-    return cql_qhead_bwd_items_acc(w.hb, w.nlse2, w.coef, w.act, B, p.Eout_b, p.b_out, L.n_items, d, alpha_scale(c),
-                                   w.ws_qb2, w.ws_qb_bytes, c->grads + L.off_E_out, c->grads + L.off_b_out,
-                                   (hipStream_t)stream, 1, 0, -1, defer, w.nlse_nat);
-  }
   CqlAdamFix fix = {};
   CQL_TRY(backward_items_long_impl(c, step, stream, &fix));
   CQL_TRY(backward_items_onehot_impl(c, step, stream));
@@ -560,7 +521,7 @@ int backward_states_impl(const cqlrec_train_ctx* c, uint64_t step, cqlrec_stream
   // the catalogue pass was done by the forward: only the slabs are combined here (scale, exp(m - lse), + coef * E[a])
   // (the soft part was formed by the forward, right behind the catalogue pass: here only the term that needs the loss)
   CQL_TRY(cql_qhead_dh_finish(w.ws_qb, B, N, d, w.lse, w.coef, w.act, p.Eout_b, alpha_scale(c), w.dH,
-                              (hipStream_t)stream, dh_early() ? 2 : 0));
+                              (hipStream_t)stream, 2));
   SideStream& ss = side_stream();
   if (ss.ok) CQL_HIP_TRY(hipEventRecord(ss.dh, (hipStream_t)stream), "train_step_backward_rest");
   return CQLREC_OK;
@@ -574,11 +535,10 @@ int backward_chain_impl(const cqlrec_train_ctx* c, uint64_t step, cqlrec_stream 
   StepWs w = carve_step(c->ws, B, N, d, W, step);
   const StepPtrs p = step_ptrs(c);
   // The window-gather backward needs dh0 only: the weight / bias gradients of the encoder (two launches reading dA1) go
-  // to the branch stream, idle in the backward, and join before this function returns.  CQL_ENC_SPLIT=0: in line.
+  // to the branch stream, idle in the backward, and join before this function returns.
   SideStream& ss = side_stream();
   hipStream_t s = (hipStream_t)stream;
-  static const int enc_split = !(getenv("CQL_ENC_SPLIT") && getenv("CQL_ENC_SPLIT")[0] == '0');
-  const bool split = enc_split && ss.ok && ss.s2 && ss.s2 != s;
+  const bool split = ss.ok && ss.s2 && ss.s2 != s;
   CQL_TRY(cql_encoder_bwd_parts(w.dH, w.zb, w.h0b, p.W1_b, p.W2_b, B, d, w.ws_enc, w.ws_enc_bytes, c->grads + L.off_W1,
                                 c->grads + L.off_b1, c->grads + L.off_W2, c->grads + L.off_b2, w.dh0, split ? 1 : 3, s));
   if (split) {
@@ -623,7 +583,7 @@ extern "C" int cqlrec_train_step_forward_early_items(const cqlrec_train_ctx* c, 
                                                      cqlrec_stream stream, void* items_ready, cqlrec_stream items_stream) {
   CQL_TRY(check_ctx(c));
   SideStream& ss = side_stream();
-  const bool early = items_stream && items_stream != stream && need_side_streams(ss) && ss.ok && !onehot_atomic();
+  const bool early = items_stream && items_stream != stream && need_side_streams(ss) && ss.ok;
   g_early_long[step & 1] = false;
   if (!early) return forward_impl(c, step, loss_out, stream, (hipEvent_t)items_ready);
   g_early_fix[step & 1] = CqlAdamFix{};
@@ -693,7 +653,7 @@ extern "C" int cqlrec_train_steps(const cqlrec_train_ctx* c, uint64_t step0, int
     // CQL_EARLY_DE=0: the long item-side kernel behind the loss (A/B knob); default: behind the fused forward
     static const int early_de = !(getenv("CQL_EARLY_DE") && getenv("CQL_EARLY_DE")[0] == '0');
     SideStream& ss0 = side_stream();
-    const bool early = early_de && ss0.ok && ss0.s && !onehot_atomic();
+    const bool early = early_de && ss0.ok && ss0.s;
     CqlAdamFix fix = {};
     // the sum of the loss terms goes to the head of the sample-ahead stream (it has slack) when that stream is used
     bool sum_deferred = false;
@@ -722,17 +682,11 @@ extern "C" int cqlrec_train_steps(const cqlrec_train_ctx* c, uint64_t step0, int
       }
       if (sum_deferred) CQL_TRY(loss_sum_impl(c, step, loss_out ? loss_out + i : nullptr, s));      // (s3 could not take it)
       CQL_HIP_TRY(hipStreamWaitEvent(ss.s, ss.loss, 0), "train_steps");
-      // sparse scatter, then the long dE_out kernel; the sum of its cut pieces is left to the item-side Adam below
-      static const int defer_fixup = !(getenv("CQL_DEFER_FIXUP") && getenv("CQL_DEFER_FIXUP")[0] == '0');
-      if (early) {          // the long kernel is running (or done) already: the one-hot part on top, cut pieces as asked
+      // the long dE_out kernel, then the one-hot part; the sum of its cut pieces is left to the item-side Adam below
+      if (early)            // the long kernel is running (or done) already: the one-hot part on top
         CQL_TRY(backward_items_onehot_impl(c, step, (cqlrec_stream)ss.s));
-        if (!defer_fixup) {
-          CQL_TRY(cql_qde_fixup_deferred(fix, c->grads + L.off_E_out, c->grads + L.off_b_out, ss.s));
-          fix.valid = 0;
-        }
-      } else {
-        CQL_TRY(backward_items_impl(c, step, (cqlrec_stream)ss.s, defer_fixup ? &fix : nullptr));
-      }
+      else
+        CQL_TRY(backward_items_impl(c, step, (cqlrec_stream)ss.s, &fix));
       if (g_mark_phase == 1) mark(MK_DE, ss.s);
       CQL_TRY(backward_states_impl(c, step, stream));                      // dh_finish, records ss.dh
       if (g_mark_phase == 1) mark(MK_DH, s);
@@ -741,15 +695,8 @@ extern "C" int cqlrec_train_steps(const cqlrec_train_ctx* c, uint64_t step0, int
       CQL_TRY(cqlrec_train_step_update_range(c, step, L.off_W1, L.total, stream));
       CQL_TRY(cqlrec_train_step_update_range(c, step, 0, L.off_E_out, stream));
       if (g_mark_phase == 1) mark(MK_ADAM_IN, s);
-      // The two Adam launches are HBM-bound and ready at about the same time: side by side (default) each takes twice as
-      // long and the next prologue (which needs E_in / W only) starts behind both.  CQL_ADAM_SERIAL=1 runs them one after
-      // the other, state side first, so that the prologue runs under the item-side Adam -- measured no faster (0.802 vs
-      // 0.796 ms per step at cfg3).
-      static const int adam_serial = getenv("CQL_ADAM_SERIAL") && getenv("CQL_ADAM_SERIAL")[0] == '1';   // A/B knob
-      if (adam_serial) {
-        CQL_HIP_TRY(hipEventRecord(ss.adam_in, s), "train_steps");
-        CQL_HIP_TRY(hipStreamWaitEvent(ss.s, ss.adam_in, 0), "train_steps");
-      }
+      // The two Adam launches are HBM-bound and run side by side: serialising them, state side first so that the next
+      // prologue runs under the item-side Adam, was measured no faster (0.802 vs 0.796 ms per step at cfg3).
       CQL_HIP_TRY(hipStreamWaitEvent(ss.s, ss.dh, 0), "train_steps");     // dh_finish reads the E_out shadow
       fix.rows_off = 0;
       fix.cs_off = L.off_b_out - L.off_E_out;

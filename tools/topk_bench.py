@@ -1,6 +1,5 @@
-"""Top-K pass timing: python tools/topk_bench.py [--users 65536] [--items 100000] [--d 128] [--train 0|35] [--k 10]
-Run once per CQL_TOPK_FUSED setting (the knob is read once per process)."""
-import argparse, os, sys, time, torch
+"""Top-K pass timing: python tools/topk_bench.py [--users 65536] [--items 100000] [--d 128] [--train 0|35] [--k 10]"""
+import argparse, sys, time, torch
 from pathlib import Path
 sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
 from replay_cql_amd import _native as N
@@ -35,11 +34,10 @@ def phases(fn):
     N.check(lib.cqlrec_prof_enable(1), "prof"); fn(); torch.cuda.synchronize()
     ph = N.prof_read(); N.check(lib.cqlrec_prof_enable(0), "prof")
     return {k: (round(v[0], 4), v[1]) for k, v in ph.items() if v[1]}
-tag = "fused=%s" % os.environ.get("CQL_TOPK_FUSED", "1")
 for name, fn in (("no seen", lambda: core.score_topk(hb, a.k, chunk=U)),
                  ("seen", lambda: core.score_topk(hb, a.k, seen=(off, seen_items), chunk=U)),
                  ("encode+seen (pipelined)", lambda: core.encode_topk(off, items, users, a.k, seen=(off, seen_items),
                                                                       chunk=U))):
     ms = t(fn)
-    print(f"{tag} U={U} N={NI} d={a.d} k={a.k} train={a.train} {name}: {ms:.3f} ms  {U / ms * 1e-3:.2f} M users/s  "
+    print(f"U={U} N={NI} d={a.d} k={a.k} train={a.train} {name}: {ms:.3f} ms  {U / ms * 1e-3:.2f} M users/s  "
           f"MFMA frac {2.0 * U * NI * a.d / (ms * 1e-3) / 2.5e15:.3f}  phases {phases(fn)}", flush=True)
