@@ -232,6 +232,35 @@ int cqlrec_topk_seen_form(const void* ws, int64_t n_users, int64_t n_cand, int32
                           cqlrec_stream stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * a11  Item-to-item nearest neighbours.  Takes the place of ItemVectorModel._get_nearest_items' cross join of the item
+ * vectors with a per-pair UDF (replay/models/base_rec.py:955-1030; vector_dot, vector_euclidean_distance_similarity,
+ * cosine_similarity at replay/utils.py:131, :677-685, :689-697) + the window top-k of _get_nearest_items_wrap
+ * (base_rec.py:893-926).  The queries x candidates matrix is never written.
+ *   E_b        [n_rows x d] bf16 item rows v_j (the E_out shadow); all arithmetic is fp32 on these values
+ *   norms      [n_rows] n_j = dot(j, j), written by cqlrec_item_norms
+ *   query_rows [n_query] distinct rows to find neighbours of;  cand_rows [n_cand] distinct rows to choose from
+ *              (NULL: every row, n_cand = n_rows).  Both hold values in [0, n_rows).
+ *   metric     CQLREC_SIM_DOT     dot(i,j)
+ *              CQLREC_SIM_COSINE  dot / (sqrtf(n_i) * sqrtf(n_j));  a pair whose denominator is 0 is not admissible
+ *              CQLREC_SIM_EUCLID  1 / (1 + sqrtf(max((n_i + n_j) - 2*dot, 0)))
+ *              in exactly this operation order, sqrtf and / correctly rounded, nothing contracted into an FMA.
+ * The pair (i, i) is never returned (base_rec.py:1015-1017); equal rows under different ids are.
+ * Output, per query: the k best (value desc, neighbour row DESC -- base_rec.py:911-917; not the predict tie rule)
+ * admissible candidates: out_idx/out_val [n_query x k] (padding: -1 / -inf) and out_cnt [n_query] = number of valid
+ * entries.  k <= 512.  Exact: group-wise upper bounds from an MFMA pass steer which candidates are re-scored, every
+ * returned value comes from the re-scoring.  No float atomics: the same call gives the same bits twice.
+ * --------------------------------------------------------------------------------------------------------- */
+#define CQLREC_SIM_DOT 0
+#define CQLREC_SIM_COSINE 1
+#define CQLREC_SIM_EUCLID 2
+#define CQLREC_ITEM_KNN_MAX_K 512
+int cqlrec_item_norms(const uint16_t* E_b, int64_t n_rows, int32_t d, float* norms, cqlrec_stream stream);
+int64_t cqlrec_item_knn_ws_bytes(int64_t n_query, int64_t n_cand, int32_t d, int32_t k); /* [host]; 0: bad arguments */
+int cqlrec_item_knn(const uint16_t* E_b, const float* norms, int64_t n_rows, int32_t d, const int32_t* query_rows,
+                    int64_t n_query, const int32_t* cand_rows, int64_t n_cand, int32_t metric, int32_t k, void* ws,
+                    int64_t ws_bytes, int32_t* out_idx, float* out_val, int32_t* out_cnt, cqlrec_stream stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * a8  Whole training step = TorchRecommender._run_train_step (replay/models/base_torch_rec.py:32-39) without
  * the per-step host sync.  The step is split in two so that a data-parallel caller can all-reduce ctx.grads
  * (RCCL) between them; losses[] receives one float per step.

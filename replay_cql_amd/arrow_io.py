@@ -127,3 +127,18 @@ def recs_to_arrow(users: torch.Tensor, idx: torch.Tensor, val: torch.Tensor, cnt
     if idx.is_cuda:
         torch.cuda.current_stream(idx.device).synchronize()          # the only host wait of the egress
     return pa.RecordBatch.from_arrays([pa.array(h.numpy()) for h in host], schema=REC_SCHEMA)
+
+
+def neighbours_schema(metric: str) -> pa.Schema:
+    """[item_idx, neighbour_item_idx, <metric>]: the value column is named after the metric
+    (replay/models/base_rec.py:910, :920-926)."""
+    return pa.schema([("item_idx", pa.int32()), ("neighbour_item_idx", pa.int32()), (metric, pa.float64())])
+
+
+def neighbours_to_arrow(items: torch.Tensor, idx: torch.Tensor, val: torch.Tensor, cnt: torch.Tensor,
+                        metric: str) -> pa.RecordBatch:
+    """Device nearest-items block ([n] query item ids, [n x k] neighbour ids / values, [n] valid counts) -> RecordBatch
+    with neighbours_schema(metric), rows in (query item, value desc, neighbour id desc) order; the egress of
+    recs_to_arrow under other column names."""
+    rb = recs_to_arrow(items, idx, val, cnt)
+    return pa.RecordBatch.from_arrays(rb.columns, schema=neighbours_schema(metric))

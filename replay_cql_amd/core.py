@@ -657,3 +657,57 @@ class CQLCore:
                                            self.theta.data_ptr() + 4 * lay.off_b_out, _ptr(item_ids), hb.shape[0], h.d,
                                            _ptr(out), _stream()), "gather_dot")
         return out
+
+    ITEM_KNN_METRICS = {"dot_product": N.SIM_DOT, "cosine_similarity": N.SIM_COSINE,
+                        "euclidean_distance_sim": N.SIM_EUCLID}
+    ITEM_KNN_MAX_K = N.ITEM_KNN_MAX_K
+    ITEM_KNN_CHUNK = 16384      # query items per launch: bounds the workspace (one float per query and 32+ candidates, twice)
+
+    def item_norms(self) -> torch.Tensor:
+        """fp32 squared norms of the bf16 shadow rows of E_out (what item_knn's cosine / euclidean values are made of)."""
+        lay = self.layout
+        norms = torch.empty((self.n_items,), dtype=torch.float32, device=self.device)
+        N.check(self.lib.cqlrec_item_norms(self.theta_b.data_ptr() + 2 * lay.off_E_out, self.n_items, self.hyper.d,
+                                           _ptr(norms), _stream()), "item_norms")
+        return norms
+
+    def item_knn(self, query_ids: torch.Tensor, k: int, metric: str, cand_ids: Optional[torch.Tensor] = None,
+                 chunk: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """The k nearest items of every query item among the candidates (None: every row of the catalogue) by `metric`
+        ('dot_product', 'cosine_similarity', 'euclidean_distance_sim'; replay/models/base_rec.py:984-993), computed on
+        the bf16 shadow rows of E_out -- the operand the model scores with, not the fp32 masters `_get_features`
+        returns.  query_ids / cand_ids: distinct item ids in [0, n_items).  Order per query item: value descending, then
+        neighbour id DESCENDING (base_rec.py:911-917); the query item itself is never its own neighbour; under cosine a
+        pair with a zero denominator (an all-zero row) is left out.  k is clamped to the number of candidates.
+        Returns (idx int32 [n, k], val float32 [n, k], cnt int32 [n]); padding -1 / -inf.  Queries go in chunks of
+        `chunk` so that the workspace stays bounded; the result does not depend on the chunking."""
+        if metric not in self.ITEM_KNN_METRICS:
+            raise NotImplementedError(f"{metric} metric is not implemented, valid metrics are "
+                                      "'euclidean_distance_sim', 'cosine_similarity', 'dot_product'")
+        lay, d = self.layout, self.hyper.d
+        q = torch.as_tensor(query_ids).to(device=self.device, dtype=torch.int32).contiguous()
+        c = None if cand_ids is None else torch.as_tensor(cand_ids).to(device=self.device, dtype=torch.int32).contiguous()
+        n, n_cand = q.numel(), (self.n_items if c is None else c.numel())
+        k = min(int(k), n_cand)
+        if k > N.ITEM_KNN_MAX_K:
+            raise ValueError(f"k = {k} is above the nearest-items kernel's limit of {N.ITEM_KNN_MAX_K}")
+        out_idx = torch.empty((n, max(k, 0)), dtype=torch.int32, device=self.device)
+        out_val = torch.empty((n, max(k, 0)), dtype=torch.float32, device=self.device)
+        out_cnt = torch.zeros((n,), dtype=torch.int32, device=self.device)
+        if n == 0 or k <= 0:
+            return out_idx, out_val, out_cnt
+        lim = torch.stack([q.min(), q.max()] + ([] if c is None else [c.min(), c.max()])).cpu().tolist()   # one small sync
+        if min(lim) < 0 or max(lim) >= self.n_items:
+            raise ValueError(f"item ids must lie in [0, {self.n_items})")
+        norms = self.item_norms()
+        chunk = max(1, min(int(chunk or self.ITEM_KNN_CHUNK), n))
+        ws_bytes = int(self.lib.cqlrec_item_knn_ws_bytes(chunk, n_cand, d, k))
+        ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=self.device)
+        E_ptr = self.theta_b.data_ptr() + 2 * lay.off_E_out
+        for lo in range(0, n, chunk):
+            hi = min(n, lo + chunk)
+            N.check(self.lib.cqlrec_item_knn(E_ptr, _ptr(norms), self.n_items, d, q.data_ptr() + 4 * lo, hi - lo, _ptr(c),
+                                             n_cand, self.ITEM_KNN_METRICS[metric], k, _ptr(ws), ws_bytes,
+                                             out_idx.data_ptr() + 4 * lo * k, out_val.data_ptr() + 4 * lo * k,
+                                             out_cnt.data_ptr() + 4 * lo, _stream()), "item_knn")
+        return out_idx, out_val, out_cnt

@@ -28,6 +28,7 @@ class CQL(PandasRecommender):
 
     can_predict_cold_users = False   # users without history in `log` yield no rows (the MultVAE behaviour,
     can_predict_cold_items = False   # replay/models/mult_vae.py:138 + base_torch_rec.py:141-145)
+    can_predict_item_to_item = True  # get_nearest_items over the rows of E_out, as ItemVectorModel (base_rec.py:955-1030)
     _search_space = {
         "learning_rate": {"type": "loguniform", "args": [1e-4, 1e-2]},
         "alpha": {"type": "loguniform", "args": [0.05, 5.0]},
@@ -333,6 +334,67 @@ class CQL(PandasRecommender):
         g_off, g_items, _ = D.build_csr_device(rows_h, gt["item_idx"].to_numpy(), None, None, len(gt_users), device=dev)
         g_items = torch.cat([g_items, torch.zeros(1, dtype=torch.int32, device=dev)])
         return evaluate_topk(rec, g_off, g_items, ks)
+
+    # ------------------------------------------------------------------------------------------- item to item
+    def _nearest_items_device(self, items, k: int, metric: Optional[str], candidates):
+        """get_nearest_items on the device.  items / candidates: anything arrow_io.ids_to_device takes (candidates None:
+        the items seen at fit).  Returns (query item ids int32 [n] ascending, idx int32 [n, k'], val float32 [n, k'],
+        cnt int32 [n]) with k' = min(k, number of candidates)."""
+        from . import arrow_io as A
+        if metric is None:
+            raise ValueError(f"Distance metric is required to get nearest items with {self} model")
+        if metric not in CQLCore.ITEM_KNN_METRICS:
+            raise NotImplementedError(f"{metric} metric is not implemented, valid metrics are "
+                                      "'euclidean_distance_sim', 'cosine_similarity', 'dot_product'")
+        core = self._require_fit()
+        dev = core.device
+        fit_i = torch.unique(torch.as_tensor(self.fit_items["item_idx"].to_numpy().astype(np.int64)).to(dev))
+        fit_i = fit_i[(fit_i >= 0) & (fit_i < core.n_items)]
+        query = A.ids_to_device(items, "item_idx", dev)                  # de-duplicated, ascending
+        query = query[torch.isin(query, fit_i)]                          # inner join with the item vectors (:996-1003)
+        cand = fit_i if candidates is None else A.ids_to_device(candidates, "item_idx", dev)
+        cand = cand[torch.isin(cand, fit_i)]                             # (:1009-1013)
+        k = min(int(k), int(cand.numel()))
+        if query.numel() == 0 or k <= 0:
+            z = torch.zeros((0, max(k, 0)), device=dev)
+            return (torch.zeros(0, dtype=torch.int32, device=dev), z.to(torch.int32), z.to(torch.float32),
+                    torch.zeros(0, dtype=torch.int32, device=dev))
+        q32 = query.to(torch.int32)
+        idx, val, cnt = core.item_knn(q32, k, metric, cand_ids=None if cand.numel() == core.n_items else cand)
+        return q32, idx, val, cnt
+
+    def nearest_items_arrow(self, items, k: int, metric: Optional[str] = "cosine_similarity", candidates=None):
+        """get_nearest_items() for Arrow callers: items / candidates = batches or tables with an item_idx column, arrays
+        or iterables of ids.  Returns ONE pyarrow.RecordBatch [item_idx:int32, neighbour_item_idx:int32,
+        <metric>:float64] with at most k rows per query item, ordered (item_idx, value desc, neighbour id DESC) -- what
+        `_get_nearest_items_wrap` over ItemVectorModel._get_nearest_items delivers (replay/models/base_rec.py:893-926,
+        :968-1030) without the item x item cross join.
+
+        The vectors are the bf16 shadow rows of E_out -- the operand the model itself scores with -- not the fp32
+        masters `_get_features` hands out; dots and norms are accumulated in fp32.  One deliberate deviation: under
+        cosine_similarity a pair whose denominator is 0 (an all-zero row) is left out; the reference would produce NaN
+        there, which Spark sorts above every number."""
+        from . import arrow_io as A
+        return A.neighbours_to_arrow(*self._nearest_items_device(items, k, metric, candidates), metric=metric)
+
+    def _get_nearest_items_wrap(self, items, k: int, metric: Optional[str] = "cosine_similarity", candidates=None):
+        """The wrapper of base_rec.py:893-926 without its full similarity frame: ids, then the device top-k."""
+        items = self._get_ids(items, "item_idx")["item_idx"].to_numpy()
+        if candidates is not None:
+            candidates = self._get_ids(candidates, "item_idx")["item_idx"].to_numpy()
+        return self.nearest_items_arrow(items, k, metric, candidates).to_pandas()
+
+    def _get_nearest_items(self, items: pd.DataFrame, metric: Optional[str] = None,
+                           candidates: Optional[pd.DataFrame] = None) -> pd.DataFrame:
+        """Every admissible pair as [item_idx_one, item_idx_two, <metric>] (base_rec.py:968-1030) -- only for candidate
+        sets small enough to materialise; get_nearest_items itself never builds this frame."""
+        n_cand = len(self.fit_items) if candidates is None else len(candidates)
+        if n_cand > CQLCore.ITEM_KNN_MAX_K:
+            raise ValueError(f"the full similarity frame is only built for at most {CQLCore.ITEM_KNN_MAX_K} candidates "
+                             f"(got {n_cand}); use get_nearest_items(items, k, metric, candidates)")
+        out = self.nearest_items_arrow(items["item_idx"].to_numpy(), max(n_cand, 1), metric,
+                                       None if candidates is None else candidates["item_idx"].to_numpy()).to_pandas()
+        return out.rename(columns={"item_idx": "item_idx_one", "neighbour_item_idx": "item_idx_two"})
 
     def _get_features(self, ids: pd.DataFrame, features):
         """Item embeddings (rows of E_out) in the shape ALS uses (replay/models/als.py:137-148)."""

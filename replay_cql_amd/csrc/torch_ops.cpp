@@ -1,6 +1,6 @@
 // torch.ops.cqlrec.* -- PyTorch-ROCm custom-op registration of the hot path ("PyTorch-ROCm custom ops in one
 // .so, namespace torch.ops.cqlrec": gather_pool_fwd/bwd, qhead_lse_fwd/bwd, qhead_gather_dot, score_topk,
-// fused_adam_ema).  A thin shim: every op validates its tensors (TORCH_CHECK -> Python RuntimeError), allocates its
+// fused_adam_ema; item_knn since).  A thin shim: every op validates its tensors (TORCH_CHECK -> Python RuntimeError), allocates its
 // outputs and scratch through torch's caching allocator, and calls the C ABI of include/cqlrec.h on the CURRENT HIP
 // stream.  No arithmetic lives here; the kernels are in libcqlrec.so, which this library links against.
 #include <ATen/ATen.h>
@@ -201,6 +201,40 @@ std::tuple<Tensor, Tensor, Tensor> score_topk(const Tensor& H_b, const Tensor& E
   return {idx, val, cnt};
 }
 
+// (idx [n x k], val [n x k], cnt [n]): the k nearest (value desc, neighbour row DESC) candidate rows of every query row of
+// the bf16 item table E_b; metric 0 = dot_product, 1 = cosine_similarity, 2 = euclidean_distance_sim (CQLREC_SIM_*)
+std::tuple<Tensor, Tensor, Tensor> item_knn(const Tensor& E_b, const Tensor& query_rows, int64_t k, int64_t metric,
+                                            const optional<Tensor>& cand_rows, const optional<Tensor>& norms) {
+  OpDevice dev_(E_b);
+  dev_contig(E_b, at::kBFloat16, "E_b");
+  dev_contig(query_rows, at::kInt, "query_rows");
+  const bool has_cand = cand_rows.has_value() && cand_rows->defined();
+  if (has_cand) dev_contig(*cand_rows, at::kInt, "cand_rows");
+  TORCH_CHECK(E_b.dim() == 2 && query_rows.dim() == 1, "shapes");
+  TORCH_CHECK(k > 0 && k <= CQLREC_ITEM_KNN_MAX_K, "k must be in 1..", CQLREC_ITEM_KNN_MAX_K);
+  const int64_t n = query_rows.numel(), nr = E_b.size(0), d = E_b.size(1), nc = has_cand ? cand_rows->numel() : nr;
+  Tensor nrm;
+  if (norms.has_value() && norms->defined()) {
+    dev_contig(*norms, at::kFloat, "norms");
+    TORCH_CHECK(norms->numel() == nr, "norms must hold one value per row of E_b");
+    nrm = *norms;
+  } else {
+    nrm = at::empty({nr}, E_b.options().dtype(at::kFloat));
+    if (nr) ok(cqlrec_item_norms(bf(E_b), nr, (int32_t)d, nrm.data_ptr<float>(), cur_stream(E_b)), "item_norms");
+  }
+  Tensor idx = at::empty({n, k}, nrm.options().dtype(at::kInt)), val = at::empty({n, k}, nrm.options()),
+         cnt = at::empty({n}, nrm.options().dtype(at::kInt));
+  if (n) {
+    const int64_t wsb = cqlrec_item_knn_ws_bytes(n, nc, (int32_t)d, (int32_t)k);
+    Tensor ws = scratch(wsb, E_b);
+    ok(cqlrec_item_knn(bf(E_b), nrm.data_ptr<float>(), nr, (int32_t)d, query_rows.data_ptr<int32_t>(), n,
+                       optp<int32_t>(cand_rows), nc, (int32_t)metric, (int32_t)k, ws.data_ptr(), wsb,
+                       idx.data_ptr<int32_t>(), val.data_ptr<float>(), cnt.data_ptr<int32_t>(), cur_stream(E_b)),
+       "item_knn");
+  }
+  return {idx, val, cnt};
+}
+
 // in place: Adam + Polyak target + both bf16 shadows (+ gradient zeroing) over flat buffers
 void fused_adam_ema(Tensor theta, Tensor grads, Tensor m, Tensor v, Tensor target, Tensor theta_b, Tensor target_b,
                     double step_size, double sqrt_bc2, double beta1, double beta2, double eps, double tau,
@@ -232,6 +266,8 @@ TORCH_LIBRARY(cqlrec, m) {
   m.def("qhead_gather_dot(Tensor H_b, Tensor E_b, Tensor b, Tensor idx) -> Tensor");
   m.def("score_topk(Tensor H_b, Tensor E_b, Tensor b, int k, Tensor? item_ids=None, Tensor? seen_off=None, "
         "Tensor? seen_items=None, Tensor? seen_rows=None) -> (Tensor, Tensor, Tensor)");
+  m.def("item_knn(Tensor E_b, Tensor query_rows, int k, int metric, Tensor? cand_rows=None, Tensor? norms=None) "
+        "-> (Tensor, Tensor, Tensor)");
   m.def("fused_adam_ema(Tensor(a!) theta, Tensor(b!) grads, Tensor(c!) m, Tensor(d!) v, Tensor(e!) target, "
         "Tensor(f!) theta_b, Tensor(g!) target_b, float step_size, float sqrt_bc2, float beta1, float beta2, float eps, "
         "float tau, bool zero_grads) -> ()");
@@ -246,5 +282,6 @@ TORCH_LIBRARY_IMPL(cqlrec, CUDA, m) {
   m.impl("qhead_lse_bwd", &qhead_lse_bwd);
   m.impl("qhead_gather_dot", &qhead_gather_dot);
   m.impl("score_topk", &score_topk);
+  m.impl("item_knn", &item_knn);
   m.impl("fused_adam_ema", &fused_adam_ema);
 }

@@ -238,8 +238,34 @@ class PandasRecommender(ABC):
         self.logger.info("get_features method is not defined for the model %s. Features will not be returned.", str(self))
         return None, None
 
+    # -------------------------------------------------------------------------------- item to item
     def get_nearest_items(self, items, k: int, metric: Optional[str] = "cosine_similarity", candidates=None):
-        raise NotImplementedError(f"item-to-item prediction is not implemented for {self}")   # base_rec.py:934-936
+        """The k most similar items of each of `items` by `metric` ('euclidean_distance_sim', 'cosine_similarity',
+        'dot_product'); `candidates`: the items to choose from (None: the items seen at fit).  Columns
+        [item_idx, neighbour_item_idx, <metric>], a bigger value meaning greater similarity (base_rec.py:851-887)."""
+        if not self.can_predict_item_to_item:
+            raise NotImplementedError(f"item-to-item prediction is not implemented for {self}")   # base_rec.py:934-936
+        if metric is None:
+            raise ValueError(f"Distance metric is required to get nearest items with {self} model")   # :871-875
+        return self._get_nearest_items_wrap(items=items, k=k, metric=metric, candidates=candidates)
+
+    def _get_nearest_items_wrap(self, items, k: int, metric: Optional[str] = "cosine_similarity", candidates=None):
+        """ids, `_get_nearest_items`, then the k best rows per item by (value desc, neighbour id DESC): the order of
+        base_rec.py:911-917 -- not the predict tie rule -- and the column renames of :920-926."""
+        items = self._get_ids(items, "item_idx")
+        if candidates is not None:
+            candidates = self._get_ids(candidates, "item_idx")
+        full = self._get_nearest_items(items=items, metric=metric, candidates=candidates)
+        rel = metric if metric is not None else "similarity"
+        top = get_top_k(full, "item_idx_one", [(rel, False), ("item_idx_two", False)], k)
+        top = top.rename(columns={"item_idx_two": "neighbour_item_idx", "item_idx_one": "item_idx"})
+        return top[["item_idx", "neighbour_item_idx", rel]].reset_index(drop=True).astype(
+            {"item_idx": np.int32, "neighbour_item_idx": np.int32, rel: np.float64})
+
+    def _get_nearest_items(self, items: pd.DataFrame, metric: Optional[str] = None,
+                           candidates: Optional[pd.DataFrame] = None) -> pd.DataFrame:
+        """Every admissible pair as [item_idx_one, item_idx_two, <metric>] (base_rec.py:928-936, :968-1030)."""
+        raise NotImplementedError(f"item-to-item prediction is not implemented for {self}")
 
     # -------------------------------------------------------------------------------- output
     @staticmethod

@@ -96,6 +96,7 @@ def build_adapter(Recommender, State, REC_SCHEMA):
 
         can_predict_cold_users = False
         can_predict_cold_items = False
+        can_predict_item_to_item = True
         _search_space = _ArrayCQL._search_space
 
         # pylint: disable=too-many-arguments
@@ -151,7 +152,11 @@ def build_adapter(Recommender, State, REC_SCHEMA):
             return State().session.createDataFrame(pdf, schema=schema)
 
         def _recs_to_spark(self, rb):
-            """REC_SCHEMA record batch -> Spark DataFrame.  `SparkSession.createDataFrame(pyarrow.Table)` is public API
+            return self._batch_to_spark(rb, REC_SCHEMA)
+
+        def _batch_to_spark(self, rb, schema):
+            """Record batch -> Spark DataFrame (`schema`: REC_SCHEMA for recommendations, None: the batch's own columns, the
+            nearest-items frame).  `SparkSession.createDataFrame(pyarrow.Table)` is public API
             since PySpark 4.0 (the release that added `DataFrame.toArrow`): there the U x k block goes over as Arrow
             data, no pandas in between.  Older sessions reject a Table with a TypeError (nothing was created): they get
             the pandas frame, which PySpark 3.x converts through Arrow itself under the session flag
@@ -161,10 +166,10 @@ def build_adapter(Recommender, State, REC_SCHEMA):
             key = type(session)
             known = _ARROW_EGRESS.get(key)
             if known is True:
-                return session.createDataFrame(pa.Table.from_batches([rb]), schema=REC_SCHEMA)
+                return session.createDataFrame(pa.Table.from_batches([rb]), schema=schema)
             if known is None:           # first use with this kind of session: try, remember
                 try:
-                    out = session.createDataFrame(pa.Table.from_batches([rb]), schema=REC_SCHEMA)
+                    out = session.createDataFrame(pa.Table.from_batches([rb]), schema=schema)
                     _ARROW_EGRESS[key] = True
                     return out
                 except Exception as exc:  # pylint: disable=broad-except
@@ -172,7 +177,7 @@ def build_adapter(Recommender, State, REC_SCHEMA):
                     # route below re-raises a genuine failure
                     _ARROW_EGRESS[key] = False
                     self.logger.debug("createDataFrame(pyarrow.Table) not supported by this session (%r): pandas egress", exc)
-            return self._to_spark(_batch_to_pandas(rb), REC_SCHEMA)
+            return self._to_spark(_batch_to_pandas(rb), schema)
 
         # pylint: disable=too-many-arguments
         def _predict(self, log, k, users, items, user_features=None, item_features=None, filter_seen_items=True):
@@ -188,6 +193,23 @@ def build_adapter(Recommender, State, REC_SCHEMA):
             out = self._impl._predict_pairs(pairs.select("user_idx", "item_idx").toPandas(),
                                             log.select("user_idx", "item_idx", "timestamp").toPandas())
             return self._to_spark(out, REC_SCHEMA)
+
+        # pylint: disable=arguments-differ
+        def _get_nearest_items_wrap(self, items, k, metric="cosine_similarity", candidates=None):
+            """base_rec.py:893-926 without the item x item frame: the ids go to the device, the k best neighbours per
+            item (value desc, neighbour id desc) come back as one Arrow batch [item_idx, neighbour_item_idx, <metric>]."""
+            items = _ids(self._get_ids(items, "item_idx"), "item_idx")
+            if candidates is not None:
+                candidates = _ids(self._get_ids(candidates, "item_idx"), "item_idx")
+            return self._batch_to_spark(self._impl.nearest_items_arrow(items, int(k), metric, candidates), None)
+
+        def _get_nearest_items(self, items, metric=None, candidates=None):
+            """The full [item_idx_one, item_idx_two, <metric>] frame of ItemVectorModel._get_nearest_items
+            (base_rec.py:968-1030), only for candidate sets small enough to materialise (else a ValueError that points
+            to get_nearest_items, which never builds it)."""
+            out = self._impl._get_nearest_items(items.select("item_idx").toPandas(), metric,
+                                                None if candidates is None else candidates.select("item_idx").toPandas())
+            return self._to_spark(out)
 
         def _get_features(self, ids, features):
             vecs, rank = self._impl._get_features(ids.toPandas(), None)

@@ -3,7 +3,7 @@
 include/cqlrec.h on the current HIP stream):
 
     gather_pool_fwd, gather_pool_bwd, qhead_lse_fwd, qhead_argmax_fwd, qhead_lse_bwd, qhead_gather_dot, score_topk,
-    fused_adam_ema
+    fused_adam_ema, item_knn
 
 `load()` makes them available; there is no fallback implementation -- a missing library raises."""
 from __future__ import annotations
@@ -11,7 +11,7 @@ from __future__ import annotations
 from pathlib import Path
 
 OPS = ("gather_pool_fwd", "gather_pool_bwd", "qhead_lse_fwd", "qhead_argmax_fwd", "qhead_lse_bwd", "qhead_gather_dot",
-       "score_topk", "fused_adam_ema")
+       "score_topk", "fused_adam_ema", "item_knn")
 _LIB = Path(__file__).resolve().parent / "libcqlrec_torch.so"
 _loaded = False
 
