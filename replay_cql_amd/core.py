@@ -523,6 +523,11 @@ class CQLCore:
         else:
             n = hb.shape[0]
         if k > self.MAX_FUSED_K:
+            if callable(hb):        # every part ranks the same users: materialise their state vectors once
+                if n == 0:
+                    hb = torch.empty((0, h.d), dtype=torch.bfloat16, device=self.device)
+                else:
+                    hb = hb(0, n)
             return self._score_topk_large_k(hb, k, cand_items, seen, seen_rows, chunk)
         eb, fp = self.theta_b.data_ptr(), self.theta.data_ptr()
         if cand_items is None:

@@ -303,6 +303,44 @@ def topk_rule_violations(idx, val, cnt, Q, k, set_tol=1e-4, val_tol=1e-3):
     return np.asarray(bad, dtype=np.int64), swaps
 
 
+TOPK_IDX_SENTINEL, TOPK_VAL_SENTINEL, TOPK_CNT_SENTINEL = -77, 12345.0, -5
+
+
+class TopkDevice:
+    """One top-K problem on the device, for several cqlrec_score_topk calls (other k, with / without item_ids): the
+    candidate rows E_c / b_c as the kernel gets them, ids = their global ids (None: candidate row = id), seen =
+    (offsets int64, ascending global ids int32) with seen_rows (None: row u is user u's)."""
+
+    def __init__(self, lib, Hb, E_c, b_c, ids=None, seen=None, seen_rows=None):
+        self.lib, self.n_users, self.d = lib, Hb.shape[0], Hb.shape[1]
+        self.n_cand = E_c.shape[0]
+        self.H, self.E, self.b = bf16_dev(Hb), bf16_dev(E_c), dev(np.asarray(b_c, dtype=np.float32))
+        self.ids = None if ids is None else dev(np.asarray(ids, dtype=np.int32))
+        self.so = self.si = self.rows = None
+        if seen is not None:
+            self.so = dev(np.asarray(seen[0], dtype=np.int64))
+            self.si = dev(np.concatenate([np.asarray(seen[1], dtype=np.int32), np.zeros(1, np.int32)]))
+            self.rows = None if seen_rows is None else dev(np.asarray(seen_rows, dtype=np.int32))
+
+    def run(self, k, use_ids=True, guard_bytes=0):
+        """(idx, val, cnt) as numpy.  Outputs are pre-filled with sentinels, so an entry the pass left unwritten shows;
+        guard_bytes > 0: a poisoned region right behind the declared workspace size must come back intact."""
+        nb = int(self.lib.cqlrec_topk_ws_bytes(self.n_users, self.n_cand, self.d, k))
+        ws = ws_bytes_tensor(nb + guard_bytes)
+        if guard_bytes:
+            ws[nb:] = 0xFF                         # "every item seen" if a live row ever read it as bitmap
+        out_idx = torch.full((self.n_users, k), TOPK_IDX_SENTINEL, dtype=torch.int32, device=DEV)
+        out_val = torch.full((self.n_users, k), TOPK_VAL_SENTINEL, dtype=torch.float32, device=DEV)
+        out_cnt = torch.full((self.n_users,), TOPK_CNT_SENTINEL, dtype=torch.int32, device=DEV)
+        N.check(self.lib.cqlrec_score_topk(ptr(self.H), self.n_users, ptr(self.E), ptr(self.b), self.n_cand, self.d,
+                                           ptr(self.ids) if use_ids else None, ptr(self.so), ptr(self.si), ptr(self.rows), k,
+                                           ptr(ws), nb, ptr(out_idx), ptr(out_val), ptr(out_cnt), stream()))
+        sync()
+        if guard_bytes:
+            assert bool((ws[nb:] == 0xFF).all()), "the pass wrote behind the workspace size it asked for"
+        return out_idx.cpu().numpy(), out_val.cpu().numpy(), out_cnt.cpu().numpy()
+
+
 def topk_case(lib, n_users, Nn, d, k, dyadic, seed, with_seen, cand=None, guard_bytes=0):
     Hb, Eb, b = qhead_inputs(n_users, Nn, d, dyadic, seed)
     rng = np.random.default_rng(seed)
@@ -331,21 +369,234 @@ def topk_case(lib, n_users, Nn, d, k, dyadic, seed, with_seen, cand=None, guard_
     kk = min(k, len(ids))
     idx_c, val_ref = O.topk_rows(Q, kk)
     idx_ref = np.where(np.isfinite(val_ref), ids[idx_c], -1)
+    case = TopkDevice(lib, Hb, E_c, b_c, ids=None if cand is None else ids,
+                      seen=None if seen_off is None else (seen_off, seen_items))
+    out_idx, out_val, out_cnt = case.run(k, guard_bytes=guard_bytes)
+    return out_idx, out_val, out_cnt, idx_ref, val_ref, Q
 
-    nb = int(lib.cqlrec_topk_ws_bytes(n_users, len(ids), d, k))
-    ws = ws_bytes_tensor(nb + guard_bytes)         # guard_bytes > 0: a poisoned region right behind the declared size
-    if guard_bytes:
-        ws[nb:] = 0xFF                             # "every item seen" if a live row ever read it as bitmap
-    out_idx = torch.empty((n_users, k), dtype=torch.int32, device=DEV)
-    out_val = torch.empty((n_users, k), dtype=torch.float32, device=DEV)
-    out_cnt = torch.empty(n_users, dtype=torch.int32, device=DEV)
-    d_ids = None if cand is None else dev(ids)
-    d_so = None if seen_off is None else dev(seen_off)
-    d_si = None if seen_items is None else dev(np.concatenate([seen_items, np.zeros(1, np.int32)]))
-    N.check(lib.cqlrec_score_topk(ptr(bf16_dev(Hb)), n_users, ptr(bf16_dev(E_c)), ptr(dev(b_c)), len(ids), d, ptr(d_ids),
-                                  ptr(d_so), ptr(d_si), None, k, ptr(ws), nb, ptr(out_idx), ptr(out_val), ptr(out_cnt),
-                                  stream()))
-    sync()
-    if guard_bytes:
-        assert bool((ws[nb:] == 0xFF).all()), "the pass wrote behind the workspace size it asked for"
-    return out_idx.cpu().numpy(), out_val.cpu().numpy(), out_cnt.cpu().numpy(), idx_ref, val_ref, Q
+
+# ---- top-K certificate against float64 ---------------------------------------------------------------------------------
+# The blanket "1e-4 around the k-th score" rule above is ~3 000 ulp at |score| = 0.5 and unusable for large scores.  The
+# certificate's only slack is eps, the worst-case bound of ANY fp32 summation order of the d products and the bias:
+#     eps[u, c] = (d + 1) 2^-24 (sum_i |Hb[u,i] Eb[c,i]| + |b[c]|)
+# (products of two bf16 values are exact in fp32; every one of the d additions rounds by at most 2^-24 of a partial sum
+# that is itself at most (1 + 2^-24)^d times the sum of the absolute terms).  tests/test_topk_certificate_cpu.py is what
+# justifies it: three fp32 orders accepted (they stay below 0.1 eps), every listed fault rejected.
+TOPK_CERT_BLOCK = 64 * 262144          # float64 elements of the largest users x items block the certificate holds
+TOPK_KINDS = ("plain", "neg", "straddle", "wide")
+
+
+def topk_inputs(kind, n_users, Nn, d, seed, k_ref=16):
+    """bf16-rounded (Hb, Eb) and an fp32 bias of the non-dyadic input kinds of the top-K tests:
+    plain     qhead_inputs(..., dyadic=False)
+    neg       plain, b -= 40: every score negative
+    straddle  plain, b shifted so that the k_ref-th best score changes sign across users (median of them at 0)
+    wide      plain, every E row scaled by exp(1.5 N(0,1)): group maxima spread over many exponents"""
+    Hb, Eb, b = qhead_inputs(n_users, Nn, d, False, seed)
+    if kind == "neg":
+        b = (b - np.float32(40.0)).astype(np.float32)
+    elif kind == "wide":
+        s = np.exp(1.5 * np.random.default_rng(seed + 1).standard_normal(Nn)).astype(np.float32)
+        Eb = O.bf16_round(Eb * s[:, None])
+    elif kind == "straddle":
+        Q = Hb @ Eb.T + b
+        kk = min(k_ref, Nn)
+        kth = -np.partition(-Q, kk - 1, axis=1)[:, kk - 1]
+        b = (b - np.float32(np.median(kth))).astype(np.float32)
+    elif kind != "plain":
+        raise ValueError(kind)
+    return Hb, Eb, b
+
+
+def tk_geometry(n_cand, k):
+    """(kernel, KPL, CB, tg, ngroups) of the two-pass family for n_cand candidates at k -- the arithmetic of tk_tile_groups /
+    TK_BY_KPL / TK_LAUNCH in csrc/topk.hip, restated (the tests assert their case tables against it)."""
+    tiles = (n_cand + 31) // 32
+    tg = 1
+    while (tiles + tg - 1) // tg > 4096:
+        tg *= 2
+    ngroups = (tiles + tg - 1) // tg
+    kpl = 16 if ngroups <= 1024 else (32 if ngroups <= 2048 else 64)
+    if k <= 16:
+        return "small", kpl, 0, tg, ngroups
+    return "select", kpl, (1024 if k <= 512 else 4096), tg, ngroups
+
+
+class TopkReference:
+    """float64 scores and eps of one (Hb, Eb, b), one item chunk at a time; cached when the whole block is one chunk."""
+
+    def __init__(self, Hb, Eb, b):
+        self.H = np.asarray(Hb, dtype=np.float32).astype(np.float64)
+        self.Ha = np.abs(self.H)
+        self.E = np.asarray(Eb, dtype=np.float32)
+        self.b = np.asarray(b, dtype=np.float32).astype(np.float64)
+        self.n_users, self.d = self.H.shape
+        self.n_cand = self.E.shape[0]
+        self.step = max(1, TOPK_CERT_BLOCK // self.n_users)
+        self._cache = None
+
+    def blocks(self):
+        """yields (lo, hi, Q64[:, lo:hi], eps[:, lo:hi]); the arrays must not be modified"""
+        if self._cache is not None:
+            yield self._cache
+            return
+        for lo in range(0, self.n_cand, self.step):
+            hi = min(self.n_cand, lo + self.step)
+            Ec = self.E[lo:hi].astype(np.float64)
+            Q = self.H @ Ec.T
+            Q += self.b[lo:hi]
+            A = self.Ha @ np.abs(Ec).T
+            A += np.abs(self.b[lo:hi])
+            A *= (self.d + 1) * _U32
+            blk = (lo, hi, Q, A)
+            if lo == 0 and hi == self.n_cand:
+                self._cache = blk
+            yield blk
+
+
+def _cert_where(u, cs, tg):
+    cs = [int(c) for c in np.atleast_1d(cs)[:4]]
+    return f"user {int(u)} [" + ", ".join(f"c {c} /32:{c // 32} /{32 * tg}:{c // (32 * tg)}" for c in cs) + "]"
+
+
+def topk_certificate(idx, val, cnt, Hb, Eb, b, k, ids=None, seen=None, seen_rows=None, ref=None):
+    """Certificate of a block of top-k lists against float64, from the kernels' own operands: Hb [n_users, d] and
+    Eb [n_cand, d] bf16-rounded, b [n_cand] fp32 (candidate rows, compacted as the kernel got them); ids [n_cand]
+    ascending global ids of the candidate rows (None: 0..n_cand-1); seen = (offsets, ascending global ids) CSR, row
+    seen_rows[u] (None: u) is user u's.  Per user, with Q64 = Hb Eb^T + b in float64 and eps as above:
+      1. cnt == min(k, number of admissible candidates)   (admissible: a candidate row whose id is not in the seen row)
+      2. the first cnt ids are distinct and admissible; the rest of the row is exactly -1 / -inf
+      3. |val[i] - Q64[idx[i]]| <= eps[idx[i]]
+      4. the row is ordered by its own values, exactly: val non-increasing, ids ascending where values are equal
+      5. (cnt == k) every admissible candidate c outside the row has Q64[c] - eps[c] <= val[cnt - 1]
+    No excluded rows, no swap budget.  Raises AssertionError naming the worst users, their candidate rows and groups
+    (c // 32 and c // (32 tg)).  Returns {"ratio": the largest |val - Q64| / eps, "share": the share of users whose
+    k-th and (k+1)-th admissible float64 scores are closer than the sum of their eps -- the only place where (5) cannot
+    see a dropped item; from the reference alone}."""
+    idx = np.asarray(idx).astype(np.int64)
+    val = np.asarray(val, dtype=np.float32)
+    cnt = np.asarray(cnt).astype(np.int64)
+    if ref is None:
+        ref = TopkReference(Hb, Eb, b)
+    n_users, n_cand = ref.n_users, ref.n_cand
+    assert idx.shape == (n_users, k) and val.shape == (n_users, k) and cnt.shape == (n_users,)
+    tg = tk_geometry(n_cand, k)[3]
+    ids = np.arange(n_cand, dtype=np.int64) if ids is None else np.asarray(ids).astype(np.int64)
+    assert ids.shape == (n_cand,) and (n_cand < 2 or np.all(np.diff(ids) > 0)), "ids must be ascending and distinct"
+    # candidate rows excluded per user (ascending)
+    seen_pos = [np.zeros(0, np.int64)] * n_users
+    if seen is not None:
+        off, items = np.asarray(seen[0]).astype(np.int64), np.asarray(seen[1]).astype(np.int64)
+        rows = np.arange(n_users) if seen_rows is None else np.asarray(seen_rows).astype(np.int64)
+        for u in range(n_users):
+            s = items[off[rows[u]]: off[rows[u] + 1]]
+            p = np.minimum(np.searchsorted(ids, s), n_cand - 1)
+            seen_pos[u] = np.unique(p[ids[p] == s])                  # seen ids that are no candidates drop out
+    n_adm = np.array([n_cand - len(p) for p in seen_pos], dtype=np.int64)
+    fails = []
+
+    # ---- 1, 2: counts, padding, ids ------------------------------------------------------------------------------------
+    want = np.minimum(k, n_adm)
+    bad = np.nonzero(cnt != want)[0]
+    if bad.size:
+        fails.append(f"(1) count: {bad.size} users, e.g. " +
+                     "; ".join(f"user {u}: cnt {cnt[u]}, admissible {n_adm[u]}" for u in bad[:4]))
+    c_ok = np.clip(cnt, 0, k)
+    col = np.arange(k)[None, :]
+    live = col < c_ok[:, None]
+    pad_bad = np.nonzero((~live & ((idx != -1) | ~np.isneginf(val))).any(1))[0]
+    if pad_bad.size:
+        fails.append(f"(2) padding is not -1 / -inf: users {pad_bad[:6].tolist()}")
+    pos = np.searchsorted(ids, np.where(live, idx, ids[0]))
+    pos = np.minimum(pos, n_cand - 1)
+    is_cand = live & (ids[pos] == idx)
+    for u in np.nonzero((live & ~is_cand).any(1))[0][:4]:
+        fails.append(f"(2) user {u}: ids outside the candidate set: {idx[u][live[u] & ~is_cand[u]][:4].tolist()}")
+    for u in range(n_users):
+        pu = pos[u][is_cand[u]]
+        if np.unique(pu).size != pu.size:
+            vals, c = np.unique(pu, return_counts=True)
+            fails.append("(2) duplicated: " + _cert_where(u, vals[c > 1], tg))
+        hit = pu[np.isin(pu, seen_pos[u])]
+        if hit.size:
+            fails.append("(2) seen items returned: " + _cert_where(u, hit, tg))
+
+    # ---- 4: the row's own order ----------------------------------------------------------------------------------------
+    vb = (val + np.float32(0.0)).view(np.uint32)
+    both = live[:, 1:] & live[:, :-1]
+    with np.errstate(invalid="ignore"):
+        desc = val[:, 1:] > val[:, :-1]
+    ties = (vb[:, 1:] == vb[:, :-1]) & (idx[:, 1:] <= idx[:, :-1])
+    unordered = ~(val[:, 1:] <= val[:, :-1])                                      # also catches NaN
+    for name, m in (("values ascend", both & (desc | unordered)), ("equal values, ids not ascending", both & ties)):
+        for u in np.nonzero(m.any(1))[0][:4]:
+            j = int(np.nonzero(m[u])[0][0])
+            fails.append(f"(4) {name}: user {u} at rank {j}/{j + 1}: ids {idx[u, j]}, {idx[u, j + 1]} "
+                         f"values {val[u, j]!r}, {val[u, j + 1]!r}")
+
+    # ---- 3, 5 and the boundary share: one sweep over the item chunks ------------------------------------------------------
+    q_sel = np.full((n_users, k), np.nan)
+    e_sel = np.full((n_users, k), np.nan)
+    full = (cnt == k) & (want == k)
+    last = np.where(full, val[np.arange(n_users), np.clip(cnt - 1, 0, k - 1)].astype(np.float64), np.inf)
+    left_n = np.zeros(n_users, np.int64)
+    left_worst = np.full(n_users, -np.inf)
+    left_c = np.zeros(n_users, np.int64)
+    top_q = np.full((n_users, 0), -np.inf)
+    top_e = np.zeros((n_users, 0))
+    uu = np.arange(n_users)[:, None]
+    for lo, hi, Q, A in ref.blocks():
+        m = is_cand & (pos >= lo) & (pos < hi)
+        ur, jr = np.nonzero(m)
+        q_sel[ur, jr] = Q[ur, pos[ur, jr] - lo]
+        e_sel[ur, jr] = A[ur, pos[ur, jr] - lo]
+        adm = np.ones(Q.shape, dtype=bool)
+        for u in range(n_users):
+            p = seen_pos[u]
+            adm[u, p[np.searchsorted(p, lo): np.searchsorted(p, hi)] - lo] = False
+        Qa = np.where(adm, Q, -np.inf)
+        # the k + 1 best admissible of the reference so far
+        w = min(k + 1, hi - lo)
+        part = np.argpartition(-Qa, w - 1, axis=1)[:, :w] if w < hi - lo else np.broadcast_to(np.arange(hi - lo), (n_users, hi - lo))
+        top_q = np.concatenate([top_q, Qa[uu, part]], 1)
+        top_e = np.concatenate([top_e, A[uu, part]], 1)
+        if top_q.shape[1] > k + 1:
+            o = np.argpartition(-top_q, k, axis=1)[:, :k + 1]
+            top_q, top_e = top_q[uu, o], top_e[uu, o]
+        # (5): admissible, not in the row, surely above the row's last value
+        Qa[ur, pos[ur, jr] - lo] = -np.inf
+        low = Qa - A
+        over = low > last[:, None]
+        n_over = over.sum(1)
+        left_n += n_over
+        for u in np.nonzero(n_over)[0]:
+            c = int(np.argmax(np.where(over[u], low[u], -np.inf)))
+            if low[u, c] - last[u] > left_worst[u]:
+                left_worst[u], left_c[u] = low[u, c] - last[u], lo + c
+    with np.errstate(invalid="ignore"):
+        err = np.abs(val.astype(np.float64) - q_sel)
+        ratio = np.where(is_cand, err / np.maximum(e_sel, 1e-300), 0.0)
+        ratio = np.where(is_cand & (err == 0), 0.0, ratio)
+        off3 = is_cand & ~(err <= e_sel)
+    if off3.any():
+        us = np.nonzero(off3.any(1))[0]
+        us = us[np.argsort(-np.nan_to_num(ratio[us], nan=np.inf).max(1))][:4]
+        fails.append(f"(3) values off by more than eps for {int(off3.any(1).sum())} users; worst: " + "; ".join(
+            _cert_where(u, pos[u][off3[u]], tg) + f" err/eps {np.nan_to_num(ratio[u], nan=np.inf).max():.3g}" for u in us))
+    if left_n.any():
+        us = np.nonzero(left_n)[0]
+        us = us[np.argsort(-left_worst[us])][:4]
+        fails.append(f"(5) better items left out for {int((left_n > 0).sum())} users; worst: " + "; ".join(
+            _cert_where(u, left_c[u], tg) + f" ({int(left_n[u])} items, Q64 - eps above the last value by "
+            f"{left_worst[u]:.3g})" for u in us))
+    share = 0.0
+    if top_q.shape[1] >= k + 1:
+        o = np.argsort(-top_q, axis=1, kind="stable")
+        tq, te = top_q[uu, o], top_e[uu, o]
+        with np.errstate(invalid="ignore"):
+            close = np.isfinite(tq[:, k]) & (tq[:, k - 1] - tq[:, k] < te[:, k - 1] + te[:, k])
+        share = float(close.mean())
+    out = {"ratio": float(np.nanmax(ratio, initial=0.0)), "share": share}
+    if fails:
+        raise AssertionError(f"top-{k} certificate (n_cand {n_cand}, tg {tg}, boundary share {share:.3f}): " + " | ".join(fails))
+    return out
