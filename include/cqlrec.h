@@ -405,6 +405,77 @@ int cqlrec_eval_topk(const int32_t* rec_idx, int64_t n_users, int32_t kmax, cons
                      void* ws, int64_t ws_bytes, double* per_user, double* sums, cqlrec_stream stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * f4, continued: the other metrics of replay/metrics, from any recommendation FRAME (a baseline, a loaded file,
+ * another model's output), not only from a block this library produced.  fp64 throughout; deterministic sums
+ * (per-block partials + one final pass); the only atomics are integer atomicMin / atomicAdd.
+ *
+ * cqlrec_recs_frame_to_block: the device columns (row, item_idx, relevance) of a frame -> rec_idx [n_users x kmax]
+ * (-1 padded) as get_top_k_recs followed by sorter do it (replay/metrics/base_metric.py:121-134, :22-51): per user
+ * order by relevance descending, keep the first kmax rows, drop later repeats of an item (dedup != 0), compact.
+ * Ties in relevance: item_idx ascending (the reference leaves them to Spark); -0.0 == +0.0.  NaN is the caller's to
+ * reject.  `row` is the row of the evaluated user set; a row outside 0..n_users-1 leaves (the right join of
+ * base_metric.py:135).  Optional outputs: rec_val (relevance), rec_pos (row_number BEFORE the repeats are dropped,
+ * 1-based: what coverage.py:90-103 ranks by), rec_w (`payload`, a per-row double, through the same permutation).
+ * n_rows == 0 is legal: every list is empty (payload may then be NULL beside a rec_w).
+ * --------------------------------------------------------------------------------------------------------- */
+int64_t cqlrec_recs_frame_to_block_ws_bytes(int64_t n_rows, int64_t n_users);
+int cqlrec_recs_frame_to_block(const int32_t* row, const int32_t* item_idx, const double* relevance,
+                               const double* payload, int64_t n_rows, int64_t n_users, int32_t kmax, int32_t dedup,
+                               void* ws, int64_t ws_bytes, int32_t* rec_idx, double* rec_val, int32_t* rec_pos,
+                               double* rec_w, cqlrec_stream stream);
+
+/* The left join of prev_policy_weights onto a frame's rows (replay/metrics/base_metric.py:535-542): `keys` ascending,
+ * (user_idx << 32 | item_idx), or item_idx alone when user_idx == NULL; out[i] = vals of the FIRST equal key, 0.0 for
+ * a miss (.na.fill(0.0)). */
+int cqlrec_recs_join_prev(const uint64_t* keys, const double* vals, int64_t n_keys, const int32_t* user_idx,
+                          const int32_t* item_idx, int64_t n_rows, double* out, cqlrec_stream stream);
+
+/* NCIS weights, in place, on a block that frame_to_block made with dedup == 0, rec_val = relevance and rec_w = the
+ * joined previous-policy relevance: the activation over each user's kept rows (_softmax_by_user: minus the user's
+ * minimum, base_metric.py:429-449; _sigmoid, :451-458), _weigh_and_clip (:460-488: prev == 0 -> threshold, else
+ * the ratio clipped to [1/threshold, threshold]), then sorter(extra_position=2) (:549-575): later repeats of an item
+ * leave with their weight.  On return rec_idx is de-duplicated and rec_w holds the weights. */
+#define CQLREC_NCIS_NONE 0
+#define CQLREC_NCIS_SIGMOID 1
+#define CQLREC_NCIS_SOFTMAX 2
+int cqlrec_recs_ncis_weights(int32_t* rec_idx, double* rec_val, double* rec_w, int64_t n_users, int32_t kmax,
+                             int32_t activation, double threshold, cqlrec_stream stream);
+
+/* Per-user metrics beside cqlrec_eval_topk's six, same indexing contract (rec_rows, CSR with ascending unique
+ * items, ks ascending within 1..kmax, n_ks <= 8).  Order: RocAuc (replay/metrics/rocauc.py:43-60, length =
+ * min(k, len(pred))), Unexpectedness (unexpectedness.py:40-46; base_idx [n_users x kb]: row u is user u's base list),
+ * Surprisal (surprisal.py:65-68; item_w [n_item_w] by item id, 1.0 beyond the table: :99-101), NCISPrecision
+ * (ncis_precision.py:24-30; rec_w beside rec_idx).  A metric whose input is NULL (gt_off / gt_items, base_idx,
+ * item_w, rec_w) comes out 0.  sums[CQLREC_EVAL_EXTRAS][n_ks]; per_user[n_users][CQLREC_EVAL_EXTRAS][n_ks] optional. */
+#define CQLREC_EVAL_EXTRAS 4
+int64_t cqlrec_eval_extras_ws_bytes(int64_t n_users, int32_t n_ks);
+int cqlrec_eval_extras(const int32_t* rec_idx, int64_t n_users, int32_t kmax, const int32_t* rec_rows,
+                       const int64_t* gt_off, const int32_t* gt_items, const int32_t* base_idx, int32_t kb,
+                       const double* item_w, int64_t n_item_w, const double* rec_w, const int32_t* ks /* [host] */,
+                       int32_t n_ks, void* ws, int64_t ws_bytes, double* per_user, double* sums, cqlrec_stream stream);
+
+/* Distinct users per item of a log (countDistinct: replay/metrics/surprisal.py:57-63, replay/distributions.py:74-78):
+ * the (user, item) pairs sorted as one 64-bit key, run heads counted.  cnt [n_items] by item id (ids >= n_items are
+ * not counted); *n_distinct_users (device) = distinct users of the log. */
+int64_t cqlrec_eval_item_user_counts_ws_bytes(int64_t n_rows);
+int cqlrec_eval_item_user_counts(const int32_t* item_idx, const int32_t* user_idx, int64_t n_rows, int64_t n_items,
+                                 void* ws, int64_t ws_bytes, int32_t* cnt, int64_t* n_distinct_users,
+                                 cqlrec_stream stream);
+/* w[i] = log2(n_users / cnt[i]) / log2(n_users) (surprisal.py:57-63), 1.0 where cnt[i] == 0; n_users > 1. */
+int cqlrec_eval_surprisal_weights(const int32_t* cnt, int64_t n_items, int64_t n_users, double* w, cqlrec_stream stream);
+
+/* Coverage (replay/metrics/coverage.py:90-112): best [n_items] = min rec_pos per item (integer atomicMin over a table
+ * set to INT_MAX), counts[q] (device int64) = items with best <= ks[q].  Items the log never saw count too (:84-88):
+ * n_items covers every id of rec_idx. */
+int cqlrec_eval_coverage(const int32_t* rec_idx, const int32_t* rec_pos, int64_t n_users, int32_t kmax, int64_t n_items,
+                         const int32_t* ks /* [host] */, int32_t n_ks, int32_t* best, int64_t* counts,
+                         cqlrec_stream stream);
+/* cnt[i] = cells of rec_idx that hold item i: rec_count of item_distribution (replay/distributions.py:80-86) when the
+ * block was cut at k with repeats dropped. */
+int cqlrec_eval_item_hist(const int32_t* rec_idx, int64_t n_users, int32_t kmax, int64_t n_items, int32_t* cnt,
+                          cqlrec_stream stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * Measurement hooks (bench.py): when enabled, every launcher brackets its kernel with a pair of HIP events on
  * the stream it launches on; cqlrec_prof_read synchronises those events and returns, per phase, the summed
  * kernel time in ms and the number of launches, then resets the pool.  Not capturable in a hipGraph; off by

@@ -26,6 +26,8 @@ SIM_DOT, SIM_COSINE, SIM_EUCLID = 0, 1, 2
 ITEM_KNN_MAX_K = 512
 QHEAD_LSE = 1
 QHEAD_ARGMAX = 2
+EVAL_EXTRAS = ("RocAuc", "Unexpectedness", "Surprisal", "NCISPrecision")
+NCIS_NONE, NCIS_SIGMOID, NCIS_SOFTMAX = 0, 1, 2
 
 vp, i32, i64, u64, f32, f64 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64, C.c_float, C.c_double
 
@@ -122,6 +124,18 @@ SIGNATURES = {
     "cqlrec_build_csr": (i32, [vp, vp, vp, vp, i64, i64, vp, i64, vp, vp, vp, vp]),
     "cqlrec_eval_topk_ws_bytes": (i64, [i64, i32]),
     "cqlrec_eval_topk": (i32, [vp, i64, i32, vp, vp, vp, C.POINTER(i32), i32, vp, i64, vp, vp, vp]),
+    "cqlrec_recs_frame_to_block_ws_bytes": (i64, [i64, i64]),
+    "cqlrec_recs_frame_to_block": (i32, [vp, vp, vp, vp, i64, i64, i32, i32, vp, i64, vp, vp, vp, vp, vp]),
+    "cqlrec_recs_join_prev": (i32, [vp, vp, i64, vp, vp, i64, vp, vp]),
+    "cqlrec_recs_ncis_weights": (i32, [vp, vp, vp, i64, i32, i32, f64, vp]),
+    "cqlrec_eval_extras_ws_bytes": (i64, [i64, i32]),
+    "cqlrec_eval_extras": (i32, [vp, i64, i32, vp, vp, vp, vp, i32, vp, i64, vp, C.POINTER(i32), i32, vp, i64, vp, vp,
+                                 vp]),
+    "cqlrec_eval_item_user_counts_ws_bytes": (i64, [i64]),
+    "cqlrec_eval_item_user_counts": (i32, [vp, vp, i64, i64, vp, i64, vp, vp, vp]),
+    "cqlrec_eval_surprisal_weights": (i32, [vp, i64, i64, vp, vp]),
+    "cqlrec_eval_coverage": (i32, [vp, vp, i64, i32, i64, C.POINTER(i32), i32, vp, vp, vp]),
+    "cqlrec_eval_item_hist": (i32, [vp, i64, i32, i64, vp, vp]),
     "cqlrec_prof_enable": (i32, [i32]),
     "cqlrec_prof_select": (i32, [C.c_uint32]),
     "cqlrec_debug_marks_enable": (i32, [i32]),

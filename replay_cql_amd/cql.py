@@ -302,13 +302,23 @@ class CQL(PandasRecommender):
         return pd.DataFrame({"user_idx": pu.cpu().numpy().astype(np.int32), "item_idx": pi.cpu().numpy().astype(np.int32),
                              "relevance": rel.cpu().numpy().astype(np.float64)})
 
-    def evaluate(self, log: pd.DataFrame, ground_truth: pd.DataFrame, ks=(10,), filter_seen_items: bool = True):
+    def evaluate(self, log: pd.DataFrame, ground_truth: pd.DataFrame, ks=(10,), filter_seen_items: bool = True,
+                 extra=()):
         """Quality of top-max(ks) recommendations for the users of `ground_truth`, computed on the GPU (f4): what
         optuna_objective.eval_quality (replay/optuna_objective.py:80-111) does with predict + a Spark metric, without
         the U x k block leaving the device.  Returns {metric: {k: value}} with the reference's metric definitions.
         `log` goes through the same cold filter as predict() (base_rec.py:560-603): a test-period log may hold users
-        and items the model never saw."""
+        and items the model never saw.
+        `extra`: any of "RocAuc", "Coverage", "Surprisal", added to the result under those names.  All three are taken
+        over the same users as the other metrics; Coverage counts against the items seen at fit (and is not a mean over
+        users), Surprisal weighs items by their users in `log` as passed."""
+        from . import metrics as M
         from .metrics import evaluate_topk
+        extra = tuple(extra)
+        unknown = [e for e in extra if e not in ("RocAuc", "Coverage", "Surprisal")]
+        if unknown:
+            raise ValueError(f"evaluate: unknown extra metrics {unknown}")
+        full_log = log
         core = self._require_fit()
         dev = core.device
         kmax = int(max(ks))
@@ -333,7 +343,26 @@ class CQL(PandasRecommender):
         rows_h = np.searchsorted(gt_users, gt["user_idx"].to_numpy().astype(np.int64))
         g_off, g_items, _ = D.build_csr_device(rows_h, gt["item_idx"].to_numpy(), None, None, len(gt_users), device=dev)
         g_items = torch.cat([g_items, torch.zeros(1, dtype=torch.int32, device=dev)])
-        return evaluate_topk(rec, g_off, g_items, ks)
+        out = evaluate_topk(rec, g_off, g_items, ks)
+        if not extra:
+            return out
+        ks_l = sorted(int(k) for k in ks)
+        n = len(gt_users)
+        if "RocAuc" in extra or "Surprisal" in extra:
+            w = None
+            if "Surprisal" in extra:
+                lg = M._columns(full_log, dev)                                       # pylint: disable=protected-access
+                w = M.surprisal_weights(lg["item_idx"], lg["user_idx"])
+            sums, _ = M.evaluate_extras(rec, ks_l, g_off, g_items, item_w=w)
+            for name in ("RocAuc", "Surprisal"):
+                if name in extra:
+                    out[name] = {k: float(sums[M.EXTRAS.index(name), i]) / n for i, k in enumerate(ks_l)}
+        if "Coverage" in extra:
+            pos = (torch.arange(1, kmax + 1, dtype=torch.int32, device=dev)[None, :]).expand(n, kmax).contiguous()
+            counts = M.coverage_counts(rec, pos, ks_l)
+            n_fit = int(np.unique(self.fit_items["item_idx"].to_numpy()).size)
+            out["Coverage"] = {k: c / n_fit for k, c in zip(ks_l, counts)}
+        return out
 
     # ------------------------------------------------------------------------------------------- item to item
     def _nearest_items_device(self, items, k: int, metric: Optional[str], candidates):
