@@ -333,7 +333,9 @@ int cqlrec_train_step_update_range(const cqlrec_train_ctx* ctx /* [host] */, uin
  * Same dataflow and results as fwd_bwd + update per step, software-pipelined across the two halves of the model:
  * Adam on E_in + encoder runs under the (MFMA-bound) item-side backward, the next step's sample / window gathers /
  * encoder start while the item-side Adam is still running, and only the Q-head kernels wait for it.  Everything is
- * joined on `stream` before the call returns.  loss_out: n_steps device floats (may be NULL). */
+ * joined on `stream` before the call returns.  loss_out: n_steps device floats (may be NULL).
+ * ctx->grads must be zero on entry and is zero again when a successful call has completed; during the call, and after
+ * a failed one, its content is unspecified (steps that have a successor do not re-zero it). */
 int cqlrec_train_steps(const cqlrec_train_ctx* ctx /* [host] */, uint64_t step0, int32_t n_steps, float* loss_out,
                        cqlrec_stream stream);
 

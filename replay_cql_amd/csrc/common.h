@@ -136,3 +136,12 @@ struct CqlAdamFix {
 int cql_adam_ema_fix(float* theta, float* grads, float* m, float* v, float* target, uint16_t* theta_b, uint16_t* target_b,
                      int64_t n, float step_size, float sqrt_bc2, float beta1, float beta2, float eps, float tau,
                      int32_t zero_grads, const CqlAdamFix* fix, hipStream_t stream);
+// Adam over a range of whole embedding rows of which only those marked in `row_map` (one byte per row, n_rows of them)
+// carry a gradient this step: the others are updated with g = 0 and their gradient elements are not read (misc.hip)
+int cql_adam_ema_rows(float* theta, float* grads, float* m, float* v, float* target, uint16_t* theta_b, uint16_t* target_b,
+                      int64_t n, float step_size, float sqrt_bc2, float beta1, float beta2, float eps, float tau,
+                      int32_t zero_grads, const uint8_t* row_map, int32_t d, int64_t n_rows, hipStream_t stream);
+// gbwd.hip: row_map[item] = 1 for every item that occurs in the sorted window pairs `ws` holds (after
+// cqlrec_gather_pool_bwd_prepare on the same stream), 0 for the others; row_map has n_items bytes
+int cql_gather_pool_bwd_mark_rows(const void* ws, int64_t n_states, int32_t L, int32_t d, int64_t n_items, uint8_t* row_map,
+                                  hipStream_t s);

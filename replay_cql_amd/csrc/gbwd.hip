@@ -258,6 +258,34 @@ extern "C" int cqlrec_gather_pool_bwd_prepare(const int64_t* offsets, const int3
   return CQLREC_OK;
 }
 
+// Which rows of g_E_in will phase 2 write?  One byte per item: cleared, then set from the sorted keys (every pair of a run
+// stores the same 1: plain byte stores, no atomics; sorted keys keep the stores of a wave on a few cache lines).  The
+// pipelined step driver hands the map to its state-side optimizer launch (misc.hip, adam_ema_rows_kernel).
+__global__ __launch_bounds__(256) void gbwd_mark_rows_kernel(const uint32_t* __restrict__ keys, int64_t n_pairs,
+                                                             uint32_t pad_key, uint8_t* __restrict__ row_map) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_pairs) return;
+  const uint32_t k = keys[i];
+  if (k < pad_key) row_map[k] = 1;
+}
+int cql_gather_pool_bwd_mark_rows(const void* ws, int64_t n_states, int32_t L, int32_t d, int64_t n_items, uint8_t* row_map,
+                                  hipStream_t s) {
+  CQL_REQUIRE(ws && row_map, "gather_pool_bwd_mark_rows: NULL pointer");
+  CQL_REQUIRE(n_items > 0 && n_items < (1ll << 31), "gather_pool_bwd_mark_rows: n_items=%lld", (long long)n_items);
+  if (hipMemsetAsync(row_map, 0, (size_t)n_items, s) != hipSuccess) {
+    cql_set_error("gather_pool_bwd_mark_rows: clearing the map failed");
+    return CQLREC_ERR_HIP;
+  }
+  if (n_states <= 0) return CQLREC_OK;
+  const GbWs w = gb_carve(const_cast<void*>(ws), n_states, L, d);
+  const int64_t n = n_states * L;
+  CqlProfScope prof(CQLREC_PH_GATHER_BWD, s);
+  hipLaunchKernelGGL(gbwd_mark_rows_kernel, dim3(cql_ceil_div(n, 256)), dim3(256), 0, s, w.keys_out, n, (uint32_t)n_items,
+                     row_map);
+  CQL_LAUNCH_CHECK("gather_pool_bwd_mark_rows");
+  return CQLREC_OK;
+}
+
 // phase 2: scale the gradient rows and sum the sorted runs into g_E_in (must be zero on entry)
 extern "C" int cqlrec_gather_pool_bwd_apply(const float* dh0, int64_t n_states, int32_t L, int32_t d, int64_t n_items,
                                             void* ws, int64_t ws_bytes, float* g_E_in, cqlrec_stream stream) {

@@ -735,7 +735,11 @@ extern "C" int cqlrec_td_loss(const float* q_a, const float* lse, const float* q
 }
 
 // =============================================================================================================
-// fused Adam + Polyak + bf16 shadows.  Pure HBM streaming: 20 B read + 24 B written per parameter.
+// fused Adam + Polyak + bf16 shadows.  Pure HBM streaming: 20 B read + 24 B written per parameter in the full form
+// (zero_grads = 1, every gradient element read).  Inside a cqlrec_train_steps call the steps that have a successor run
+// leaner (train.hip): the item-side range keeps its gradient (20 B + 20 B: the next long dE_out kernel overwrites every
+// row), the E_in range goes through adam_ema_rows_kernel (16 B + 20 B for a row the batch did not touch, + 4 B read
+// for a row it did).
 // Compiled with -ffp-contract=off so the expression order below is the normative one (oracle.adam_ema_step).
 // =============================================================================================================
 template <bool NT>
@@ -764,6 +768,62 @@ __global__ __launch_bounds__(256) void adam_ema_kernel(float4* __restrict__ thet
     target_b[i] = make_uint2(pack_bf16x2(tt[0], tt[1]), pack_bf16x2(tt[2], tt[3]));
     if (zero_grads) st4<NT>(grads + i, 0.f, 0.f, 0.f, 0.f);
   }
+}
+
+// The E_in range of the pipelined single-rank driver: `row_map[r] != 0` says that the window-gather backward of THIS step
+// wrote gradient row r (gbwd.hip, cql_gather_pool_bwd_mark_rows).  Any other row contributes g = +0.0f -- what the full
+// form loads from a zeroed buffer -- without being read, so what an earlier step left in it is dead data.  The range starts
+// at a row boundary; rows >= n_rows (the pad row, alignment padding) are never written by anyone.  zero_grads = 1 (the
+// last step of a call) zeroes every element, stale rows included.
+template <bool NT>
+__global__ __launch_bounds__(256) void adam_ema_rows_kernel(float4* __restrict__ theta, float4* __restrict__ grads,
+                                                            float4* __restrict__ m, float4* __restrict__ v,
+                                                            float4* __restrict__ target, uint2* __restrict__ theta_b,
+                                                            uint2* __restrict__ target_b, int64_t n4, float step_size,
+                                                            float sqrt_bc2, float beta1, float beta2, float eps, float tau,
+                                                            int zero_grads, const uint8_t* __restrict__ row_map, int ld4row,
+                                                            int64_t n_rows) {
+  const float omb1 = 1.0f - beta1, omb2 = 1.0f - beta2, omt = 1.0f - tau;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t row = i >> ld4row;
+    const bool live = row < n_rows && row_map[row] != 0;
+    float4 p4 = ld4<NT>(theta + i), m4 = ld4<NT>(m + i), v4 = ld4<NT>(v + i), t4 = ld4<NT>(target + i);
+    float4 g4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (live) g4 = ld4<NT>(grads + i);
+    const float g[4] = {g4.x, g4.y, g4.z, g4.w};
+    float p[4] = {p4.x, p4.y, p4.z, p4.w}, mm[4] = {m4.x, m4.y, m4.z, m4.w}, vv[4] = {v4.x, v4.y, v4.z, v4.w},
+          tt[4] = {t4.x, t4.y, t4.z, t4.w};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      adam_ema_elem(g[k], p[k], mm[k], vv[k], tt[k], step_size, sqrt_bc2, beta1, beta2, eps, tau, omb1, omb2, omt);
+    }
+    st4<NT>(theta + i, p[0], p[1], p[2], p[3]);
+    st4<NT>(m + i, mm[0], mm[1], mm[2], mm[3]);
+    st4<NT>(v + i, vv[0], vv[1], vv[2], vv[3]);
+    st4<NT>(target + i, tt[0], tt[1], tt[2], tt[3]);
+    theta_b[i] = make_uint2(pack_bf16x2(p[0], p[1]), pack_bf16x2(p[2], p[3]));
+    target_b[i] = make_uint2(pack_bf16x2(tt[0], tt[1]), pack_bf16x2(tt[2], tt[3]));
+    if (zero_grads) st4<NT>(grads + i, 0.f, 0.f, 0.f, 0.f);
+  }
+}
+
+int cql_adam_ema_rows(float* theta, float* grads, float* m, float* v, float* target, uint16_t* theta_b, uint16_t* target_b,
+                      int64_t n, float step_size, float sqrt_bc2, float beta1, float beta2, float eps, float tau,
+                      int32_t zero_grads, const uint8_t* row_map, int32_t d, int64_t n_rows, hipStream_t stream) {
+  CQL_REQUIRE(theta && grads && m && v && target && theta_b && target_b && row_map, "adam_ema_rows: NULL pointer");
+  CQL_REQUIRE(n > 0 && n % 4 == 0, "adam_ema_rows: n=%lld must be a positive multiple of 4", (long long)n);
+  CQL_REQUIRE(d == 64 || d == 128 || d == 256, "adam_ema_rows: d=%d unsupported", d);
+  CQL_REQUIRE(n_rows >= 0 && n_rows * d <= n, "adam_ema_rows: %lld rows of %d do not fit n=%lld", (long long)n_rows, d,
+              (long long)n);
+  const int64_t n4 = n / 4;
+  int blocks = (int)((n4 + 255) / 256);
+  if (blocks > 8192) blocks = 8192;
+  CqlProfScope prof(CQLREC_PH_ADAM, stream);
+  hipLaunchKernelGGL(adam_ema_rows_kernel<true>, dim3(blocks), dim3(256), 0, stream, (float4*)theta, (float4*)grads,
+                     (float4*)m, (float4*)v, (float4*)target, (uint2*)theta_b, (uint2*)target_b, n4, step_size, sqrt_bc2,
+                     beta1, beta2, eps, tau, zero_grads, row_map, __builtin_ctz((unsigned)d) - 2, n_rows);
+  CQL_LAUNCH_CHECK("adam_ema (row map)");
+  return CQLREC_OK;
 }
 
 // what qde_fixup_kernel would have added to the four gradient elements 4 i4 .. 4 i4 + 3 (relative to the start of the

@@ -54,6 +54,7 @@ struct StepWs {
   float *h0_s, *dH, *dh0;
   uint16_t *h0b, *zb, *hb, *h0b_t, *zb_t, *hb_t;
   void *ws_q, *ws_q2, *ws_qb, *ws_qb2, *ws_enc, *ws_gb, *ws_oh;
+  uint8_t* row_map;      // [n_items] which rows of g_E_in this step's window-gather backward writes (cqlrec_train_steps)
   int64_t ws_q_bytes, ws_qb_bytes, ws_qf_bytes, ws_enc_bytes, ws_gb_bytes, ws_oh_bytes;
   int64_t total;
 };
@@ -115,6 +116,9 @@ StepWs carve_step(void* ws, int32_t B, int64_t N, int32_t d, int32_t L, uint64_t
   void* oh0 = c.take<char>(w.ws_oh_bytes);   // sorted (action, transition) pairs of the one-hot scatter, by parity too
   void* oh1 = c.take<char>(w.ws_oh_bytes);
   w.ws_oh = (step & 1) ? oh1 : oh0;
+  uint8_t* rm0 = c.take<uint8_t>(N);         // by parity like the pairs it is built from: the map of step t+1 is made
+  uint8_t* rm1 = c.take<uint8_t>(N);         // while the optimizer of step t has not read its own yet
+  w.row_map = (step & 1) ? rm1 : rm0;
   w.total = c.off;
   return w;
 }
@@ -382,6 +386,7 @@ int sample_ahead(const cqlrec_train_ctx* c, uint64_t step, cqlrec_stream stream,
   CQL_HIP_TRY(hipEventRecord(sampled_ev, (hipStream_t)stream), "train_steps");
   CQL_TRY(cqlrec_gather_pool_bwd_prepare(c->offsets, c->items, w.users, w.tpos, 0, c->batch, c->window, L.d, L.n_items,
                                          w.ws_gb, w.ws_gb_bytes, stream));
+  CQL_TRY(cql_gather_pool_bwd_mark_rows(w.ws_gb, c->batch, c->window, L.d, L.n_items, w.row_map, (hipStream_t)stream));
   return cql_onehot_prepare(w.act, c->batch, L.n_items, L.d, w.ws_oh, w.ws_oh_bytes, (hipStream_t)stream);
 }
 
@@ -395,9 +400,10 @@ int loss_sum_impl(const cqlrec_train_ctx* c, uint64_t step, float* loss_out, hip
   return cql_td_loss_sum(w.term, c->batch, inv_batch, loss_out ? loss_out : w.loss, on);
 }
 // loss_sum_deferred != NULL: the loss terms are left for the caller's loss_sum_impl (on a stream that has slack)
+// want_row_map: the side-stream sort of a step that was not sampled ahead also fills the step's row map (sample_ahead does)
 int forward_impl(const cqlrec_train_ctx* c, uint64_t step, float* loss_out, cqlrec_stream stream, hipEvent_t eout_ready,
                  hipEvent_t presampled = nullptr, hipStream_t early_items = nullptr, CqlAdamFix* early_fix = nullptr,
-                 bool* loss_sum_deferred = nullptr) {
+                 bool* loss_sum_deferred = nullptr, bool want_row_map = false) {
   const cqlrec_layout& L = c->layout;
   const int32_t B = c->batch, d = L.d, W = c->window;
   const int64_t N = L.n_items;
@@ -421,6 +427,7 @@ int forward_impl(const cqlrec_train_ctx* c, uint64_t step, float* loss_out, cqlr
   } else if (ss.ok) {
     CQL_TRY(cqlrec_gather_pool_bwd_prepare(c->offsets, c->items, w.users, w.tpos, 0, B, W, d, N, w.ws_gb, w.ws_gb_bytes,
                                            (cqlrec_stream)ss.s));
+    if (want_row_map) CQL_TRY(cql_gather_pool_bwd_mark_rows(w.ws_gb, B, W, d, N, w.row_map, ss.s));
     CQL_TRY(cql_onehot_prepare(w.act, B, N, d, w.ws_oh, w.ws_oh_bytes, ss.s));
     CQL_HIP_TRY(hipEventRecord(ss.sorted[step & 1], ss.s), "train_step_forward");
   } else {
@@ -636,8 +643,18 @@ extern "C" int cqlrec_train_step_fwd_bwd(const cqlrec_train_ctx* c, uint64_t ste
 //     it runs under the MFMA-bound item-side kernel -- then ALREADY the prologue of step t+1 (sample, window gathers,
 //     encoder: they read only E_in / W), which waits for the item-side Adam only in front of its Q-head kernels.
 // Same dataflow as fwd_bwd + update per step; joined before returning.  world must be 1 (no all-reduce in here).
+//
+// Steps that have a successor in the same call leave the gradient buffer as it is instead of zeroing it ("lean"):
+//   * [off_E_out, off_W1): the next writer is the long item-side kernel of step t+1, which stores every row of g_E_out and
+//     every element of g_b_out (qde_kernel, qde2_kernel, qde3_kernel: store_piece of the piece holding stage 0, plain
+//     stores with accumulate = 0, in either placement of that kernel); the one-hot part and the cut pieces go on top.
+//   * E_in: the window-gather backward writes only the rows of the batch, so the step's row map (built with the sorted
+//     pairs, by parity) tells the optimizer which rows to read; the others take g = 0 unread and whatever an earlier step
+//     left in them is dead.
+// The last step of a call runs the zeroing forms (E_in still through its map, so that stale rows count as zero and are
+// cleared), which leaves ctx->grads all zeros as the phase entry points expect.  A single-step call runs the full forms only.
 int update_range_impl(const cqlrec_train_ctx* c, uint64_t step, int64_t lo, int64_t hi, cqlrec_stream stream,
-                      const CqlAdamFix* fix);
+                      const CqlAdamFix* fix, int zero_grads = 1, const uint8_t* row_map = nullptr);
 extern "C" int cqlrec_train_steps(const cqlrec_train_ctx* c, uint64_t step0, int32_t n_steps, float* loss_out,
                                   cqlrec_stream stream) {
   CQL_TRY(check_ctx(c));
@@ -648,8 +665,11 @@ extern "C" int cqlrec_train_steps(const cqlrec_train_ctx* c, uint64_t step0, int
   hipEvent_t pending = nullptr;   // item-side Adam of the previous step
   hipEvent_t sampled = nullptr;   // transitions + sorted pairs of this step, prepared during the previous backward
   need_side_streams(side_stream(), true);
+  const bool use_map = n_steps > 1 && L.off_E_in == 0;
+  bool grads_dirty = false;       // a lean step has run: the gradient buffer holds dead data until the last step clears it
   for (int32_t i = 0; i < n_steps; ++i) {
     const uint64_t step = step0 + (uint64_t)i;
+    const bool lean = use_map && i + 1 < n_steps;
     // CQL_EARLY_DE=0: the long item-side kernel behind the loss (A/B knob); default: behind the fused forward
     static const int early_de = !(getenv("CQL_EARLY_DE") && getenv("CQL_EARLY_DE")[0] == '0');
     SideStream& ss0 = side_stream();
@@ -659,7 +679,7 @@ extern "C" int cqlrec_train_steps(const cqlrec_train_ctx* c, uint64_t step0, int
     bool sum_deferred = false;
     const bool can_defer = ss0.ok && ss0.s3 && i + 1 < n_steps;
     CQL_TRY(forward_impl(c, step, loss_out ? loss_out + i : nullptr, stream, pending, sampled, early ? ss0.s : nullptr, &fix,
-                         can_defer ? &sum_deferred : nullptr));
+                         can_defer ? &sum_deferred : nullptr, use_map));
     pending = sampled = nullptr;
     if (g_marks_on && n_steps >= 4) {   // marks: backward of step n/2, forward of step n/2 + 1
       if (i == n_steps / 2) g_mark_phase = 1;
@@ -693,18 +713,26 @@ extern "C" int cqlrec_train_steps(const cqlrec_train_ctx* c, uint64_t step0, int
       CQL_TRY(backward_chain_impl(c, step, stream));                       // encoder, window gather
       if (g_mark_phase == 1) mark(MK_CHAIN, s);
       CQL_TRY(cqlrec_train_step_update_range(c, step, L.off_W1, L.total, stream));
-      CQL_TRY(cqlrec_train_step_update_range(c, step, 0, L.off_E_out, stream));
+      if (use_map) {
+        const StepWs w = carve_step(c->ws, c->batch, L.n_items, L.d, c->window, step);
+        CQL_TRY(update_range_impl(c, step, 0, L.off_E_out, stream, nullptr, lean ? 0 : 1, w.row_map));
+      } else {
+        CQL_TRY(cqlrec_train_step_update_range(c, step, 0, L.off_E_out, stream));
+      }
       if (g_mark_phase == 1) mark(MK_ADAM_IN, s);
       // The two Adam launches are HBM-bound and run side by side: serialising them, state side first so that the next
       // prologue runs under the item-side Adam, was measured no faster (0.802 vs 0.796 ms per step at cfg3).
       CQL_HIP_TRY(hipStreamWaitEvent(ss.s, ss.dh, 0), "train_steps");     // dh_finish reads the E_out shadow
       fix.rows_off = 0;
       fix.cs_off = L.off_b_out - L.off_E_out;
-      CQL_TRY(update_range_impl(c, step, L.off_E_out, L.off_W1, (cqlrec_stream)ss.s, &fix));
+      CQL_TRY(update_range_impl(c, step, L.off_E_out, L.off_W1, (cqlrec_stream)ss.s, &fix, lean ? 0 : 1));
+      grads_dirty = lean;
       CQL_HIP_TRY(hipEventRecord(ss.eout, ss.s), "train_steps");
       if (g_mark_phase == 1) { mark(MK_ADAM_OUT, ss.s); g_mark_phase = 2; }
       pending = ss.eout;
     } else {
+      // (the serial form needs a zeroed gradient buffer; the side streams do not go away in the middle of a call)
+      CQL_REQUIRE(!grads_dirty, "train_steps: lost the side streams in the middle of a call");
       if (sum_deferred) CQL_TRY(loss_sum_impl(c, step, loss_out ? loss_out + i : nullptr, s));
       CQL_TRY(backward_rest_impl(c, step, stream));
       CQL_TRY(backward_items_impl(c, step, stream));
@@ -723,7 +751,7 @@ extern "C" int cqlrec_train_step_update_range(const cqlrec_train_ctx* c, uint64_
 }
 
 int update_range_impl(const cqlrec_train_ctx* c, uint64_t step, int64_t lo, int64_t hi, cqlrec_stream stream,
-                      const CqlAdamFix* fix) {
+                      const CqlAdamFix* fix, int zero_grads, const uint8_t* row_map) {
   CQL_TRY(check_ctx(c));
   CQL_REQUIRE(lo >= 0 && hi <= c->layout.total && lo < hi && lo % 4 == 0 && hi % 4 == 0,
               "train_step_update_range: bad range [%lld, %lld)", (long long)lo, (long long)hi);
@@ -732,9 +760,15 @@ int update_range_impl(const cqlrec_train_ctx* c, uint64_t step, int64_t lo, int6
   const double bc2 = 1.0 - pow((double)c->beta2, t);
   const float step_size = (float)((double)c->lr / bc1);
   const float sqrt_bc2 = (float)sqrt(bc2);
+  if (row_map) {      // rows of E_in: the range starts at row 0 of the table
+    CQL_REQUIRE(lo == c->layout.off_E_in && !fix, "train_step_update_range: the row map belongs to the E_in range");
+    return cql_adam_ema_rows(c->theta + lo, c->grads + lo, c->adam_m + lo, c->adam_v + lo, c->target + lo, c->theta_b + lo,
+                             c->target_b + lo, hi - lo, step_size, sqrt_bc2, (float)c->beta1, (float)c->beta2, (float)c->eps,
+                             (float)c->tau, zero_grads, row_map, c->layout.d, c->layout.n_items, (hipStream_t)stream);
+  }
   return cql_adam_ema_fix(c->theta + lo, c->grads + lo, c->adam_m + lo, c->adam_v + lo, c->target + lo, c->theta_b + lo,
                           c->target_b + lo, hi - lo, step_size, sqrt_bc2, (float)c->beta1, (float)c->beta2, (float)c->eps,
-                          (float)c->tau, 1, fix, (hipStream_t)stream);
+                          (float)c->tau, zero_grads, fix, (hipStream_t)stream);
 }
 
 extern "C" int cqlrec_train_step_update(const cqlrec_train_ctx* c, uint64_t step, cqlrec_stream stream) {
