@@ -68,13 +68,16 @@ def build_torch_ops(verbose: bool = True) -> Path:
     return TORCH_LIB
 
 
-def build(force: bool = False, verbose: bool = True) -> Path:
-    if not force and not _stale():
+def build(force: bool = False, verbose: bool = True, variant: str | None = None, defines: tuple = ()) -> Path:
+    """`variant` NAME with extra -D... flags builds libcqlrec_NAME.so beside the library (A/B-ing kernel parameters; load
+    it with CQLREC_LIB): same sources and per-file flags, objects of its own, no torch shim."""
+    if variant is None and not force and not _stale():
         return LIB
     hipcc = _hipcc()
-    objdir = PKG / "build"
-    objdir.mkdir(exist_ok=True)
-    common = [hipcc, f"--offload-arch={ARCH}", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]
+    objdir = PKG / "build" / (f"var_{variant}" if variant else "")
+    objdir.mkdir(parents=True, exist_ok=True)
+    lib = PKG / f"libcqlrec_{variant}.so" if variant else LIB
+    common = [hipcc, f"--offload-arch={ARCH}", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function", *defines]
 
     def compile_one(src: str) -> Path:
         obj = objdir / (src + ".o")
@@ -86,12 +89,13 @@ def build(force: bool = False, verbose: bool = True) -> Path:
 
     with ThreadPoolExecutor(max_workers=4) as ex:
         objs = list(ex.map(compile_one, SOURCES))
-    cmd = [hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", str(LIB)] + [str(o) for o in objs]
+    cmd = [hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", str(lib)] + [str(o) for o in objs]
     if verbose:
         print(" ".join(cmd), file=sys.stderr)
     subprocess.run(cmd, check=True)
-    build_torch_ops(verbose)
-    return LIB
+    if variant is None:
+        build_torch_ops(verbose)
+    return lib
 
 
 def build_asan(verbose: bool = False) -> Path:
@@ -144,5 +148,8 @@ def build_asan(verbose: bool = False) -> Path:
 if __name__ == "__main__":
     if "--asan" in sys.argv:
         print(build_asan(verbose=True))
+    elif "--variant" in sys.argv:      # --variant NAME -DX=1 ...
+        i = sys.argv.index("--variant")
+        print(build(verbose=False, variant=sys.argv[i + 1], defines=tuple(x for x in sys.argv[i + 2:] if x.startswith("-D"))))
     else:
         print(build(force="--force" in sys.argv))

@@ -16,7 +16,7 @@
 // stages it issues lie past the slice; the buffer descriptor bounds them and nobody uses them).
 #include <stdlib.h>
 #include <type_traits>
-#include "qhead_de_common.h"
+#include "qhead_fwd_common.h"
 
 struct QArgmax2Args {
   const uint16_t* H_b;      // [n_states x D] owner rows
@@ -40,62 +40,26 @@ template <int D>
 __global__ __launch_bounds__(256, 1) void qargmax2_kernel(QArgmax2Args a) {
   using C = DeCfg<D, 4>;
   constexpr int KS = C::KS, TILES = C::TILES;
-  constexpr bool PAR_ALT = ((4 / C::PPG) & 1) != 0;          // d = 256: the row group's parity alternates with the piece
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];   // the ONLY LDS object of this kernel
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int r = lane & 31, h = lane >> 5;
-  const int split = blockIdx.x % a.nsplit;
-  const int64_t rblk = blockIdx.x / a.nsplit;
-  const int64_t s_begin = (int64_t)split * a.split_rows;
-  const int64_t s_end = (s_begin + a.split_rows < a.n_items) ? (s_begin + a.split_rows) : a.n_items;
-  const int nst = (s_end > s_begin) ? (int)((s_end - s_begin + C::TI - 1) / C::TI) : 0;
+  const QSlice sl = slice_preamble<C::TI>(a.nsplit, a.split_rows, a.n_items);
+  const int nst = sl.nst;
   if (nst <= 0) return;
-  const uint32_t gst0 = (uint32_t)(s_begin / C::TI);
 
-  // ---- staging (see qde_kernel) -------------------------------------------------------------------------------------------
-  __amdgpu_buffer_rsrc_t rs_e = __builtin_amdgcn_make_buffer_rsrc((void*)a.E_b, 0, (int)(a.n_items * C::ROWB), 0x00020000);
-  __amdgpu_buffer_rsrc_t rs_b = __builtin_amdgcn_make_buffer_rsrc((void*)a.bias, 0, (int)(a.n_items * 4), 0x00020000);
-  uint32_t voff[2];
-  {
-    const int sub = lane >> 5, r7 = (lane >> 2) & 7, slot = lane & 3;
-    const int rg0 = wave / C::PPG, hc = wave % C::PPG;
-#pragma unroll
-    for (int par = 0; par < 2; ++par) {
-      const int rg1 = (PAR_ALT ? (rg0 + par) : rg0) & 1;
-      const int q2 = (r7 >> 2) | (rg1 << 1);
-      voff[par] = (uint32_t)((rg0 * 8 + r7) * C::ROWB + (8 * hc + 4 * sub + (slot ^ q2)) * 16);
-    }
-  }
-  const uint32_t voff_strip = (uint32_t)lane * 4;
-  const uint32_t smem_base = lds_addr_of(smem);
-  auto issue_piece = [&](int stage, int buf, int i) __attribute__((always_inline)) {
-    const uint32_t bufp = __builtin_amdgcn_readfirstlane(smem_base + buf * C::BUF_BYTES);
-    const uint32_t gs = gst0 + (uint32_t)stage;
-    bdma16(voff[PAR_ALT ? (i & 1) : 0], rs_e, gs * C::STAGE_BYTES + C::PSTEP * i, bufp + (4 * i + wave) * 1024);
-  };
-  auto issue_strip = [&](int stage, int buf) __attribute__((always_inline)) {
-    const uint32_t bufp = __builtin_amdgcn_readfirstlane(smem_base + buf * C::BUF_BYTES);
-    const uint32_t gs = gst0 + (uint32_t)stage;
-    if (wave == (stage & 3)) bdma4(voff_strip, rs_b, gs * (C::TI * 4), bufp + C::STAGE_BYTES);
-  };
+  // ---- staging --------------------------------------------------------------------------------------------------------------
+  const ImgStager<C> stg(lane, wave, lds_addr_of(smem), sl.gst0, make_rsrc(a.E_b, a.n_items * C::ROWB), make_rsrc(a.bias, a.n_items * 4));
   // items past the end of the catalogue (last stage of the last slice): bias -inf, so that they never are a maximum
   auto patch_strip = [&](int stage, int buf) __attribute__((always_inline)) {
-    const int64_t valid = a.n_items - (int64_t)(gst0 + (uint32_t)stage) * C::TI;
-    if (valid < C::TI) {
-      if (wave == 0 && lane < C::TI && lane >= valid)
-        *(__attribute__((address_space(3))) float*)((lds_u8*)smem + buf * C::BUF_BYTES + C::STAGE_BYTES + lane * 4) = NEG_INF_F;
-      __builtin_amdgcn_s_waitcnt(0xC07F);
-      __builtin_amdgcn_s_barrier();
-    }
+    img_patch_strip<C>((lds_u8*)smem, buf, a.n_items - (int64_t)(sl.gst0 + (uint32_t)stage) * C::TI, lane, wave);
   };
 
   // ---- read geometry ------------------------------------------------------------------------------------------------------
   const lds_u8* lbase = (const lds_u8*)smem;
-  const int oa0 = C::RG_BYTES * (r >> 3) + 64 * (r & 7) + 16 * ((0 + h) ^ ((r >> 2) & 3));
-  const int oa1 = C::RG_BYTES * (r >> 3) + 64 * (r & 7) + 16 * ((2 + h) ^ ((r >> 2) & 3));
-  const int os = C::STAGE_BYTES + 16 * h;
+  const ImgRead o = img_read_offsets<C>(lane);
+  const int oa0 = o.oa0, oa1 = o.oa1, os = o.os;
   const lds_u8 *pA0, *pA1, *pS;        // current stage's buffer
   const lds_u8 *nA0, *nA1, *nS;        // next stage's buffer
   auto set_ptrs = [&](int bc, int bn) __attribute__((always_inline)) {
@@ -106,15 +70,8 @@ __global__ __launch_bounds__(256, 1) void qargmax2_kernel(QArgmax2Args a) {
   // ---- owner state ------------------------------------------------------------------------------------------------------
   bf16x8 rf[2][KS];
 #pragma unroll
-  for (int g = 0; g < 2; ++g) {
-    int64_t row = rblk * 256 + wave * 64 + g * 32 + r;
-    if (row >= a.n_states) row = a.n_states - 1;
-#pragma unroll
-    for (int s = 0; s < KS; ++s) rf[g][s] = *reinterpret_cast<const bf16x8*>(a.H_b + row * D + 16 * s + 8 * h);
-  }
-  __builtin_amdgcn_s_waitcnt(0x0F70);       // (see qde2_kernel::load_owner)
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  for (int g = 0; g < 2; ++g) load_owner_frags<D>(a.H_b, sl.rblk * 256 + wave * 64 + g * 32 + r, a.n_states, h, rf[g]);
+  owner_fence();
   float best[2] = {NEG_INF_F, NEG_INF_F};
   int btile[2] = {0x7FFFFFFF, 0x7FFFFFFF};
 
@@ -185,8 +142,8 @@ __global__ __launch_bounds__(256, 1) void qargmax2_kernel(QArgmax2Args a) {
       AM2_FENCE();
       epi(s, acc1, 1, row0_prev);
       AM2_FENCE();
-      if (END && s >= 1 && s <= C::LPS) issue_piece(issued, cur_buf, s - 1);      // refill, one piece per gap
-      if (END && s == C::LPS + 1) issue_strip(issued, cur_buf);
+      if (END && s >= 1 && s <= C::LPS) stg.piece(issued, cur_buf, s - 1);      // refill, one piece per gap
+      if (END && s == C::LPS + 1) stg.strip(issued, cur_buf);
       AM2_FENCE();
       next_read(IT, P_, s);
       AM2_FENCE();
@@ -205,9 +162,7 @@ __global__ __launch_bounds__(256, 1) void qargmax2_kernel(QArgmax2Args a) {
 
   // ---- prologue: two stages in flight; rows and bias of the first tile in registers ------------------------------------------
   for (int s0 = 0; s0 < 2; ++s0) {
-#pragma unroll
-    for (int i = 0; i < C::LPS; ++i) issue_piece(s0, s0, i);
-    issue_strip(s0, s0);
+    stg.all(s0, s0);
     ++issued;
   }
   de_wait_vmcnt<0>();
@@ -222,11 +177,11 @@ __global__ __launch_bounds__(256, 1) void qargmax2_kernel(QArgmax2Args a) {
 
   using I0 = std::integral_constant<int, 0>;
   using I1 = std::integral_constant<int, 1>;
-  int row_prev = (int)s_begin;
+  int row_prev = (int)sl.s_begin;
   if constexpr (TILES == 2) {
     for (st = 0; st < nst; ++st) {
       set_ptrs(cur_buf, cur_buf ^ 1);
-      const int row0 = (int)s_begin + st * C::TI;
+      const int row0 = (int)sl.s_begin + st * C::TI;
       tile(I0{}, I0{}, row0, row_prev);
       tile(I1{}, I1{}, row0 + 32, row0);
       row_prev = row0 + 32;
@@ -235,13 +190,13 @@ __global__ __launch_bounds__(256, 1) void qargmax2_kernel(QArgmax2Args a) {
   } else {          // one tile per stage: the register-set parity alternates with the stage -- two stages per trip
     for (st = 0; st < nst; ++st) {
       set_ptrs(cur_buf, cur_buf ^ 1);
-      const int row0 = (int)s_begin + st * C::TI;
+      const int row0 = (int)sl.s_begin + st * C::TI;
       tile(I0{}, I0{}, row0, row_prev);
       row_prev = row0;
       cur_buf ^= 1;
       if (++st >= nst) break;
       set_ptrs(cur_buf, cur_buf ^ 1);
-      const int row1 = (int)s_begin + st * C::TI;
+      const int row1 = (int)sl.s_begin + st * C::TI;
       tile(I0{}, I1{}, row1, row_prev);
       row_prev = row1;
       cur_buf ^= 1;
@@ -255,12 +210,12 @@ __global__ __launch_bounds__(256, 1) void qargmax2_kernel(QArgmax2Args a) {
   // ---- partials: the two lanes of a state hold different rows of every tile -------------------------------------------------
 #pragma unroll
   for (int g = 0; g < 2; ++g) {
-    const int64_t row = rblk * 256 + wave * 64 + g * 32 + r;
+    const int64_t row = sl.rblk * 256 + wave * 64 + g * 32 + r;
     const float v2 = __shfl_xor(best[g], 32);
     const int i2 = __shfl_xor(btile[g], 32);
     const bool take2 = (v2 > best[g]) || (v2 == best[g] && i2 < btile[g]);
     if (row < a.n_states && h == 0) {
-      const int64_t pidx = (int64_t)split * a.n_states + row;
+      const int64_t pidx = (int64_t)sl.split * a.n_states + row;
       a.part_v[pidx] = take2 ? v2 : best[g];
       a.part_i[pidx] = take2 ? i2 : btile[g];
     }

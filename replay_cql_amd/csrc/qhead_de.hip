@@ -24,7 +24,7 @@
 // piece), so a group that is not cut gives bit-identical rows to the generic kernel.
 #include <stdlib.h>
 
-#include "qhead_de_common.h"
+#include "qhead_image.h"
 
 template <int D, int NBUF, int WAVES>
 __global__ __launch_bounds__(64 * WAVES, (D == 256 ? 1 : 2)) void qde_kernel(QDeArgs a) {
@@ -50,8 +50,9 @@ __global__ __launch_bounds__(64 * WAVES, (D == 256 ? 1 : 2)) void qde_kernel(QDe
   int t_dma = t;                         // stage of the next DMA to issue
 
   // ---- staging geometry (per-lane constants) -------------------------------------------------------------------
-  __amdgpu_buffer_rsrc_t rs_h = __builtin_amdgcn_make_buffer_rsrc((void*)a.H_b, 0, (int)(a.n_states * C::ROWB), 0x00020000);
-  __amdgpu_buffer_rsrc_t rs_s = __builtin_amdgcn_make_buffer_rsrc((void*)a.nlse2, 0, (int)(a.n_states * 4), 0x00020000);
+  __amdgpu_buffer_rsrc_t rs_h = make_rsrc(a.H_b, a.n_states * C::ROWB);
+  __amdgpu_buffer_rsrc_t rs_s = make_rsrc(a.nlse2, a.n_states * 4);
+  // (img_stage_voff of qhead_image.h, kept in place: through the shared function hipcc orders this kernel's loop differently)
   // piece pc = 4 i + wave of a stage: 8-row group rg = pc / PPG, chunk octet hc = pc % PPG; lane l fills image bytes
   // [16 l, 16 l + 16) of the piece: subtile l >> 5, row (l >> 2) & 7, slot l & 3 = (chunk & 3) ^ ((row >> 2) & 3)
   uint32_t voff[2];

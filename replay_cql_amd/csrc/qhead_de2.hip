@@ -22,7 +22,7 @@
 // Work decomposition, LDS image, staging and the deterministic two-piece sum of cut groups: as qde_kernel (qhead_de.hip).
 #include <stdlib.h>
 #include <type_traits>
-#include "qhead_de_common.h"
+#include "qhead_image.h"
 
 #define QDE2_ITEMS 256      // items per group: 4 waves x 2 x 32
 #ifndef QDE2_NBUF
@@ -61,46 +61,22 @@ __global__ __launch_bounds__(256, 1) void qde2_kernel(QDeArgs a) {
   int t_seg = t;
   int t_dma = t;
 
-  // ---- staging (see qde_kernel) ----------------------------------------------------------------------------------
-  __amdgpu_buffer_rsrc_t rs_h = __builtin_amdgcn_make_buffer_rsrc((void*)a.H_b, 0, (int)(a.n_states * C::ROWB), 0x00020000);
-  __amdgpu_buffer_rsrc_t rs_s = __builtin_amdgcn_make_buffer_rsrc((void*)a.nlse2, 0, (int)(a.n_states * 4), 0x00020000);
-  uint32_t voff;
-  {
-    const int sub = lane >> 5, r7 = (lane >> 2) & 7, slot = lane & 3;
-    const int rg0 = wave / C::PPG, hc = wave % C::PPG;
-    const int q2 = (r7 >> 2) | ((rg0 & 1) << 1);             // 4 / PPG is even for d = 64, 128: parity independent of i
-    voff = (uint32_t)((rg0 * 8 + r7) * C::ROWB + (8 * hc + 4 * sub + (slot ^ q2)) * 16);
-  }
-  const uint32_t voff_strip = (uint32_t)lane * 4;
-  const uint32_t smem_base = lds_addr_of(smem);
-  auto issue = [&](int stage_t, int buf) {
-    const uint32_t bufp = __builtin_amdgcn_readfirstlane(smem_base + buf * C::BUF_BYTES);
-    const uint32_t soff = (uint32_t)stage_t * C::STAGE_BYTES;
-#pragma unroll
-    for (int i = 0; i < C::LPS; ++i) bdma16(voff, rs_h, soff + C::PSTEP * i, bufp + (4 * i + wave) * 1024);
-    if (wave == (stage_t & 3)) bdma4(voff_strip, rs_s, (uint32_t)stage_t * (C::TI * 4), bufp + C::STAGE_BYTES);
-  };
+  // ---- staging ------------------------------------------------------------------------------------------------------
+  const ImgStager<C> stg(lane, wave, lds_addr_of(smem), 0, make_rsrc(a.H_b, a.n_states * C::ROWB), make_rsrc(a.nlse2, a.n_states * 4));
+  auto issue = [&](int stage_t, int buf) { stg.all(stage_t, buf); };
 
-  // ---- read geometry (see qde_kernel).  Two sets of per-lane bases, one per ring buffer; they swap at the end of every
+  // ---- read geometry.  Two sets of per-lane bases, one per ring buffer; they swap at the end of every
   // stage, so the stage body is written once and every LDS address in it is "base register + immediate"
   const lds_u8* lbase = (const lds_u8*)smem;
   const lds_u8 *pA0, *pA1, *pT0, *pT1, *pS;          // current buffer
   const lds_u8 *nA0, *nA1, *nT0, *nT1, *nS;          // the next buffer of the ring
-  int oa0, oa1, ot0, ot1, os;
-  {
-    const int g1 = (lane >> 4) & 1, q = (lane & 15) >> 2, p = lane & 3;
-    oa0 = C::RG_BYTES * (r >> 3) + 64 * (r & 7) + 16 * ((0 + h) ^ ((r >> 2) & 3));
-    oa1 = C::RG_BYTES * (r >> 3) + 64 * (r & 7) + 16 * ((2 + h) ^ ((r >> 2) & 3));
-    ot0 = 64 * (4 * h + q) + 16 * ((2 * g1 + (p >> 1)) ^ ((0 + h) & 3)) + 8 * (p & 1);
-    ot1 = 64 * (4 * h + q) + 16 * ((2 * g1 + (p >> 1)) ^ ((2 + h) & 3)) + 8 * (p & 1);
-    os = C::STAGE_BYTES + 16 * h;
-  }
+  const ImgRead o = img_read_offsets<C>(lane);
   // per-lane bases of buffers `bc` (current) and `bn` (next): recomputed when the ring turns (10 adds per 64 MFMAs)
   auto set_ptrs = [&](int bc, int bn) {
     const lds_u8* c0 = lbase + bc * C::BUF_BYTES;
     const lds_u8* n0 = lbase + bn * C::BUF_BYTES;
-    pA0 = c0 + oa0; pA1 = c0 + oa1; pT0 = c0 + ot0; pT1 = c0 + ot1; pS = c0 + os;
-    nA0 = n0 + oa0; nA1 = n0 + oa1; nT0 = n0 + ot0; nT1 = n0 + ot1; nS = n0 + os;
+    pA0 = c0 + o.oa0; pA1 = c0 + o.oa1; pT0 = c0 + o.ot0; pT1 = c0 + o.ot1; pS = c0 + o.os;
+    nA0 = n0 + o.oa0; nA1 = n0 + o.oa1; nT0 = n0 + o.ot0; nT1 = n0 + o.ot1; nS = n0 + o.os;
   };
   set_ptrs(0, 1 % QDE2_NBUF);
 
@@ -115,17 +91,10 @@ __global__ __launch_bounds__(256, 1) void qde2_kernel(QDeArgs a) {
     for (int gi = 0; gi < 2; ++gi) {
       int64_t row = (int64_t)grp * QDE2_ITEMS + wave * 64 + gi * 32 + r;
       if (row >= a.n_items) row = a.n_items - 1;
-#pragma unroll
-      for (int s = 0; s < KS; ++s) rf[gi][s] = *reinterpret_cast<const bf16x8*>(a.E_b + row * D + 16 * s + 8 * h);
+      load_owner_frags<D>(a.E_b, row, a.n_items, h, rf[gi]);
       bv[gi] = a.bias[row];
     }
-    // These ordinary loads must be retired -- in hipcc's own bookkeeping too -- before the next LDS-DMA is issued: its
-    // counted waits assume that nothing younger than its loads is in flight (cdna_hip_programming.md 5, trap (b)).  The
-    // builtin is a wait the compiler models (vmcnt(0) only: 0x0F70); an empty asm with "+v" operands would do as well but
-    // pins the fragments to the VGPR half, and the MFMA operands then get copied to AGPRs in every loop trip.
-    __builtin_amdgcn_s_waitcnt(0x0F70);
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    owner_fence();
 #pragma unroll
     for (int gi = 0; gi < 2; ++gi) {
       bl2[gi] = bv[gi] * CQL_LOG2E;
@@ -203,37 +172,20 @@ __global__ __launch_bounds__(256, 1) void qde2_kernel(QDeArgs a) {
   f32x16 acc0, acc1;        // S accumulators: A writes acc0, B writes acc1
   bf16x8 tf[2][FT][2];      // transposed fragments, by tile parity inside the stage
   bf16x8 dpa, dpb;          // P1 fragments of the previous tile (for the D products still pending)
-  float ht0 = 0.f, ht1 = 0.f;      // the two exponent arguments / values travelling from half A to half B of a chunk
-  // half-chunks of the exponentials.  Volatile asm: hipcc would otherwise regroup them (sinks the column sums to the end
-  // of the stage as v_pk_add_f32 and keeps every exponential alive).  Half B reads a v_exp result one instruction later
-  // at the earliest (gfx950: one wait state behind a transcendental).
+  QExpPair ex;              // half-chunks of the exponentials
   auto half_a = [&](const f32x16& acc, int k, float b0, float b1) {
 #ifdef QDE2_ABL_NOCHUNK      // timing-only build: no exponentials
-    ht0 = acc[2 * k]; ht1 = acc[2 * k + 1];
+    ex.ht0 = acc[2 * k]; ex.ht1 = acc[2 * k + 1];
     return;
 #endif
-    asm volatile(
-        "v_fmamk_f32 %0, %2, 0x3fb8aa3b, %4\n\t"
-        "v_fmamk_f32 %1, %3, 0x3fb8aa3b, %5\n\t"
-        "v_exp_f32 %0, %0"
-        : "=&v"(ht0), "=&v"(ht1)
-        : "v"(acc[2 * k]), "v"(acc[2 * k + 1]), "v"(b0), "v"(b1));
+    ex.a(acc, k, b0, b1);
   };
   auto half_b = [&](uint32_t& w, float& csum) {
 #ifdef QDE2_ABL_NOCHUNK
-    asm volatile("v_cvt_pk_bf16_f32 %0, %1, %2" : "=&v"(w) : "v"(ht0), "v"(ht1));
+    asm volatile("v_cvt_pk_bf16_f32 %0, %1, %2" : "=&v"(w) : "v"(ex.ht0), "v"(ex.ht1));
     return;
 #endif
-    asm volatile(
-        "v_exp_f32 %1, %1\n\t"
-        "v_add_f32 %3, %3, %0\n\t"
-        "v_add_f32 %3, %3, %1\n\t"
-        "v_cvt_pk_bf16_f32 %2, %0, %1"
-        : "+v"(ht0), "+v"(ht1), "=&v"(w), "+v"(csum));
-  };
-  auto frag = [](const uint32_t (&pw)[8], int s2) {
-    u32x4 v = {pw[4 * s2 + 0], pw[4 * s2 + 1], pw[4 * s2 + 2], pw[4 * s2 + 3]};
-    return __builtin_bit_cast(bf16x8, v);
+    ex.b(w, csum);
   };
   // LDS reads of the tile FOLLOWING tile (cur buffer, IT): NIT = its index in its stage, from the other buffer if IT is
   // the last tile of the stage.  idx 0..3 strip, 4..11 rows, 12..27 transposed.
@@ -361,8 +313,8 @@ __global__ __launch_bounds__(256, 1) void qde2_kernel(QDeArgs a) {
         acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[P][s], rf[1][s], acc1, 0, 0, 0);
       } else if (gp < 21) {
         const int m = gp - 13, ft = m % FT, s2 = m / FT;
-        if (m == 0) pa0 = frag(pw0, 0);
-        if (m == FT) pb0 = frag(pw0, 1);
+        if (m == 0) pa0 = q_frag(pw0, 0);
+        if (m == FT) pb0 = q_frag(pw0, 1);
         y[0][ft] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tf[P][ft][s2], s2 ? pb0 : pa0, y[0][ft], 0, 0, 0);
       } else if (gp < 29) {
         const int s = gp - 21;
@@ -370,7 +322,7 @@ __global__ __launch_bounds__(256, 1) void qde2_kernel(QDeArgs a) {
         acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[P ^ 1][s], rf[0][s], acc0, 0, 0, 0);
       } else {
         const int m = gp - 29, ft = m % FT;
-        if (m == 0) pa1 = frag(pw1, 0);
+        if (m == 0) pa1 = q_frag(pw1, 0);
         y[1][ft] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tf[P][ft][0], pa1, y[1][ft], 0, 0, 0);
       }
       QDE2_FENCE();
@@ -397,7 +349,7 @@ __global__ __launch_bounds__(256, 1) void qde2_kernel(QDeArgs a) {
     cs[0] += c0;
     cs[1] += c1;
     dpa = pa1;
-    dpb = frag(pw1, 1);
+    dpb = q_frag(pw1, 1);
   };
 
   load_owner(g);

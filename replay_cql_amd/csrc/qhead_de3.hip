@@ -18,7 +18,7 @@
 // and forming that tile's scores on its own; the scores the previous piece formed for it with ITS items are dropped.
 #include <stdlib.h>
 #include <type_traits>
-#include "qhead_de_common.h"
+#include "qhead_image.h"
 
 #define QDE3_ITEMS 128
 #define QDE3_NBUF 3
@@ -49,18 +49,10 @@ __global__ __launch_bounds__(256, 1) void qde3_kernel(QDeArgs a) {
   int t_seg = t;
   int t_dma = t;
 
-  // ---- staging (qfwd3_kernel's: piece 4 i + wave = 8-row group i, column octet `wave`; parity of the row group = i & 1) ----
-  __amdgpu_buffer_rsrc_t rs_h = __builtin_amdgcn_make_buffer_rsrc((void*)a.H_b, 0, (int)(a.n_states * C::ROWB), 0x00020000);
-  __amdgpu_buffer_rsrc_t rs_s = __builtin_amdgcn_make_buffer_rsrc((void*)a.nlse2, 0, (int)(a.n_states * 4), 0x00020000);
-  uint32_t voff[2];
-  {
-    const int sub = lane >> 5, r7 = (lane >> 2) & 7, slot = lane & 3;
-#pragma unroll
-    for (int par = 0; par < 2; ++par) {
-      const int q2 = (r7 >> 2) | (par << 1);
-      voff[par] = (uint32_t)(r7 * C::ROWB + (8 * wave + 4 * sub + (slot ^ q2)) * 16);
-    }
-  }
+  // ---- staging (piece 4 i + wave = 8-row group i, column octet `wave`; parity of the row group = i & 1) ----
+  __amdgpu_buffer_rsrc_t rs_h = make_rsrc(a.H_b, a.n_states * C::ROWB);
+  __amdgpu_buffer_rsrc_t rs_s = make_rsrc(a.nlse2, a.n_states * 4);
+  const uint32_t voff[2] = {img_stage_voff<C>(lane, wave, 0), img_stage_voff<C>(lane, wave, 1)};
   const uint32_t voff_strip = (uint32_t)lane * 4;
   const uint32_t smem_base = lds_addr_of(smem);
   auto issue_piece = [&](int stage_t, int buf, int i) __attribute__((always_inline)) {
@@ -74,23 +66,15 @@ __global__ __launch_bounds__(256, 1) void qde3_kernel(QDeArgs a) {
 
   // ---- read geometry ------------------------------------------------------------------------------------------------
   const lds_u8* lbase = (const lds_u8*)smem;
-  int oa0, oa1, ot0, ot1, os;
-  {
-    const int g1 = (lane >> 4) & 1, q = (lane & 15) >> 2, p = lane & 3;
-    oa0 = C::RG_BYTES * (r >> 3) + 64 * (r & 7) + 16 * ((0 + h) ^ ((r >> 2) & 3));
-    oa1 = C::RG_BYTES * (r >> 3) + 64 * (r & 7) + 16 * ((2 + h) ^ ((r >> 2) & 3));
-    ot0 = 64 * (4 * h + q) + 16 * ((2 * g1 + (p >> 1)) ^ ((0 + h) & 3)) + 8 * (p & 1);
-    ot1 = 64 * (4 * h + q) + 16 * ((2 * g1 + (p >> 1)) ^ ((2 + h) & 3)) + 8 * (p & 1);
-    os = C::STAGE_BYTES + 16 * h;
-  }
+  const ImgRead o = img_read_offsets<C>(lane);
   const lds_u8 *pT0, *pT1;              // transposed reads: the CURRENT tile's buffer
   const lds_u8 *fA0, *fA1, *fS;         // rows + strip: the buffer of the tile after next (or whichever set_ptrs names)
   auto set_ptrs = [&](int b_cur, int b_far) __attribute__((always_inline)) {
-    pT0 = lbase + b_cur * C::BUF_BYTES + ot0;
-    pT1 = lbase + b_cur * C::BUF_BYTES + ot1;
-    fA0 = lbase + b_far * C::BUF_BYTES + oa0;
-    fA1 = lbase + b_far * C::BUF_BYTES + oa1;
-    fS = lbase + b_far * C::BUF_BYTES + os;
+    pT0 = lbase + b_cur * C::BUF_BYTES + o.ot0;
+    pT1 = lbase + b_cur * C::BUF_BYTES + o.ot1;
+    fA0 = lbase + b_far * C::BUF_BYTES + o.oa0;
+    fA1 = lbase + b_far * C::BUF_BYTES + o.oa1;
+    fS = lbase + b_far * C::BUF_BYTES + o.os;
   };
 
   // ---- owner state: one 32-item group per wave ---------------------------------------------------------------------------
@@ -104,9 +88,7 @@ __global__ __launch_bounds__(256, 1) void qde3_kernel(QDeArgs a) {
 #pragma unroll
     for (int s = 0; s < KS; ++s) rf[s] = *reinterpret_cast<const bf16x8*>(a.E_b + row * D + 16 * s + 8 * h);
     const float bv = a.bias[row];
-    __builtin_amdgcn_s_waitcnt(0x0F70);       // (see qde2_kernel::load_owner)
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    owner_fence();
     bl2 = bv * CQL_LOG2E;
 #pragma unroll
     for (int ft = 0; ft < FT; ++ft)
@@ -174,10 +156,6 @@ __global__ __launch_bounds__(256, 1) void qde3_kernel(QDeArgs a) {
         "v_add_f32 %3, %3, %1\n\t"
         "v_cvt_pk_bf16_f32 %2, %0, %1"
         : "+v"(ht0), "+v"(ht1), "=&v"(w), "+v"(csum));
-  };
-  auto frag = [](const uint32_t (&pw)[8], int s2) __attribute__((always_inline)) {
-    u32x4 v = {pw[4 * s2 + 0], pw[4 * s2 + 1], pw[4 * s2 + 2], pw[4 * s2 + 3]};
-    return __builtin_bit_cast(bf16x8, v);
   };
   auto far_read = [&](int idx) __attribute__((always_inline)) {     // rows (0..15) and strip quarters (16..19) at fA / fS
     if (idx < KS) {
@@ -247,8 +225,8 @@ __global__ __launch_bounds__(256, 1) void qde3_kernel(QDeArgs a) {
         const int m = gp - 16, ft = m % FT, s2 = m / FT;
         if (m == 0) {
           ring_turn();
-          pa = frag(pw, 0);
-          pb = frag(pw, 1);
+          pa = q_frag(pw, 0);
+          pb = q_frag(pw, 1);
         }
         y[ft] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tf[ft][s2], s2 ? pb : pa, y[ft], 0, 0, 0);
         QDE3_FENCE();

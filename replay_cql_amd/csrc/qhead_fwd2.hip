@@ -8,7 +8,7 @@
 // that is ~220 B/clk of LDS traffic, the LDS limit (0.207 ms at cfg3, MFMA busy 43 %).  Here the same 28 KB feed 32 MFMAs.
 //
 // Reference of the exponentials: FIXED per (item slice, state) -- the maximum of the slice's FIRST tile plus
-// QF2_REF_MARGIN nats -- instead of the running reference of the first form.  P = exp(S - ref) then exceeds 1 for scores
+// QF_REF_MARGIN nats -- instead of the running reference of the first form.  P = exp(S - ref) then exceeds 1 for scores
 // above the reference, which costs nothing (bf16 and fp32 keep their relative precision over 2^+-126; the partial sums
 // are merged relative to the slices' references by qhead_finalize_lse_kernel / qhead_dh_finish_kernel as before); only a
 // score more than ~80 nats above the first tile's maximum would overflow.  That case is detected (non-finite partial
@@ -19,26 +19,7 @@
 // groups), C = Y0, D = Y1 (Y += E^T . P), 32 half-chunks of the exponentials, one LDS read per gap (see qhead_de2.hip).
 #include <stdlib.h>
 #include <type_traits>
-#include "qhead_de_common.h"
-
-#define QF2_REF_MARGIN 8.0f
-
-// Y += A . B with the accumulator in AccVGPRs, as inline asm: the builtin form of this translation unit
-// (-amdgpu-mfma-vgpr-form, which the score chains need: the VALU reads their results) would put the 128 accumulator
-// registers of Y into the VGPR half too, and the rest of the kernel then no longer fits there -- hipcc parks owner
-// fragments in AccVGPRs and copies them back in front of every product.  A = transposed item fragment (VGPRs: where
-// hipcc lets the ds_read_tr land), B = probability fragment (VGPRs).  The leading s_nop covers "VALU wrote B just before"
-// (the hazard recogniser does not look into asm); products on the same accumulator are four products apart.
-#ifndef QF2_BUILTIN_Y
-__device__ __forceinline__ void qf2_mfma_y(f32x16& y, const bf16x8& a_frag, const bf16x8& b_frag) {
-  const u32x4 av = __builtin_bit_cast(u32x4, a_frag), bv = __builtin_bit_cast(u32x4, b_frag);
-  asm volatile("s_nop 1\n\tv_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+a"(y) : "v"(av), "v"(bv));
-}
-#else
-__device__ __forceinline__ void qf2_mfma_y(f32x16& y, const bf16x8& a_frag, const bf16x8& b_frag) {
-  y = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_frag, b_frag, y, 0, 0, 0);
-}
-#endif
+#include "qhead_fwd_common.h"
 
 #ifdef QF2_PROBE_PSTORE
 __device__ uint32_t* qf2_probe_p_dev;      // timing-only probe buffer (cql_qfwd2_run allocates it)
@@ -64,16 +45,10 @@ __global__ __launch_bounds__(256, 1) void qfwd2_kernel(QFwd2Args a) {
   if (nst <= 0) return;
   const uint32_t gst0 = (uint32_t)(s_begin / C::TI);
 
-  // ---- staging (see qde_kernel) ----------------------------------------------------------------------------------
-  __amdgpu_buffer_rsrc_t rs_e = __builtin_amdgcn_make_buffer_rsrc((void*)a.E_b, 0, (int)(a.n_items * C::ROWB), 0x00020000);
-  __amdgpu_buffer_rsrc_t rs_b = __builtin_amdgcn_make_buffer_rsrc((void*)a.bias, 0, (int)(a.n_items * 4), 0x00020000);
-  uint32_t voff;
-  {
-    const int sub = lane >> 5, r7 = (lane >> 2) & 7, slot = lane & 3;
-    const int rg0 = wave / C::PPG, hc = wave % C::PPG;
-    const int q2 = (r7 >> 2) | ((rg0 & 1) << 1);
-    voff = (uint32_t)((rg0 * 8 + r7) * C::ROWB + (8 * hc + 4 * sub + (slot ^ q2)) * 16);
-  }
+  // ---- staging --------------------------------------------------------------------------------------------------
+  __amdgpu_buffer_rsrc_t rs_e = make_rsrc(a.E_b, a.n_items * C::ROWB);
+  __amdgpu_buffer_rsrc_t rs_b = make_rsrc(a.bias, a.n_items * 4);
+  const uint32_t voff = img_stage_voff<C>(lane, wave, 0);
   const uint32_t voff_strip = (uint32_t)lane * 4;
   const uint32_t smem_base = lds_addr_of(smem);
   auto issue = [&](int stage, int buf) __attribute__((always_inline)) {
@@ -95,17 +70,12 @@ __global__ __launch_bounds__(256, 1) void qfwd2_kernel(QFwd2Args a) {
     }
   };
 
-  // ---- read geometry (see qde2_kernel): two sets of per-lane bases, swapped at the end of every stage -------------------
+  // ---- read geometry: two sets of per-lane bases, swapped at the end of every stage -------------------
   const lds_u8* lbase = (const lds_u8*)smem;
   const lds_u8 *pA0, *pA1, *pT0, *pT1, *pS;          // current buffer
   const lds_u8 *nA0, *nA1, *nT0, *nT1, *nS;          // the other buffer
   {
-    const int g1 = (lane >> 4) & 1, q = (lane & 15) >> 2, p = lane & 3;
-    const int oa0 = C::RG_BYTES * (r >> 3) + 64 * (r & 7) + 16 * ((0 + h) ^ ((r >> 2) & 3));
-    const int oa1 = C::RG_BYTES * (r >> 3) + 64 * (r & 7) + 16 * ((2 + h) ^ ((r >> 2) & 3));
-    const int ot0 = 64 * (4 * h + q) + 16 * ((2 * g1 + (p >> 1)) ^ ((0 + h) & 3)) + 8 * (p & 1);
-    const int ot1 = 64 * (4 * h + q) + 16 * ((2 * g1 + (p >> 1)) ^ ((2 + h) & 3)) + 8 * (p & 1);
-    const int os = C::STAGE_BYTES + 16 * h;
+    const auto [oa0, oa1, ot0, ot1, os] = img_read_offsets<C>(lane);
     pA0 = lbase + oa0; pA1 = lbase + oa1; pT0 = lbase + ot0; pT1 = lbase + ot1; pS = lbase + os;
     nA0 = pA0 + C::BUF_BYTES; nA1 = pA1 + C::BUF_BYTES; nT0 = pT0 + C::BUF_BYTES; nT1 = pT1 + C::BUF_BYTES;
     nS = pS + C::BUF_BYTES;
@@ -130,11 +100,6 @@ __global__ __launch_bounds__(256, 1) void qfwd2_kernel(QFwd2Args a) {
 #pragma unroll
     for (int s = 0; s < KS; ++s) rf[slot][s] = *reinterpret_cast<const bf16x8*>(base + row * D + 16 * s + 8 * h);
   };
-  auto owner_fence = [&]() __attribute__((always_inline)) {
-    __builtin_amdgcn_s_waitcnt(0x0F70);       // (see qde2_kernel::load_owner)
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  };
 #pragma unroll
   for (int gi = 0; gi < 2; ++gi)
 #pragma unroll
@@ -149,11 +114,7 @@ __global__ __launch_bounds__(256, 1) void qfwd2_kernel(QFwd2Args a) {
   bf16x8 tf[2][FT][2];
   bf16x8 dpa, dpb;
 
-  // half-chunks of the exponentials (qde2_kernel's; volatile asm: hipcc would otherwise regroup them).  -DQF2_PACKED
-  // selects packed forms (v_pk_fma_f32 for both exponent arguments, v_pk_add_f32 into a pair of partial sums: 5 instead
-  // of 7 instructions per pair) -- correct, but slower beside MFMAs (0.266 vs 0.198 ms): kept for A/B only.
-#ifndef QF2_PACKED
-  typedef float csum_t;
+  // half-chunks of the exponentials (volatile asm: hipcc would otherwise regroup them)
   float ht0 = 0.f, ht1 = 0.f;
   auto half_a = [&](const f32x16& acc, int k, float b0) __attribute__((always_inline)) {
     asm volatile(
@@ -170,36 +131,6 @@ __global__ __launch_bounds__(256, 1) void qfwd2_kernel(QFwd2Args a) {
         "v_add_f32 %3, %3, %1\n\t"
         "v_cvt_pk_bf16_f32 %2, %0, %1"
         : "+v"(ht0), "+v"(ht1), "=&v"(w), "+v"(csum));
-  };
-  auto csum_total = [](float c) __attribute__((always_inline)) { return c; };
-#else
-  // packed form: v_pk_fma_f32 forms both exponent arguments (accumulator elements 2k, 2k+1 are a register pair),
-  // v_pk_add_f32 adds both values to a pair of partial sums (even / odd elements)
-  typedef __attribute__((ext_vector_type(2))) float f32x2;
-  typedef f32x2 csum_t;
-  f32x2 ht = {0.f, 0.f};
-  f32x2 l2e2 = {CQL_LOG2E, CQL_LOG2E};
-  asm volatile("" : "+v"(l2e2));
-  auto half_a = [&](const f32x16& acc, int k, float b0) __attribute__((always_inline)) {
-    const f32x2 a2 = {acc[2 * k], acc[2 * k + 1]};
-    const f32x2 b2 = {b0, b0};
-    asm volatile("v_pk_fma_f32 %0, %1, %2, %3 op_sel_hi:[1,1,1]" : "=&v"(ht) : "v"(a2), "v"(l2e2), "v"(b2));
-    float e0 = ht[0];
-    asm volatile("v_exp_f32 %0, %0" : "+v"(e0));
-    ht[0] = e0;
-  };
-  auto half_b = [&](uint32_t& w, f32x2& csum) __attribute__((always_inline)) {
-    float e1 = ht[1];
-    asm volatile("v_exp_f32 %0, %0" : "+v"(e1));
-    ht[1] = e1;
-    asm volatile("v_pk_add_f32 %0, %0, %1 op_sel_hi:[1,1]" : "+v"(csum) : "v"(ht));
-    asm volatile("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(w) : "v"(ht[0]), "v"(ht[1]));
-  };
-  auto csum_total = [](f32x2 c) __attribute__((always_inline)) { return c[0] + c[1]; };
-#endif
-  auto frag = [](const uint32_t (&pw)[8], int s2) __attribute__((always_inline)) {
-    u32x4 v = {pw[4 * s2 + 0], pw[4 * s2 + 1], pw[4 * s2 + 2], pw[4 * s2 + 3]};
-    return __builtin_bit_cast(bf16x8, v);
   };
   // LDS reads of the tile FOLLOWING tile (cur buffer, IT): kind 0 = bias quarter idx, 1 = row fragment idx, 2 = transposed
   // read idx (0..15)
@@ -254,30 +185,30 @@ __global__ __launch_bounds__(256, 1) void qfwd2_kernel(QFwd2Args a) {
     constexpr int P = decltype(IT)::value & 1;
     constexpr bool END = decltype(IT)::value == C::TILES - 1;
     uint32_t pw0[8], pw1[8];
-    csum_t c0 = {}, c1 = {};
+    float c0 = 0.f, c1 = 0.f;
     bf16x8 pa0 = {}, pb0 = {}, pa1 = {};
 #pragma unroll
     for (int gp = 0; gp < 32; ++gp) {
       if (gp < 5) {
         const int m = 3 + gp, ft = m % FT, s2 = m / FT;
-        qf2_mfma_y(y[1][ft], tf[P ^ 1][ft][s2], s2 ? dpb : dpa);
+        q_mfma_y_acc(y[1][ft], tf[P ^ 1][ft][s2], s2 ? dpb : dpa);
       } else if (gp < 13) {
         const int s = gp - 5;
         if (s == 0) acc1 = sv;
         acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[s], rf[1][s], acc1, 0, 0, 0);
       } else if (gp < 21) {
         const int m = gp - 13, ft = m % FT, s2 = m / FT;
-        if (m == 0) pa0 = frag(pw0, 0);
-        if (m == FT) pb0 = frag(pw0, 1);
-        qf2_mfma_y(y[0][ft], tf[P][ft][s2], s2 ? pb0 : pa0);
+        if (m == 0) pa0 = q_frag(pw0, 0);
+        if (m == FT) pb0 = q_frag(pw0, 1);
+        q_mfma_y_acc(y[0][ft], tf[P][ft][s2], s2 ? pb0 : pa0);
       } else if (gp < 29) {
         const int s = gp - 21;
         if (s == 0) acc0 = sv;
         acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[s], rf[0][s], acc0, 0, 0, 0);
       } else {
         const int m = gp - 29, ft = m % FT;
-        if (m == 0) pa1 = frag(pw1, 0);
-        qf2_mfma_y(y[1][ft], tf[P][ft][0], pa1);
+        if (m == 0) pa1 = q_frag(pw1, 0);
+        q_mfma_y_acc(y[1][ft], tf[P][ft][0], pa1);
       }
       QF2_FENCE();
       {
@@ -297,10 +228,10 @@ __global__ __launch_bounds__(256, 1) void qfwd2_kernel(QFwd2Args a) {
       gap_read(IT, gp);
       QF2_FENCE();
     }
-    cs[0] += csum_total(c0);
-    cs[1] += csum_total(c1);
+    cs[0] += c0;
+    cs[1] += c1;
     dpa = pa1;
-    dpb = frag(pw1, 1);
+    dpb = q_frag(pw1, 1);
 #ifdef QF2_PROBE_PSTORE      // timing-only probe: what does it cost this kernel to write its P tiles out?
     {                        // 2 groups x 32 B per lane and tile, as four 1 KiB wave stores into a per-wave stream
       const int64_t tile = ((int64_t)blockIdx.x * 4 + wave) * (2 * nst) + 2 * st + decltype(IT)::value;
@@ -354,7 +285,7 @@ __global__ __launch_bounds__(256, 1) void qfwd2_kernel(QFwd2Args a) {
 #pragma unroll
     for (int i = 1; i < 16; ++i) m = fmaxf(m, t[i]);
     m = fmaxf(m, __shfl_xor(m, 32));
-    const float rv = (m == NEG_INF_F) ? 0.f : m + QF2_REF_MARGIN;
+    const float rv = (m == NEG_INF_F) ? 0.f : m + QF_REF_MARGIN;
     rl2[gi] = -rv * CQL_LOG2E;
     asm volatile("v_accvgpr_write_b32 %0, %1" : "=a"(ref_a[gi]) : "v"(rv));
     asm volatile("" : "+v"(rl2[gi]));      // (keeps the temporaries' uses in front of the loads below)
@@ -376,7 +307,7 @@ __global__ __launch_bounds__(256, 1) void qfwd2_kernel(QFwd2Args a) {
 #pragma unroll
   for (int m = 3; m < 2 * FT; ++m) {
     const int ft = m % FT, s2 = m / FT;
-    qf2_mfma_y(y[1][ft], tf[1][ft][s2], s2 ? dpb : dpa);
+    q_mfma_y_acc(y[1][ft], tf[1][ft][s2], s2 ? dpb : dpa);
   }
   asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");      // the last products have left the pipe before Y is read
 

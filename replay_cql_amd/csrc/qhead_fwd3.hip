@@ -20,15 +20,9 @@
 // Fixed per-(slice, state) reference, overflow flag + guarded fall-back, partial results: exactly as qfwd2_kernel.
 #include <stdlib.h>
 #include <type_traits>
-#include "qhead_de_common.h"
+#include "qhead_fwd_common.h"
 
-#define QF3_REF_MARGIN 8.0f
 #define QF3_NBUF 3
-
-__device__ __forceinline__ void qf3_mfma_y(f32x16& y, const bf16x8& a_frag, const bf16x8& b_frag) {
-  const u32x4 av = __builtin_bit_cast(u32x4, a_frag), bv = __builtin_bit_cast(u32x4, b_frag);
-  asm volatile("s_nop 1\n\tv_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+a"(y) : "v"(av), "v"(bv));
-}
 
 template <int D>
 __global__ __launch_bounds__(256, 1) void qfwd3_kernel(QFwd2Args a) {
@@ -40,70 +34,27 @@ __global__ __launch_bounds__(256, 1) void qfwd3_kernel(QFwd2Args a) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int r = lane & 31, h = lane >> 5;
-  const int split = blockIdx.x % a.nsplit;
-  const int64_t rblk = blockIdx.x / a.nsplit;
-  const int64_t s_begin = (int64_t)split * a.split_rows;
-  const int64_t s_end = (s_begin + a.split_rows < a.n_items) ? (s_begin + a.split_rows) : a.n_items;
-  const int nst = (s_end > s_begin) ? (int)((s_end - s_begin + C::TI - 1) / C::TI) : 0;
+  const QSlice sl = slice_preamble<C::TI>(a.nsplit, a.split_rows, a.n_items);
+  const int nst = sl.nst;
   if (nst <= 0) return;
-  const uint32_t gst0 = (uint32_t)(s_begin / C::TI);
 
-  // ---- staging: piece 4 i + wave of a stage = 8-row group i, column octet `wave` (see qde_kernel; the row group's parity,
-  // which enters the image's swizzle, alternates with i here) ---------------------------------------------------------
-  __amdgpu_buffer_rsrc_t rs_e = __builtin_amdgcn_make_buffer_rsrc((void*)a.E_b, 0, (int)(a.n_items * C::ROWB), 0x00020000);
-  __amdgpu_buffer_rsrc_t rs_b = __builtin_amdgcn_make_buffer_rsrc((void*)a.bias, 0, (int)(a.n_items * 4), 0x00020000);
-  uint32_t voff[2];
-  {
-    const int sub = lane >> 5, r7 = (lane >> 2) & 7, slot = lane & 3;
-#pragma unroll
-    for (int par = 0; par < 2; ++par) {
-      const int q2 = (r7 >> 2) | (par << 1);
-      voff[par] = (uint32_t)(r7 * C::ROWB + (8 * wave + 4 * sub + (slot ^ q2)) * 16);
-    }
-  }
-  const uint32_t voff_strip = (uint32_t)lane * 4;
-  const uint32_t smem_base = lds_addr_of(smem);
-  auto issue_piece = [&](int stage, int buf, int i) __attribute__((always_inline)) {
-    const uint32_t bufp = __builtin_amdgcn_readfirstlane(smem_base + buf * C::BUF_BYTES);
-    const uint32_t gs = gst0 + (uint32_t)stage;
-    bdma16(voff[i & 1], rs_e, gs * C::STAGE_BYTES + C::PSTEP * i, bufp + (4 * i + wave) * 1024);
-  };
-  auto issue_strip = [&](int stage, int buf) __attribute__((always_inline)) {
-    const uint32_t bufp = __builtin_amdgcn_readfirstlane(smem_base + buf * C::BUF_BYTES);
-    const uint32_t gs = gst0 + (uint32_t)stage;
-    if (wave == (stage & 3)) bdma4(voff_strip, rs_b, gs * (C::TI * 4), bufp + C::STAGE_BYTES);
-  };
-  // Items past the end of the catalogue (last stage of the last slice): rows and bias read as 0 (buffer bounds); a bias of
-  // -inf makes their probabilities exactly 0.  Block-uniform; called between the turn's barrier and the first read.
+  // ---- staging: piece 4 i + wave of a stage = 8-row group i, column octet `wave` (the row group's parity alternates with i) ----
+  const ImgStager<C> stg(lane, wave, lds_addr_of(smem), sl.gst0, make_rsrc(a.E_b, a.n_items * C::ROWB), make_rsrc(a.bias, a.n_items * 4));
   auto patch_strip = [&](int stage, int buf) __attribute__((always_inline)) {
-    const int64_t valid = a.n_items - (int64_t)(gst0 + (uint32_t)stage) * C::TI;
-    if (valid < C::TI) {
-      if (wave == 0 && lane < C::TI && lane >= valid)
-        *(__attribute__((address_space(3))) float*)((lds_u8*)smem + buf * C::BUF_BYTES + C::STAGE_BYTES + lane * 4) = NEG_INF_F;
-      __builtin_amdgcn_s_waitcnt(0xC07F);
-      __builtin_amdgcn_s_barrier();
-    }
+    img_patch_strip<C>((lds_u8*)smem, buf, a.n_items - (int64_t)(sl.gst0 + (uint32_t)stage) * C::TI, lane, wave);
   };
 
-  // ---- read geometry (qde_kernel's image): per-lane offsets inside a buffer; bases recomputed when the ring turns ----------
+  // ---- read geometry: per-lane offsets inside a buffer; bases recomputed when the ring turns ----------------------------
   const lds_u8* lbase = (const lds_u8*)smem;
-  int oa0, oa1, ot0, ot1, os;
-  {
-    const int g1 = (lane >> 4) & 1, q = (lane & 15) >> 2, p = lane & 3;
-    oa0 = C::RG_BYTES * (r >> 3) + 64 * (r & 7) + 16 * ((0 + h) ^ ((r >> 2) & 3));
-    oa1 = C::RG_BYTES * (r >> 3) + 64 * (r & 7) + 16 * ((2 + h) ^ ((r >> 2) & 3));
-    ot0 = 64 * (4 * h + q) + 16 * ((2 * g1 + (p >> 1)) ^ ((0 + h) & 3)) + 8 * (p & 1);
-    ot1 = 64 * (4 * h + q) + 16 * ((2 * g1 + (p >> 1)) ^ ((2 + h) & 3)) + 8 * (p & 1);
-    os = C::STAGE_BYTES + 16 * h;
-  }
+  const ImgRead o = img_read_offsets<C>(lane);
   const lds_u8 *pT0, *pT1;              // transposed reads: the CURRENT tile's buffer
   const lds_u8 *fA0, *fA1, *fS;         // rows + bias: the buffer of the tile after next
   auto set_ptrs = [&](int b_cur, int b_far) __attribute__((always_inline)) {
-    pT0 = lbase + b_cur * C::BUF_BYTES + ot0;
-    pT1 = lbase + b_cur * C::BUF_BYTES + ot1;
-    fA0 = lbase + b_far * C::BUF_BYTES + oa0;
-    fA1 = lbase + b_far * C::BUF_BYTES + oa1;
-    fS = lbase + b_far * C::BUF_BYTES + os;
+    pT0 = lbase + b_cur * C::BUF_BYTES + o.ot0;
+    pT1 = lbase + b_cur * C::BUF_BYTES + o.ot1;
+    fA0 = lbase + b_far * C::BUF_BYTES + o.oa0;
+    fA1 = lbase + b_far * C::BUF_BYTES + o.oa1;
+    fS = lbase + b_far * C::BUF_BYTES + o.os;
   };
 
   // ---- owner state: one 32-state group per wave ------------------------------------------------------------------------
@@ -122,27 +73,7 @@ __global__ __launch_bounds__(256, 1) void qfwd3_kernel(QFwd2Args a) {
   f32x16 acc0, acc1;        // score accumulators by tile parity
   bf16x8 tf[FT][2];         // transposed fragments of the current tile
 
-  float ht0 = 0.f, ht1 = 0.f;
-  auto half_a = [&](const f32x16& acc, int k, float b0) __attribute__((always_inline)) {
-    asm volatile(
-        "v_fmamk_f32 %0, %2, 0x3fb8aa3b, %4\n\t"
-        "v_fmamk_f32 %1, %3, 0x3fb8aa3b, %4\n\t"
-        "v_exp_f32 %0, %0"
-        : "=&v"(ht0), "=&v"(ht1)
-        : "v"(acc[2 * k]), "v"(acc[2 * k + 1]), "v"(b0));
-  };
-  auto half_b = [&](uint32_t& w, float& csum) __attribute__((always_inline)) {
-    asm volatile(
-        "v_exp_f32 %1, %1\n\t"
-        "v_add_f32 %3, %3, %0\n\t"
-        "v_add_f32 %3, %3, %1\n\t"
-        "v_cvt_pk_bf16_f32 %2, %0, %1"
-        : "+v"(ht0), "+v"(ht1), "=&v"(w), "+v"(csum));
-  };
-  auto frag = [](const uint32_t (&pw)[8], int s2) __attribute__((always_inline)) {
-    u32x4 v = {pw[4 * s2 + 0], pw[4 * s2 + 1], pw[4 * s2 + 2], pw[4 * s2 + 3]};
-    return __builtin_bit_cast(bf16x8, v);
-  };
+  QExpPair ex;
   // rows (idx 0..15) and bias quarters (idx 16..19) of the far tile; transposed read q (0..31) of the current tile
   auto far_read = [&](int idx) __attribute__((always_inline)) {
     if (idx < KS) {
@@ -200,8 +131,8 @@ __global__ __launch_bounds__(256, 1) void qfwd3_kernel(QFwd2Args a) {
         QF3_FENCE();
         {
           const int k = gp >> 1;
-          if ((gp & 1) == 0) half_a(PAR == 0 ? acc0 : acc1, k, rl2);
-          else half_b(pw[k], c0);
+          if ((gp & 1) == 0) ex.a(PAR == 0 ? acc0 : acc1, k, rl2, rl2);
+          else ex.b(pw[k], c0);
         }
         QF3_FENCE();
         tr_read(2 * gp);
@@ -211,14 +142,14 @@ __global__ __launch_bounds__(256, 1) void qfwd3_kernel(QFwd2Args a) {
         const int m = gp - 16, ft = m % FT, s2 = m / FT;
         if (m == 0) {
           ring_turn();
-          pa = frag(pw, 0);
-          pb = frag(pw, 1);
+          pa = q_frag(pw, 0);
+          pb = q_frag(pw, 1);
         }
-        qf3_mfma_y(y[ft], tf[ft][s2], s2 ? pb : pa);
+        q_mfma_y_acc(y[ft], tf[ft][s2], s2 ? pb : pa);
         QF3_FENCE();
         // the buffer just left is refilled three stages ahead, one piece per gap behind the turn
-        if (m < C::LPS) issue_piece(issued, b_cur, m);
-        else if (m == C::LPS) issue_strip(issued, b_cur);
+        if (m < C::LPS) stg.piece(issued, b_cur, m);
+        else if (m == C::LPS) stg.strip(issued, b_cur);
         QF3_FENCE();
         far_read(m);          // rows of the tile after next, one per gap; its bias in the last four gaps
         if (m >= 12) far_read(KS + (m - 12));
@@ -231,9 +162,7 @@ __global__ __launch_bounds__(256, 1) void qfwd3_kernel(QFwd2Args a) {
 
   // ---- prologue: the whole ring in flight ------------------------------------------------------------------------------
   for (int s0 = 0; s0 < QF3_NBUF && s0 < nst; ++s0) {
-#pragma unroll
-    for (int i = 0; i < C::LPS; ++i) issue_piece(s0, s0, i);
-    issue_strip(s0, s0);
+    stg.all(s0, s0);
     ++issued;
   }
   de_wait_vmcnt<0>();
@@ -243,37 +172,11 @@ __global__ __launch_bounds__(256, 1) void qfwd3_kernel(QFwd2Args a) {
   set_ptrs(0, 0);
 #pragma unroll
   for (int idx = 0; idx < KS + 4; ++idx) far_read(idx);
-  // Scores of the first tile through TEMPORARY fragments: their maximum fixes the reference (see qfwd2_kernel)
-  float ref_a;
-  {
-    bf16x8 tmpf[KS];
-    {
-      int64_t row = rblk * 128 + wave * 32 + r;
-      if (row >= a.n_states) row = a.n_states - 1;
-#pragma unroll
-      for (int s = 0; s < KS; ++s) tmpf[s] = *reinterpret_cast<const bf16x8*>(a.H_b + row * D + 16 * s + 8 * h);
-    }
-    f32x16 t = sv;
-#pragma unroll
-    for (int s = 0; s < KS; ++s) t = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[s], tmpf[s], t, 0, 0, 0);
-    float m = t[0];
-#pragma unroll
-    for (int i = 1; i < 16; ++i) m = fmaxf(m, t[i]);
-    m = fmaxf(m, __shfl_xor(m, 32));
-    const float rv = (m == NEG_INF_F) ? 0.f : m + QF3_REF_MARGIN;
-    rl2 = -rv * CQL_LOG2E;
-    asm volatile("v_accvgpr_write_b32 %0, %1" : "=a"(ref_a) : "v"(rv));
-    asm volatile("" : "+v"(rl2));
-  }
-  {
-    int64_t row = rblk * 128 + wave * 32 + r;
-    if (row >= a.n_states) row = a.n_states - 1;
-#pragma unroll
-    for (int s = 0; s < KS; ++s) rf[s] = *reinterpret_cast<const bf16x8*>(a.H_b + row * D + 16 * s + 8 * h);
-    __builtin_amdgcn_s_waitcnt(0x0F70);       // (see qde2_kernel::load_owner)
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  }
+  const int64_t row = sl.rblk * 128 + wave * 32 + r;
+  float ref_a;      // the reference, parked in an AccVGPR until the end (the loop needs only rl2)
+  first_tile_reference<D>(af, sv, a.H_b, row, a.n_states, h, rl2, ref_a);
+  load_owner_frags<D>(a.H_b, row, a.n_states, h, rf);
+  owner_fence();
   acc0 = sv;        // scores of tile 0
 #pragma unroll
   for (int s = 0; s < KS; ++s) acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[s], rf[s], acc0, 0, 0, 0);
@@ -308,28 +211,7 @@ __global__ __launch_bounds__(256, 1) void qfwd3_kernel(QFwd2Args a) {
   asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");      // the last products have left the pipe before Y is read
   de_wait_vmcnt<0>();      // the stages issued past the slice have landed before this wave gives its LDS back
 
-  // ---- partials: (reference, sum relative to it) and the un-normalised slab ---------------------------------------------
-  {
-    const int64_t row = rblk * 128 + wave * 32 + r;
-    const float ls = cs + __shfl_xor(cs, 32);
-    if (row < a.n_states) {
-      const int64_t pidx = (int64_t)split * a.n_states + row;
-      float* dst = a.slab + pidx * D;
-#pragma unroll
-      for (int ft = 0; ft < FT; ++ft)
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-          *reinterpret_cast<float4*>(dst + ft * 32 + 8 * q + 4 * h) =
-              make_float4(y[ft][4 * q + 0], y[ft][4 * q + 1], y[ft][4 * q + 2], y[ft][4 * q + 3]);
-      if (h == 0) {
-        float rv;
-        asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(rv) : "a"(ref_a));
-        a.part_a[pidx] = rv;
-        a.part_b[pidx] = ls;
-        if (!(ls < 3.0e38f) && a.flag) atomicOr(a.flag, 1);      // inf or NaN: the guarded first form redoes the pass
-      }
-    }
-  }
+  store_partials<D>(a, sl.split, row, h, y, cs, ref_a);
 }
 
 // =============================================================================================================

@@ -32,7 +32,7 @@
 // queues 4 waves x 2 groups x 24 x 512 B = 96 KiB.  The lists (2 x 16 keys per lane) sit in AGPRs.
 #include <stdlib.h>
 #include <type_traits>
-#include "qhead_de_common.h"
+#include "qhead_image.h"
 
 #define TK2_Q 24         // queue entries per lane and group: a tile adds at most 16, so a merge in front of a tile
                          // whenever some lane holds more than 8 keeps the scan of the tile free of overflow handling
@@ -118,20 +118,11 @@ __global__ __launch_bounds__(256, 1) void qtopk2_kernel(QTk2Args a) {
   // ---- user fragments ------------------------------------------------------------------------------------------------
   bf16x8 rf[2][KS];
 #pragma unroll
-  for (int g = 0; g < 2; ++g) {
-    int64_t row = res0 + g * 32 + r;
-    if (row >= a.n_users) row = a.n_users - 1;
-#pragma unroll
-    for (int s = 0; s < KS; ++s) rf[g][s] = *reinterpret_cast<const bf16x8*>(a.H_b + row * D + 16 * s + 8 * h);
-  }
-  // retired in hipcc's own bookkeeping before the first LDS-DMA is issued (see qde2_kernel::load_owner)
-  __builtin_amdgcn_s_waitcnt(0x0F70);
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  for (int g = 0; g < 2; ++g) load_owner_frags<D>(a.H_b, res0 + g * 32 + r, a.n_users, h, rf[g]);
+  owner_fence();
 
   // ---- staging ---------------------------------------------------------------------------------------------------------
-  __amdgpu_buffer_rsrc_t rs_e = __builtin_amdgcn_make_buffer_rsrc((void*)a.E_b, 0, (int)(a.n_cand * C::ROWB), 0x00020000);
-  __amdgpu_buffer_rsrc_t rs_b = __builtin_amdgcn_make_buffer_rsrc((void*)a.bias, 0, (int)(a.n_cand * 4), 0x00020000);
+  __amdgpu_buffer_rsrc_t rs_e = make_rsrc(a.E_b, a.n_cand * C::ROWB), rs_b = make_rsrc(a.bias, a.n_cand * 4);
   // seen words of this wave's 64 users: [stage][64 users][2 words], 512 B per stage; no filter = an empty buffer (reads 0)
   // A wave whose 64 users all lie past n_users (the tail of the last 256-user row-block) has no group in the bitmap --
   // it holds ceil(n_users / 64) groups -- and gets the empty buffer too: its rows are discarded, and num_records is
@@ -140,14 +131,8 @@ __global__ __launch_bounds__(256, 1) void qtopk2_kernel(QTk2Args a) {
   const bool has_seen = a.seen_bits != nullptr && res0 < a.n_users;        // wave-uniform
   const uint32_t* wsrc = has_seen ? a.seen_bits + (res0 >> 6) * nst_all * 128 : (const uint32_t*)a.bias;
   __amdgpu_buffer_rsrc_t rs_w =
-      __builtin_amdgcn_make_buffer_rsrc((void*)wsrc, 0, has_seen ? (int)(nst_all * 512) : 0, 0x00020000);
-  uint32_t voff;
-  {
-    const int sub = lane >> 5, r7 = (lane >> 2) & 7, slot = lane & 3;
-    const int rg0 = wave / C::PPG, hc = wave % C::PPG;
-    const int q2 = (r7 >> 2) | ((rg0 & 1) << 1);
-    voff = (uint32_t)((rg0 * 8 + r7) * C::ROWB + (8 * hc + 4 * sub + (slot ^ q2)) * 16);
-  }
+      make_rsrc(wsrc, has_seen ? nst_all * 512 : 0);
+  const uint32_t voff = img_stage_voff<C>(lane, wave, 0);
   const uint32_t voff4 = (uint32_t)lane * 4;
   const uint32_t smem_base = lds_addr_of(smem);
   // piece `pc` (0..VPS-1) of stage `stage` into ring buffer `buf`
@@ -165,8 +150,8 @@ __global__ __launch_bounds__(256, 1) void qtopk2_kernel(QTk2Args a) {
 
   // ---- read geometry: per-lane offsets inside a ring buffer (qde_kernel's image); the buffer offsets rotate ----------
   const lds_u8* lbase = (const lds_u8*)smem;
-  const int oa0 = C::RG_BYTES * (r >> 3) + 64 * (r & 7) + 16 * ((0 + h) ^ ((r >> 2) & 3));
-  const int oa1 = C::RG_BYTES * (r >> 3) + 64 * (r & 7) + 16 * ((2 + h) ^ ((r >> 2) & 3));
+  const ImgRead o = img_read_offsets<C>(lane);
+  const int oa0 = o.oa0, oa1 = o.oa1;
   const int os = C::STAGE_BYTES + wave * 256 + 16 * h;
   const int ow = C::STAGE_BYTES + T::STRIPS + wave * 512 + r * 8;      // + 256 for the second user group
   const lds_u8 *pA0, *pA1, *pS, *pW;       // current buffer

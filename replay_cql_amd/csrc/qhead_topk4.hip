@@ -20,7 +20,7 @@
 //    stage's seen (user, item) cells (tk4_lists_kernel, at the end of this file), which spares the 1.6 GB bitmap.
 #include <stdlib.h>
 #include <type_traits>
-#include "qhead_de_common.h"
+#include "qhead_image.h"
 
 #define TK4_G 4          // user groups per wave
 #define TK4_Q 12         // queue entries per lane and group (16 queues of 6 KiB per block beside the 61 KiB ring)
@@ -110,13 +110,10 @@ __global__ __launch_bounds__(256, 1) void qtopk4_kernel(QTk2Args a) {
     for (int s = 0; s < KS; ++s) rfa[g][s] = *reinterpret_cast<const u32x4*>(a.H_b + row * D + 16 * s + 8 * h);   // only ever an
                                                                                 // "a" operand: hipcc keeps it in AccVGPRs
   }
-  __builtin_amdgcn_s_waitcnt(0x0F70);       // (see qde2_kernel::load_owner)
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  owner_fence();
 
   // ---- staging ---------------------------------------------------------------------------------------------------------
-  __amdgpu_buffer_rsrc_t rs_e = __builtin_amdgcn_make_buffer_rsrc((void*)a.E_b, 0, (int)(a.n_cand * C::ROWB), 0x00020000);
-  __amdgpu_buffer_rsrc_t rs_b = __builtin_amdgcn_make_buffer_rsrc((void*)a.bias, 0, (int)(a.n_cand * 4), 0x00020000);
+  __amdgpu_buffer_rsrc_t rs_e = make_rsrc(a.E_b, a.n_cand * C::ROWB), rs_b = make_rsrc(a.bias, a.n_cand * 4);
   // seen words of this wave's 128 users = two consecutive 64-user blocks of the bitmap ([block][stage][64 users][2 words]):
   // lanes 0..31 fetch the first block's 512 B of a stage, lanes 32..63 the second block's.  A block past n_users does not
   // exist in the bitmap: its lanes get an offset past num_records (they read 0).  No filter = an empty buffer.
@@ -137,13 +134,7 @@ __global__ __launch_bounds__(256, 1) void qtopk4_kernel(QTk2Args a) {
                                                                   0x00020000);
   const uint32_t voff_w = LISTS ? (uint32_t)lane * 4u
                                 : (uint32_t)((lane >> 5) * (uint32_t)(nst_all * 512) + (lane & 31) * 16);
-  uint32_t voff;
-  {
-    const int sub = lane >> 5, r7 = (lane >> 2) & 7, slot = lane & 3;
-    const int rg0 = wave / C::PPG, hc = wave % C::PPG;
-    const int q2 = (r7 >> 2) | ((rg0 & 1) << 1);
-    voff = (uint32_t)((rg0 * 8 + r7) * C::ROWB + (8 * hc + 4 * sub + (slot ^ q2)) * 16);
-  }
+  const uint32_t voff = img_stage_voff<C>(lane, wave, 0);
   const uint32_t voff4 = (uint32_t)lane * 4;
   const uint32_t smem_base = lds_addr_of(smem);
   // piece pc of stage `stage` into ring buffer `buf`: 0..3 rows, 4 seen words, 5 the bias strip (one wave per stage)
@@ -161,8 +152,8 @@ __global__ __launch_bounds__(256, 1) void qtopk4_kernel(QTk2Args a) {
 
   // ---- read geometry ------------------------------------------------------------------------------------------------------
   const lds_u8* lbase = (const lds_u8*)smem;
-  const int oa0 = C::RG_BYTES * (r >> 3) + 64 * (r & 7) + 16 * ((0 + h) ^ ((r >> 2) & 3));
-  const int oa1 = C::RG_BYTES * (r >> 3) + 64 * (r & 7) + 16 * ((2 + h) ^ ((r >> 2) & 3));
+  const ImgRead o = img_read_offsets<C>(lane);
+  const int oa0 = o.oa0, oa1 = o.oa1;
   const int os = C::STAGE_BYTES + 16 * h;
   const int ow = C::STAGE_BYTES + T::STRIP + wave * 1024 + r * 8;      // + 256 g for user group g
   const lds_u8 *pA0, *pA1, *pS, *pW;
