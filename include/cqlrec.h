@@ -261,6 +261,33 @@ int cqlrec_item_knn(const uint16_t* E_b, const float* norms, int64_t n_rows, int
                     int64_t ws_bytes, int32_t* out_idx, float* out_val, int32_t* out_cnt, cqlrec_stream stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * a12  Ranking of per-row candidate lists = predict_pairs(..., k=) (replay/models/base_rec.py:725-782; the use
+ * sample_top_k_recs' docstring describes, replay/utils.py:717-727; TwoStagesScenario's candidate frames,
+ * two_stages_scenario.py:478-483): the score of every (row, item) pair of a ragged CSR and, per selected row, the k
+ * best admissible pairs.  Nothing of size nnz x d is built: a wave keeps its row's state vector in registers.
+ *   H_b        [n_sel x d] bf16 state vectors;  rows [n_sel] the CSR row of H_b[i] (NULL: row i), distinct
+ *   pair_off / pair_items   CSR of candidates: items of a row ascending, duplicates allowed, values in [0, n_items)
+ *   seen_off / seen_items   CSR over the SAME rows, items ascending (NULL, NULL: no filter)
+ * Score of a pair: bit for bit what cqlrec_gather_dot gives for (h, item) -- per lane eight sequential fmaf, the
+ * butterfly sum over d/8 lanes, + b[item].  out_score (optional, [nnz], CSR order) receives the score of every pair of
+ * a selected row, seen or not; pairs of rows that are not selected are not touched.
+ * Selection (k > 0), per selected row: the k best pairs by (score desc, item id asc) -- the tie rule of
+ * cqlrec_score_topk -- among those whose item is not in the row's seen list.  A candidate listed twice is two entries
+ * (adjacent in the output).  out_idx / out_val [n_sel x k] (padding -1 / -inf), out_cnt [n_sel] = valid entries.
+ * Scores are assumed finite.  k == 0: scores only (out_idx, out_val, out_cnt NULL, out_score required).
+ * Lists of any length in one call: a row longer than max(4096, (summed length of such rows) / 8192) is cut into
+ * pieces on the device and merged there; the workspace depends on k alone
+ * (8192 * 8 k bytes + 192 KiB).  n_sel <= 2^26 per call (one 64-thread block per row).  Integer atomics hand out piece slots, no
+ * float atomics: the same call gives the same bits twice.
+ * --------------------------------------------------------------------------------------------------------- */
+#define CQLREC_PAIRS_MAX_K 512
+int64_t cqlrec_pairs_topk_ws_bytes(int64_t n_sel, int64_t nnz, int32_t d, int32_t k);   /* [host]; 0: bad arguments */
+int cqlrec_pairs_topk(const uint16_t* H_b, const uint16_t* E_b, const float* b, int64_t n_items, int32_t d,
+                      const int64_t* pair_off, const int32_t* pair_items, const int32_t* rows, int64_t n_sel,
+                      const int64_t* seen_off, const int32_t* seen_items, int32_t k, void* ws, int64_t ws_bytes,
+                      float* out_score, int32_t* out_idx, float* out_val, int32_t* out_cnt, cqlrec_stream stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * a8  Whole training step = TorchRecommender._run_train_step (replay/models/base_torch_rec.py:32-39) without
  * the per-step host sync.  The step is split in two so that a data-parallel caller can all-reduce ctx.grads
  * (RCCL) between them; losses[] receives one float per step.

@@ -24,6 +24,7 @@ ABI_VERSION = 2
 TOPK_ALL, TOPK_SEEN, TOPK_SCORE, TOPK_SEEN_BESIDE = 0, 1, 2, 3
 SIM_DOT, SIM_COSINE, SIM_EUCLID = 0, 1, 2
 ITEM_KNN_MAX_K = 512
+PAIRS_MAX_K = 512
 QHEAD_LSE = 1
 QHEAD_ARGMAX = 2
 EVAL_EXTRAS = ("RocAuc", "Unexpectedness", "Surprisal", "NCISPrecision")
@@ -102,6 +103,8 @@ SIGNATURES = {
     "cqlrec_item_norms": (i32, [vp, i64, i32, vp, vp]),
     "cqlrec_item_knn_ws_bytes": (i64, [i64, i64, i32, i32]),
     "cqlrec_item_knn": (i32, [vp, vp, i64, i32, vp, i64, vp, i64, i32, i32, vp, i64, vp, vp, vp, vp]),
+    "cqlrec_pairs_topk_ws_bytes": (i64, [i64, i64, i32, i32]),
+    "cqlrec_pairs_topk": (i32, [vp, vp, vp, i64, i32, vp, vp, vp, i64, vp, vp, i32, vp, i64, vp, vp, vp, vp, vp]),
     "cqlrec_train_ws_bytes": (i64, [i32, i64, i32, i32]),
     "cqlrec_train_step_fwd_bwd": (i32, [C.POINTER(TrainCtx), u64, vp, vp]),
     "cqlrec_train_step_update": (i32, [C.POINTER(TrainCtx), u64, vp]),

@@ -663,6 +663,55 @@ class CQLCore:
                                            _ptr(out), _stream()), "gather_dot")
         return out
 
+    PAIRS_MAX_K = N.PAIRS_MAX_K
+
+    def pairs_topk(self, hb: torch.Tensor, pair_off: torch.Tensor, pair_items: torch.Tensor,
+                   rows: Optional[torch.Tensor], k: int, seen: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
+                   want_scores: bool = False):
+        """Rank per-row candidate lists (a12): hb [n, d] bf16 state vectors, (pair_off int64, pair_items int32) a CSR of
+        candidates (ascending per row, duplicates allowed, ids in [0, n_items)), rows int32 [n] the CSR row of hb[i]
+        (None: row i; distinct), seen = (offsets int64, ascending item ids int32) over the same rows or None.
+        Returns (idx int32 [n, k], val float32 [n, k], cnt int32 [n]) -- the k best unseen pairs per row by (score desc,
+        item id asc), padding -1 / -inf -- and, with want_scores, a float32 [nnz] tensor with the score of every pair in
+        CSR order (NaN for pairs of rows that were not selected).  k = 0: scores only (idx, val have no columns).
+        Scores are cqlrec_gather_dot's, bit for bit; no [nnz, d] intermediate exists."""
+        h, lay = self.hyper, self.layout
+        k = int(k)
+        if k < 0 or k > N.PAIRS_MAX_K:
+            raise ValueError(f"k = {k} is outside the candidate-list kernel's range 0..{N.PAIRS_MAX_K}")
+        n, nnz = hb.shape[0], pair_items.numel()
+        if hb.dtype != torch.bfloat16 or hb.dim() != 2 or hb.shape[1] != h.d or not hb.is_contiguous():
+            raise ValueError(f"hb must be a contiguous bf16 [n, {h.d}] tensor")
+        dev_t = lambda x, dt: x.to(device=self.device, dtype=dt).contiguous()       # noqa: E731
+        pair_off, pair_items = dev_t(pair_off, torch.int64), dev_t(pair_items, torch.int32)
+        rows = None if rows is None else dev_t(rows, torch.int32)
+        if rows is not None and rows.numel() != n:
+            raise ValueError("rows must hold one CSR row per state vector")
+        if rows is None and pair_off.numel() < n + 1:
+            raise ValueError("pair_off is shorter than the state vectors it is indexed by")
+        if seen is not None:
+            seen = (dev_t(seen[0], torch.int64), dev_t(seen[1], torch.int32))
+            if seen[0].numel() != pair_off.numel():
+                raise ValueError("the seen CSR must be over the same rows as the pairs CSR")
+        want_scores = want_scores or k == 0
+        out_idx = torch.empty((n, k), dtype=torch.int32, device=self.device)
+        out_val = torch.empty((n, k), dtype=torch.float32, device=self.device)
+        out_cnt = torch.zeros((n,), dtype=torch.int32, device=self.device)
+        scores = torch.full((nnz,), float("nan"), dtype=torch.float32, device=self.device) if want_scores else None
+        if n > 0 and nnz > 0:
+            ws_bytes = int(self.lib.cqlrec_pairs_topk_ws_bytes(n, nnz, h.d, k))
+            ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=self.device)
+            N.check(self.lib.cqlrec_pairs_topk(
+                _ptr(hb), self.theta_b.data_ptr() + 2 * lay.off_E_out, self.theta.data_ptr() + 4 * lay.off_b_out,
+                self.n_items, h.d, _ptr(pair_off), _ptr(pair_items), _ptr(rows), n,
+                None if seen is None else _ptr(seen[0]), None if seen is None else _ptr(seen[1]), k, _ptr(ws), ws_bytes,
+                _ptr(scores), _ptr(out_idx) if k else None, _ptr(out_val) if k else None, _ptr(out_cnt) if k else None,
+                _stream()), "pairs_topk")
+        elif k:
+            out_idx.fill_(-1)
+            out_val.fill_(float("-inf"))
+        return (out_idx, out_val, out_cnt, scores) if want_scores else (out_idx, out_val, out_cnt)
+
     ITEM_KNN_METRICS = {"dot_product": N.SIM_DOT, "cosine_similarity": N.SIM_COSINE,
                         "euclidean_distance_sim": N.SIM_EUCLID}
     ITEM_KNN_MAX_K = N.ITEM_KNN_MAX_K

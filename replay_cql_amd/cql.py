@@ -18,7 +18,7 @@ import torch
 
 from . import data as D
 from .core import CQLCore, CQLHyper
-from .recommender_api import PandasRecommender, REC_COLUMNS
+from .recommender_api import PandasRecommender, REC_COLUMNS, _is_spark, to_pandas
 
 
 class CQL(PandasRecommender):
@@ -301,6 +301,169 @@ class CQL(PandasRecommender):
             pu, pi, rel = pu[keep], pi[keep], rel[keep]
         return pd.DataFrame({"user_idx": pu.cpu().numpy().astype(np.int32), "item_idx": pi.cpu().numpy().astype(np.int32),
                              "relevance": rel.cpu().numpy().astype(np.float64)})
+
+    # ------------------------------------------------------------------------------------------- candidate lists
+    def _pairs_device(self, pcols, lcols, k: int, filter_seen_items: bool, drop_history_less: Optional[bool] = None):
+        """Candidate lists on the device.  pcols / lcols: device columns of the pairs / the log (cold rows already
+        dropped); k = 0: scores only.  drop_history_less: users without rows in the log get no rows (default: unless
+        predict_cold_users).  Returns None when nothing is left to score, else a dict: users int32 [n] (ascending;
+        the users that get rows), idx / val / cnt (the [n, k] block of cqlrec_pairs_topk), and for k = 0 the whole
+        CSR: off int64, items int32, scores float32 [nnz] (NaN for users that get no rows), keep bool [nnz] (False for
+        pairs of such users and, under filter_seen_items, for seen pairs)."""
+        core = self._require_fit()
+        dev = core.device
+        if pcols is None or pcols["user_idx"].numel() == 0:
+            return None
+        pu, pi = pcols["user_idx"], pcols["item_idx"]
+        lim = torch.stack([pu.min(), pi.min(), pi.max()]).cpu().tolist()              # one small sync
+        if lim[0] < 0:
+            raise ValueError("user_idx / item_idx must be non-negative dense indices")
+        if lim[1] < 0 or lim[2] >= core.n_items:
+            raise ValueError("pairs hold an item_idx outside the fitted catalogue; filter cold items first")
+        uniq = torch.unique(pu.to(torch.int64))
+        offsets, items, seen = self._device_states(lcols, uniq, filter_seen_items)
+        n_rows = offsets.numel() - 1
+        p_off, p_items, _ = D.build_csr_device(pu, pi, None, None, n_rows, device=dev, check=False)   # (user, item asc)
+        if drop_history_less is None:
+            drop_history_less = not self.predict_cold_users
+        if drop_history_less:                 # "no history -> no rows", as _predict_pairs and _predict_device
+            uniq = uniq[(offsets[uniq + 1] - offsets[uniq]) > 0]
+            if uniq.numel() == 0:
+                return None
+        users32 = uniq.to(torch.int32)
+        hb = core.encode(offsets, items, users32)
+        out = core.pairs_topk(hb, p_off, p_items, users32, k, seen=None if seen is None else (offsets, seen),
+                              want_scores=(k == 0))
+        res = {"users": users32, "idx": out[0], "val": out[1], "cnt": out[2]}
+        if k == 0:
+            row = torch.repeat_interleave(torch.arange(n_rows, device=dev), p_off[1:] - p_off[:-1])
+            sel = torch.zeros(n_rows, dtype=torch.bool, device=dev)
+            sel[uniq] = True
+            keep = sel[row]
+            if seen is not None:             # the anti-join with the log on (user, item) keys
+                s_row = torch.repeat_interleave(torch.arange(n_rows, device=dev), offsets[1:] - offsets[:-1])
+                s_key = s_row * core.n_items + seen[: s_row.numel()].to(torch.int64)
+                keep &= ~torch.isin(row * core.n_items + p_items.to(torch.int64), s_key)
+            res.update(off=p_off, items=p_items, scores=out[3], keep=keep, row=row)
+        return res
+
+    def _cold_filtered_cols(self, cols):
+        """Drop the rows of device columns whose user or item the model has not seen at fit
+        (_filter_cold_for_predict, base_rec.py:560-603)."""
+        if cols is None or cols["user_idx"].numel() == 0:
+            return None
+        if self.can_predict_cold_users and self.can_predict_cold_items:
+            return cols
+        dev = cols["user_idx"].device
+        keep = torch.ones(cols["user_idx"].numel(), dtype=torch.bool, device=dev)
+        if not self.can_predict_cold_users:
+            fit_u = torch.as_tensor(self.fit_users["user_idx"].to_numpy().astype(np.int64)).to(dev)
+            keep &= torch.isin(cols["user_idx"].to(torch.int64), fit_u)
+        if not self.can_predict_cold_items:
+            fit_i = torch.as_tensor(self.fit_items["item_idx"].to_numpy().astype(np.int64)).to(dev)
+            keep &= torch.isin(cols["item_idx"].to(torch.int64), fit_i)
+        return {n: (None if c is None else c[keep]) for n, c in cols.items()}
+
+    def _pairs_to_arrow(self, res, k: int):
+        from . import arrow_io as A
+        dev = self._require_fit().device
+        if res is None:
+            z = torch.zeros((0, 1), device=dev)
+            return A.recs_to_arrow(z[:, 0].to(torch.int32), z.to(torch.int32), z.to(torch.float32), z[:, 0].to(torch.int32))
+        if k:
+            return A.recs_to_arrow(res["users"], res["idx"], res["val"], res["cnt"])
+        keep = res["keep"]
+        return A.recs_to_arrow(res["row"][keep].to(torch.int32), res["items"][keep][:, None],
+                               res["scores"][keep][:, None], torch.ones(int(keep.sum()), dtype=torch.int32, device=dev))
+
+    def predict_pairs_arrow(self, pairs, log, k: Optional[int] = None, filter_seen_items: bool = False):
+        """predict_pairs() for Arrow callers: `pairs` = record batches with user_idx, item_idx (a candidate list per
+        user; an item may be listed more than once and is then scored and returned as often), `log` as predict_arrow
+        takes it.  Returns ONE pyarrow.RecordBatch with REC_SCHEMA: with k, at most k rows per user ordered (user_idx,
+        relevance desc, item_idx asc) -- `_predict_pairs_wrap` + get_top_k (base_rec.py:725-782) -- selected on the device
+        (k <= 512); without k, every pair ordered (user_idx, item_idx).  filter_seen_items drops the pairs that occur in
+        `log`.  Cold users / items are dropped from pairs and log as `_filter_cold_for_predict` does; users without
+        history yield no rows unless predict_cold_users.  Relevance holds the bits `_predict_pairs` gives."""
+        from . import arrow_io as A
+        core = self._require_fit()
+        if log is None:
+            raise ValueError("log is not provided, but it is required for prediction")
+        k = int(k) if k else 0
+        if k < 0 or k > core.PAIRS_MAX_K:
+            raise ValueError(f"k = {k}: the device ranking of candidate lists takes 1..{core.PAIRS_MAX_K} (or None)")
+        dev = core.device
+        pcols = self._cold_filtered_cols(A.columns_to_device(pairs, dev, ("user_idx", "item_idx")))
+        lcols = self._cold_filtered_cols(A.columns_to_device(log, dev, ("user_idx", "item_idx", "timestamp")))
+        return self._pairs_to_arrow(self._pairs_device(pcols, lcols, k, filter_seen_items), k)
+
+    def _predict_pairs_wrap(self, pairs, log=None, user_features=None, item_features=None,
+                            recs_file_path: Optional[str] = None, k: Optional[int] = None):
+        """With 0 < k <= 512 the per-user top-k of the wrapper (base_rec.py:725-782) is taken on the device: the frame is
+        the one `_predict_pairs` + get_top_k give -- rows, order, dtypes, relevance bits -- without the pairs x d state
+        block and without the host sort.  Everything else goes the wrapper's way."""
+        core = self._require_fit()
+        if not k or k < 0 or k > core.PAIRS_MAX_K or pairs is None or len(to_pandas(pairs)) == 0:
+            return super()._predict_pairs_wrap(pairs, log, user_features, item_features, recs_file_path, k)
+        spark_out = _is_spark(pairs)
+        log, pairs = to_pandas(log), to_pandas(pairs)
+        if sorted(pairs.columns) != ["item_idx", "user_idx"]:
+            raise ValueError("pairs must be a dataframe with columns strictly [user_idx, item_idx]")
+        pairs, log = self._filter_cold_for_predict(pairs, log, "user")
+        pairs, log = self._filter_cold_for_predict(pairs, log, "item")
+        if log is None:
+            raise ValueError("log is not provided, but it is required for prediction")   # as _predict_pairs
+        dev = core.device
+        pcols = None
+        if len(pairs):
+            pcols = {"user_idx": D._dev_col(pairs["user_idx"].to_numpy(), torch.int32, dev),     # pylint: disable=protected-access
+                     "item_idx": D._dev_col(pairs["item_idx"].to_numpy(), torch.int32, dev)}     # pylint: disable=protected-access
+        res = self._pairs_device(pcols, self._pdf_cols(log, dev), int(k), False)
+        pred = self._pairs_to_arrow(res, int(k)).to_pandas()
+        return self._deliver(pred[REC_COLUMNS].reset_index(drop=True), recs_file_path, spark_out)
+
+    def candidates_block(self, log: pd.DataFrame, users, pairs: pd.DataFrame, k: int, filter_seen_items: bool = False):
+        """The ranked candidate lists of `users` (ids; taken sorted and distinct) as a device block: int32
+        [len(users), k], row i = the k best DISTINCT candidates of the i-th user from `pairs` (user_idx, item_idx), best
+        first, padded with -1.  A candidate listed twice counts once (the metrics take unique items per row); users
+        without candidates, cold users and users without history in `log` get an all -1 row; cold items are dropped
+        from the lists.  Returns (users int64 numpy, block)."""
+        core = self._require_fit()
+        dev = core.device
+        k = int(k)
+        if k <= 0 or k > core.PAIRS_MAX_K:
+            raise ValueError(f"k = {k} is outside 1..{core.PAIRS_MAX_K}")
+        _, log = self._filter_cold(log, "user")
+        _, log = self._filter_cold(log, "item")
+        users = np.unique(np.asarray(users).astype(np.int64))
+        pairs = pairs[["user_idx", "item_idx"]]
+        pairs = pairs[pairs["user_idx"].isin(users)].drop_duplicates()
+        _, pairs = self._filter_cold(pairs, "user")
+        _, pairs = self._filter_cold(pairs, "item")
+        rec = torch.full((len(users), k), -1, dtype=torch.int32, device=dev)
+        if len(pairs):
+            pcols = {"user_idx": D._dev_col(pairs["user_idx"].to_numpy(), torch.int32, dev),     # pylint: disable=protected-access
+                     "item_idx": D._dev_col(pairs["item_idx"].to_numpy(), torch.int32, dev)}     # pylint: disable=protected-access
+            res = self._pairs_device(pcols, self._pdf_cols(log, dev), k, filter_seen_items, drop_history_less=True)
+            if res is not None:
+                rows = torch.searchsorted(torch.as_tensor(users).to(dev), res["users"].to(torch.int64))
+                rec[rows] = res["idx"]
+        return users, rec
+
+    def evaluate_candidates(self, log: pd.DataFrame, ground_truth: pd.DataFrame, pairs: pd.DataFrame, ks=(10,),
+                            filter_seen_items: bool = False):
+        """Quality of ranking each user's OWN candidate list (`pairs`: user_idx, item_idx -- e.g. the held-out item among
+        sampled negatives) for the users of `ground_truth`: the top-max(ks) of every list (candidates_block) goes from
+        cqlrec_pairs_topk to metrics.evaluate_topk without leaving the device.  Returns {metric: {k: value}} as
+        evaluate() does.  Users without candidates, cold users and users without history count with empty predictions;
+        cold items are dropped from the lists; a candidate listed twice counts once."""
+        from .metrics import evaluate_topk
+        dev = self._require_fit().device
+        gt = ground_truth[["user_idx", "item_idx"]].drop_duplicates()
+        gt_users, rec = self.candidates_block(log, gt["user_idx"].to_numpy(), pairs, int(max(ks)), filter_seen_items)
+        rows_h = np.searchsorted(gt_users, gt["user_idx"].to_numpy().astype(np.int64))
+        g_off, g_items, _ = D.build_csr_device(rows_h, gt["item_idx"].to_numpy(), None, None, len(gt_users), device=dev)
+        g_items = torch.cat([g_items, torch.zeros(1, dtype=torch.int32, device=dev)])
+        return evaluate_topk(rec, g_off, g_items, ks)
 
     def evaluate(self, log: pd.DataFrame, ground_truth: pd.DataFrame, ks=(10,), filter_seen_items: bool = True,
                  extra=()):
