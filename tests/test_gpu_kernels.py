@@ -61,28 +61,27 @@ def test_sampler_empty_users(lib):
 
 
 # ------------------------------------------------------------------------------------------------ gather
-@pytest.mark.parametrize("d", [64, 128, 256])
-@pytest.mark.parametrize("dyadic", [True, False])
-def test_gather_pool_fwd(lib, d, dyadic):
-    Nn, L = 301, 7
-    off, items, _ = small_log(U=80, N=Nn, seed=2, mean_len=10, max_len=30)
+def _gather_pool_fwd_case(lib, d, dyadic, L, delta, mean_len, max_len):
+    """ends + delta is the state's end; the oracle gets the shifted ends"""
+    Nn = 301
+    off, items, _ = small_log(U=80, N=Nn, seed=2, mean_len=mean_len, max_len=max_len)
     m = O.OracleModel.create(Nn, d, seed=5, dyadic=dyadic)
     E_in_b = O.bf16_round(m.layout.view(m.theta, "E_in"))
     rng = np.random.default_rng(0)
     users = rng.integers(0, 80, 333).astype(np.int32)
     cnt = (off[users.astype(np.int64) + 1] - off[users]).astype(np.int64)
-    ends = (rng.integers(0, 10**6, 333) % (cnt + 1)).astype(np.int32)  # 0..count (0 -> empty window)
+    ends = (rng.integers(0, 10**6, 333) % (cnt + 1 - delta)).astype(np.int32)  # ends + delta in 0..count (0 -> empty window)
     ends[:5] = 0
-    h0_ref, len_ref = O.gather_pool(E_in_b, off, items, users, ends, L)
+    h0_ref, len_ref = O.gather_pool(E_in_b, off, items, users, ends + delta, L)
     h0 = torch.empty((333, d), dtype=torch.float32, device=DEV)
     h0b = torch.empty((333, d), dtype=torch.bfloat16, device=DEV)
     lens = torch.empty(333, dtype=torch.int32, device=DEV)
     N.check(lib.cqlrec_gather_pool_fwd(ptr(bf16_dev(E_in_b)), ptr(dev(off)), ptr(dev(items)), ptr(dev(users)),
-                                       ptr(dev(ends)), 0, 333, L, d, ptr(h0), ptr(h0b), ptr(lens), stream()))
+                                       ptr(dev(ends)), delta, 333, L, d, ptr(h0), ptr(h0b), ptr(lens), stream()))
     sync()
     assert np.array_equal(lens.cpu().numpy(), len_ref)
     if dyadic:
-        # sums of <= 7 multiples of 2^-6 are exact; the division is one correctly rounded fp32 op on both sides
+        # sums of <= 70 multiples of 2^-6 are exact; the division is one correctly rounded fp32 op on both sides
         assert np.array_equal(h0.cpu().numpy(), h0_ref)
     else:
         np.testing.assert_allclose(h0.cpu().numpy(), h0_ref, rtol=1e-5, atol=1e-6)
@@ -94,6 +93,23 @@ def test_gather_pool_fwd(lib, d, dyadic):
     sync()
     ref_p, _ = O.gather_pool(E_in_b, off, items, users, cnt, L)
     np.testing.assert_allclose(h0p.cpu().numpy(), ref_p, rtol=1e-5, atol=1e-6)
+    return len_ref
+
+
+@pytest.mark.parametrize("d", [64, 128, 256])
+@pytest.mark.parametrize("dyadic", [True, False])
+def test_gather_pool_fwd(lib, d, dyadic):
+    _gather_pool_fwd_case(lib, d, dyadic, 7, 0, 10, 30)
+
+
+@pytest.mark.parametrize("d", [64, 128, 256])
+@pytest.mark.parametrize("dyadic", [True, False])
+@pytest.mark.parametrize("L,delta", [(70, 0), (50, 1), (7, 1)])
+def test_gather_pool_fwd_long_and_shifted_windows(lib, d, dyadic, L, delta):
+    """the same comparison for a window longer than a wave (L = 70: more rows than one round of wave-instructions holds)
+    and for next-state windows (end_delta = 1), against the oracle on the shifted ends; dyadic data bit-exact"""
+    lens = _gather_pool_fwd_case(lib, d, dyadic, L, delta, 70, 217)
+    assert lens.max() == L and lens.min() == delta and np.unique(lens).size > 5       # full, shortest and partial windows
 
 
 @pytest.mark.parametrize("d", [64, 128, 256])

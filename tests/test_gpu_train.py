@@ -27,7 +27,7 @@ def _make(U, Nn, d, B, L, dyadic=False, seed=3, alpha=1.0):
 
 
 @pytest.mark.parametrize("U,Nn,d,B,L", [(64, 257, 64, 64, 5), (300, 1000, 128, 256, 8), (200, 4099, 128, 96, 50),
-                                        (100, 513, 256, 128, 10)])
+                                        (100, 513, 256, 128, 10), (64, 40, 128, 256, 5)])
 def test_step_intermediates_and_grads(U, Nn, d, B, L):
     m, core, (off, items, rew) = _make(U, Nn, d, B, L)
     lay = m.layout
