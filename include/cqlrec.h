@@ -505,6 +505,89 @@ int cqlrec_eval_item_hist(const int32_t* rec_idx, int64_t n_users, int32_t kmax,
                           cqlrec_stream stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * f5  Train/test splitters on the device: the window passes of replay/splitters/{user_log_splitter,log_splitter}.py
+ * (row_number() over a user's history, the order statistics behind DateSplitter / NewUsersSplitter, the distinct + join
+ * passes of base_splitter.py:73-107) as a ranking inside each user, a row predicate and a stable compaction.  Integer
+ * work throughout; the only atomics are integer ones (atomicMin / atomicAdd / atomicOr), so the same input gives the
+ * same bytes.  user_idx / item_idx are dense non-negative ids below n_users / n_items: the CALLER range-checks them,
+ * the kernels index count arrays and bitmaps with them.  n_rows < 2^31; n_rows == 0 is legal where stated.
+ *
+ * Tie-break.  The reference's row_number().over(partitionBy(user).orderBy(ts.desc())) leaves rows of equal timestamp
+ * to Spark.  Here: rank = 1-based row number inside the user ordered by (key DESCENDING, input row index DESCENDING)
+ * -- of equal timestamps the later input row is the "more recent" one.
+ *
+ * Random draws (Spark's rand(seed) / randomSplit cannot be reproduced): for element x (an input row index or a user
+ * id) h(x) = mix64(mix64(seed) ^ x), mix64 = the splitmix64 finaliser of the transition sampler above (add the golden
+ * constant first); u(x) = ((h >> 11) + 0.5) * 2^-53 in double.  A shuffled ranking uses h(row), compared as an
+ * unsigned number, in place of the key.
+ * --------------------------------------------------------------------------------------------------------- */
+/* rank [n_rows] (see above), count [n_users] rows per user, *n_present (may be NULL) = users with count > 0.
+ * key: any int64 whose signed order is the order wanted (data.timestamp_key); shuffle != 0: key is ignored (may be
+ * NULL) and h(row) under `seed` ranks the rows.  Two stable LSD radix sorts over a row permutation (key, then user)
+ * and one pass that turns sorted position into rank, as cqlrec_build_csr does it.  n_rows == 0: count = 0. */
+int64_t cqlrec_split_rank_ws_bytes(int64_t n_rows, int64_t n_users);
+int cqlrec_split_rank(const int32_t* user_idx, const int64_t* key, int64_t n_rows, int64_t n_users, int32_t shuffle,
+                      uint64_t seed, void* ws, int64_t ws_bytes, int32_t* rank, int32_t* count, int64_t* n_present,
+                      cqlrec_stream stream);
+
+/* *out = the m-th smallest (1-based, 1 <= m <= n) of key[n]: DateSplitter's float test_start (log_splitter.py:71-80). */
+int64_t cqlrec_split_kth_key_ws_bytes(int64_t n);
+int cqlrec_split_kth_key(const int64_t* key, int64_t n, int64_t m, void* ws, int64_t ws_bytes, int64_t* out,
+                         cqlrec_stream stream);
+
+/* NewUsersSplitter (log_splitter.py:238-264): user_start [n_users] = min key of the user's rows (INT64_MAX for a user
+ * without rows), *threshold = the largest start key dt such that the number of users starting at or after dt is
+ * >= total_users * test_size (total_users = users with a row; the comparison in double).  n_rows >= 1. */
+int64_t cqlrec_split_new_users_ws_bytes(int64_t n_users);
+int cqlrec_split_new_users(const int32_t* user_idx, const int64_t* key, int64_t n_rows, int64_t n_users,
+                           double test_size, void* ws, int64_t ws_bytes, int64_t* user_start, int64_t* threshold,
+                           cqlrec_stream stream);
+
+/* user_test_size (user_log_splitter.py:142-180): test_user [n_users] = 1 for the n_pick users with the smallest h(user)
+ * among those with count > 0, ties by user id ascending; 0 for the others.  0 <= n_pick. */
+int64_t cqlrec_split_pick_users_ws_bytes(int64_t n_users);
+int cqlrec_split_pick_users(const int32_t* count, int64_t n_users, uint64_t seed, int64_t n_pick, void* ws,
+                            int64_t ws_bytes, uint8_t* test_user, cqlrec_stream stream);
+
+/* Per-row train / test bytes.  Unless stated, is_train = !is_test.  test_user (NULL: every user) gates the two
+ * per-user rules.
+ *   QUANTITY     test_user[u] && rank <= n                                       (_split_quantity)
+ *   PROPORTION   test_user[u] && (double)rank / (double)count[u] <= frac         (_split_proportion's `_frac`)
+ *   DATE         key >= *threshold                                               (DateSplitter)
+ *   RANDOM_ROW   u(row) >= frac     (frac = 1 - test_size, computed by the caller) (RandomSplitter)
+ *   RANDOM_USER  u(user) >= frac                                                 (ColdUserRandomSplitter)
+ *   NEW_USERS    is_train = key < *threshold; is_test = user_start[u] >= *threshold: a row may be in neither
+ *   FOLD         rank % n == fold, n folds                                       (k_folds)
+ * Arrays a rule does not read may be NULL. */
+#define CQLREC_SPLIT_QUANTITY 0
+#define CQLREC_SPLIT_PROPORTION 1
+#define CQLREC_SPLIT_DATE 2
+#define CQLREC_SPLIT_RANDOM_ROW 3
+#define CQLREC_SPLIT_RANDOM_USER 4
+#define CQLREC_SPLIT_NEW_USERS 5
+#define CQLREC_SPLIT_FOLD 6
+int cqlrec_split_classify(int32_t rule, const int32_t* user_idx, const int64_t* key, const int32_t* rank,
+                          const int32_t* count, const uint8_t* test_user, const int64_t* user_start,
+                          const int64_t* threshold, int64_t n_rows, int64_t n, int64_t fold, double frac, uint64_t seed,
+                          uint8_t* is_train, uint8_t* is_test, cqlrec_stream stream);
+
+/* _drop_cold_items_and_users + _filter_zero_relevance (base_splitter.py:59-107), in place on is_test: presence bitmaps
+ * of the users and items among the train rows (atomicOr on 32-bit words); a test row stays if its item is present
+ * (drop_cold_items), its user is present (drop_cold_users) and relevance > 0.0 (drop_zero_rel).  item_idx / relevance
+ * may be NULL when their flag is 0. */
+int64_t cqlrec_split_filter_test_ws_bytes(int64_t n_users, int64_t n_items);
+int cqlrec_split_filter_test(const int32_t* user_idx, const int32_t* item_idx, const double* relevance,
+                             const uint8_t* is_train, int64_t n_rows, int64_t n_users, int64_t n_items,
+                             int32_t drop_cold_users, int32_t drop_cold_items, int32_t drop_zero_rel, void* ws,
+                             int64_t ws_bytes, uint8_t* is_test, cqlrec_stream stream);
+
+/* Stable compaction: train_rows / test_rows [n_rows each] receive the ascending indices of the rows whose byte is
+ * non-zero, counts[0] / counts[1] (device) how many.  n_rows == 0: counts = 0. */
+int64_t cqlrec_split_compact_ws_bytes(int64_t n_rows);
+int cqlrec_split_compact(const uint8_t* is_train, const uint8_t* is_test, int64_t n_rows, void* ws, int64_t ws_bytes,
+                         int64_t* train_rows, int64_t* test_rows, int64_t* counts, cqlrec_stream stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * Measurement hooks (bench.py): when enabled, every launcher brackets its kernel with a pair of HIP events on
  * the stream it launches on; cqlrec_prof_read synchronises those events and returns, per phase, the summed
  * kernel time in ms and the number of launches, then resets the pool.  Not capturable in a hipGraph; off by

@@ -139,6 +139,19 @@ SIGNATURES = {
     "cqlrec_eval_surprisal_weights": (i32, [vp, i64, i64, vp, vp]),
     "cqlrec_eval_coverage": (i32, [vp, vp, i64, i32, i64, C.POINTER(i32), i32, vp, vp, vp]),
     "cqlrec_eval_item_hist": (i32, [vp, i64, i32, i64, vp, vp]),
+    "cqlrec_split_rank_ws_bytes": (i64, [i64, i64]),
+    "cqlrec_split_rank": (i32, [vp, vp, i64, i64, i32, u64, vp, i64, vp, vp, vp, vp]),
+    "cqlrec_split_kth_key_ws_bytes": (i64, [i64]),
+    "cqlrec_split_kth_key": (i32, [vp, i64, i64, vp, i64, vp, vp]),
+    "cqlrec_split_new_users_ws_bytes": (i64, [i64]),
+    "cqlrec_split_new_users": (i32, [vp, vp, i64, i64, f64, vp, i64, vp, vp, vp]),
+    "cqlrec_split_pick_users_ws_bytes": (i64, [i64]),
+    "cqlrec_split_pick_users": (i32, [vp, i64, u64, i64, vp, i64, vp, vp]),
+    "cqlrec_split_classify": (i32, [i32, vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, f64, u64, vp, vp, vp]),
+    "cqlrec_split_filter_test_ws_bytes": (i64, [i64, i64]),
+    "cqlrec_split_filter_test": (i32, [vp, vp, vp, vp, i64, i64, i64, i32, i32, i32, vp, i64, vp, vp]),
+    "cqlrec_split_compact_ws_bytes": (i64, [i64]),
+    "cqlrec_split_compact": (i32, [vp, vp, i64, vp, i64, vp, vp, vp, vp]),
     "cqlrec_prof_enable": (i32, [i32]),
     "cqlrec_prof_select": (i32, [C.c_uint32]),
     "cqlrec_debug_marks_enable": (i32, [i32]),
