@@ -362,7 +362,12 @@ int cqlrec_train_step_update_range(const cqlrec_train_ctx* ctx /* [host] */, uin
  * encoder start while the item-side Adam is still running, and only the Q-head kernels wait for it.  Everything is
  * joined on `stream` before the call returns.  loss_out: n_steps device floats (may be NULL).
  * ctx->grads must be zero on entry and is zero again when a successful call has completed; during the call, and after
- * a failed one, its content is unspecified (steps that have a successor do not re-zero it). */
+ * a failed one, its content is unspecified (steps that have a successor do not re-zero it).
+ * Inside a call of more than one step, rows of E_in that no step reads are brought up to date late (their missed
+ * optimizer steps are replayed, bit for bit, when a step needs the row, and at the latest by the last step of the call):
+ * a successful call leaves theta, adam_m, adam_v, target and both shadows complete, but after an error return from the
+ * middle of a call the E_in rows of those six buffers may be several steps behind -- reload the model, as after losing
+ * the side streams in the middle of a call. */
 int cqlrec_train_steps(const cqlrec_train_ctx* ctx /* [host] */, uint64_t step0, int32_t n_steps, float* loss_out,
                        cqlrec_stream stream);
 

@@ -136,11 +136,24 @@ struct CqlAdamFix {
 int cql_adam_ema_fix(float* theta, float* grads, float* m, float* v, float* target, uint16_t* theta_b, uint16_t* target_b,
                      int64_t n, float step_size, float sqrt_bc2, float beta1, float beta2, float eps, float tau,
                      int32_t zero_grads, const CqlAdamFix* fix, hipStream_t stream);
-// Adam over a range of whole embedding rows of which only those marked in `row_map` (one byte per row, n_rows of them)
-// carry a gradient this step: the others are updated with g = 0 and their gradient elements are not read (misc.hip)
-int cql_adam_ema_rows(float* theta, float* grads, float* m, float* v, float* target, uint16_t* theta_b, uint16_t* target_b,
-                      int64_t n, float step_size, float sqrt_bc2, float beta1, float beta2, float eps, float tau,
-                      int32_t zero_grads, const uint8_t* row_map, int32_t d, int64_t n_rows, hipStream_t stream);
+// Adam over the whole embedding rows of E_in inside a cqlrec_train_steps call (misc.hip).  Only the rows
+// marked in `row_map` (one byte per row, n_rows of them) carry a gradient this step: the others take g = 0 and their gradient
+// elements are not read.  `age[r]` counts the steps row r is behind; a row is brought up to date -- the missed steps replayed in order with g = +0.0f, then this step's -- when it has a
+// gradient (`row_map`), when the next step's forward reads it (`read_next`; NULL: every row, the flush), or when its age
+// reaches the table's length.  `tab` holds the (step_size, sqrt_bc2) pairs of the last CQL_ADAM_DEFER_CAP steps, slot =
+// step % CQL_ADAM_DEFER_CAP, formed on the host in double like the dense launch's two scalars.
+#define CQL_ADAM_DEFER_CAP 64
+struct CqlAdamSteps {
+  float step_size[CQL_ADAM_DEFER_CAP], sqrt_bc2[CQL_ADAM_DEFER_CAP];
+};
+int cql_adam_ema_rows_deferred(float* theta, float* grads, float* m, float* v, float* target, uint16_t* theta_b,
+                               uint16_t* target_b, int64_t n, const CqlAdamSteps& tab, uint64_t step, float beta1, float beta2,
+                               float eps, float tau, int32_t zero_grads, const uint8_t* row_map, const uint8_t* read_next,
+                               uint8_t* age, int32_t d, int64_t n_rows, hipStream_t stream);
+// gbwd.hip: read_map[item] = 1 for every E_in row the forward of the sampled transitions gathers (the windows of s and of
+// s': items[base - min(tpos, L) .. base] with base = offsets[user] + tpos), 0 for the others; read_map has n_items bytes
+int cql_mark_read_rows(const int64_t* offsets, const int32_t* items, const int32_t* users, const int32_t* tpos,
+                       int64_t n_states, int32_t L, int64_t n_items, uint8_t* read_map, hipStream_t s);
 // gbwd.hip: row_map[item] = 1 for every item that occurs in the sorted window pairs `ws` holds (after
 // cqlrec_gather_pool_bwd_prepare on the same stream), 0 for the others; row_map has n_items bytes
 int cql_gather_pool_bwd_mark_rows(const void* ws, int64_t n_states, int32_t L, int32_t d, int64_t n_items, uint8_t* row_map,

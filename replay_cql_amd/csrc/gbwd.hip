@@ -260,7 +260,7 @@ extern "C" int cqlrec_gather_pool_bwd_prepare(const int64_t* offsets, const int3
 
 // Which rows of g_E_in will phase 2 write?  One byte per item: cleared, then set from the sorted keys (every pair of a run
 // stores the same 1: plain byte stores, no atomics; sorted keys keep the stores of a wave on a few cache lines).  The
-// pipelined step driver hands the map to its state-side optimizer launch (misc.hip, adam_ema_rows_kernel).
+// pipelined step driver hands the map to its state-side optimizer launch (misc.hip, adam_ema_rows_deferred_kernel).
 __global__ __launch_bounds__(256) void gbwd_mark_rows_kernel(const uint32_t* __restrict__ keys, int64_t n_pairs,
                                                              uint32_t pad_key, uint8_t* __restrict__ row_map) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -283,6 +283,38 @@ int cql_gather_pool_bwd_mark_rows(const void* ws, int64_t n_states, int32_t L, i
   hipLaunchKernelGGL(gbwd_mark_rows_kernel, dim3(cql_ceil_div(n, 256)), dim3(256), 0, s, w.keys_out, n, (uint32_t)n_items,
                      row_map);
   CQL_LAUNCH_CHECK("gather_pool_bwd_mark_rows");
+  return CQLREC_OK;
+}
+
+// The rows the forward of a step reads: one thread per (transition, window slot), slot j = 0 is the action item (the last
+// item of the window of s'), slots 1 .. min(tpos, L) the window of s behind it.  Needs users / tpos only, no sorted keys.
+__global__ __launch_bounds__(256) void mark_read_rows_kernel(const int64_t* __restrict__ offsets,
+                                                             const int32_t* __restrict__ items,
+                                                             const int32_t* __restrict__ users,
+                                                             const int32_t* __restrict__ tpos, int64_t n_states, int L,
+                                                             uint32_t n_items, uint8_t* __restrict__ read_map) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t b = t / (L + 1);
+  const int j = (int)(t % (L + 1));
+  if (b >= n_states) return;
+  const int tp = tpos[b];
+  if (j > (tp < L ? tp : L)) return;
+  const uint32_t it = (uint32_t)items[offsets[users[b]] + tp - j];
+  if (it < n_items) read_map[it] = 1;
+}
+int cql_mark_read_rows(const int64_t* offsets, const int32_t* items, const int32_t* users, const int32_t* tpos,
+                       int64_t n_states, int32_t L, int64_t n_items, uint8_t* read_map, hipStream_t s) {
+  CQL_REQUIRE(offsets && items && users && tpos && read_map, "mark_read_rows: NULL pointer");
+  CQL_REQUIRE(n_items > 0 && n_items < (1ll << 31) && L > 0, "mark_read_rows: n_items=%lld L=%d", (long long)n_items, L);
+  if (hipMemsetAsync(read_map, 0, (size_t)n_items, s) != hipSuccess) {
+    cql_set_error("mark_read_rows: clearing the map failed");
+    return CQLREC_ERR_HIP;
+  }
+  if (n_states <= 0) return CQLREC_OK;
+  CqlProfScope prof(CQLREC_PH_GATHER_BWD, s);
+  hipLaunchKernelGGL(mark_read_rows_kernel, dim3(cql_ceil_div(n_states * (L + 1), 256)), dim3(256), 0, s, offsets, items,
+                     users, tpos, n_states, L, (uint32_t)n_items, read_map);
+  CQL_LAUNCH_CHECK("mark_read_rows");
   return CQLREC_OK;
 }
 

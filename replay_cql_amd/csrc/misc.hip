@@ -738,8 +738,8 @@ extern "C" int cqlrec_td_loss(const float* q_a, const float* lse, const float* q
 // fused Adam + Polyak + bf16 shadows.  Pure HBM streaming: 20 B read + 24 B written per parameter in the full form
 // (zero_grads = 1, every gradient element read).  Inside a cqlrec_train_steps call the steps that have a successor run
 // leaner (train.hip): the item-side range keeps its gradient (20 B + 20 B: the next long dE_out kernel overwrites every
-// row), the E_in range goes through adam_ema_rows_kernel (16 B + 20 B for a row the batch did not touch, + 4 B read
-// for a row it did).
+// row), the E_in range goes through adam_ema_rows_deferred_kernel (16 B + 20 B for a row that is brought up to
+// date, + 4 B read if the batch touched it; one byte of age for a row that is left behind).
 // Compiled with -ffp-contract=off so the expression order below is the normative one (oracle.adam_ema_step).
 // =============================================================================================================
 template <bool NT>
@@ -770,59 +770,93 @@ __global__ __launch_bounds__(256) void adam_ema_kernel(float4* __restrict__ thet
   }
 }
 
-// The E_in range of the pipelined single-rank driver: `row_map[r] != 0` says that the window-gather backward of THIS step
+// The E_in range of the pipelined single-rank driver.  `row_map[r] != 0` says that the window-gather backward of THIS step
 // wrote gradient row r (gbwd.hip, cql_gather_pool_bwd_mark_rows).  Any other row contributes g = +0.0f -- what the full
 // form loads from a zeroed buffer -- without being read, so what an earlier step left in it is dead data.  The range starts
 // at a row boundary; rows >= n_rows (the pad row, alignment padding) are never written by anyone.  zero_grads = 1 (the
 // last step of a call) zeroes every element, stale rows included.
+//
+// Rows are deferred.  An Adam + Polyak step with g = +0.0f is a pure function of the
+// row's own (theta, m, v, target) and of the step's two scalars, so a row that no step reads may stay behind: `age[r]` counts
+// the steps row r has missed, and the launch that needs the row -- it has a gradient (row_map), the next step's forward
+// gathers it (read_next), its age reaches the table's length, or every row is wanted (read_next == NULL: the last step of a
+// call, or a step whose successor was not sampled ahead) -- replays the missed steps in registers, oldest first, each with
+// the scalars of its own step from `tab`, then runs this step's: the same adam_ema_elem in the same order as the dense
+// form, so the same bits, and the row crosses HBM once.  A row left behind has its age stored and nothing else touched;
+// its shadows are stale, and nobody reads them before a later launch has brought the row up to date.
+// A row of D floats is D/4 consecutive float4 (16 / 32 / 64 lanes) starting at a multiple of its length: it sits inside
+// one wave, whose lanes all load age[r] before the row's first lane stores it (the stored value depends on the load).
+// Rows >= n_rows (pad row, alignment padding) have no age: they take one dense step per launch, as in the form above.
+// The zero of a replayed step goes through a register the compiler cannot see through: every step of the loop, replayed
+// or current, is the one instruction sequence.
 template <bool NT>
-__global__ __launch_bounds__(256) void adam_ema_rows_kernel(float4* __restrict__ theta, float4* __restrict__ grads,
-                                                            float4* __restrict__ m, float4* __restrict__ v,
-                                                            float4* __restrict__ target, uint2* __restrict__ theta_b,
-                                                            uint2* __restrict__ target_b, int64_t n4, float step_size,
-                                                            float sqrt_bc2, float beta1, float beta2, float eps, float tau,
-                                                            int zero_grads, const uint8_t* __restrict__ row_map, int ld4row,
-                                                            int64_t n_rows) {
+__global__ __launch_bounds__(256) void adam_ema_rows_deferred_kernel(
+    float4* __restrict__ theta, float4* __restrict__ grads, float4* __restrict__ m, float4* __restrict__ v,
+    float4* __restrict__ target, uint2* __restrict__ theta_b, uint2* __restrict__ target_b, int64_t n4, CqlAdamSteps tab,
+    uint32_t step, float beta1, float beta2, float eps, float tau, int zero_grads, const uint8_t* __restrict__ row_map,
+    const uint8_t* __restrict__ read_next, uint8_t* age, int ld4row, int64_t n_rows) {
+  __shared__ float2 tab_s[CQL_ADAM_DEFER_CAP];
+  if (threadIdx.x < CQL_ADAM_DEFER_CAP)
+    tab_s[threadIdx.x] = make_float2(tab.step_size[threadIdx.x], tab.sqrt_bc2[threadIdx.x]);
+  __syncthreads();
   const float omb1 = 1.0f - beta1, omb2 = 1.0f - beta2, omt = 1.0f - tau;
+  float zero = 0.f;
+  asm volatile("" : "+v"(zero));
+  const int64_t row_lane = ((int64_t)1 << ld4row) - 1;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
     const int64_t row = i >> ld4row;
-    const bool live = row < n_rows && row_map[row] != 0;
-    float4 p4 = ld4<NT>(theta + i), m4 = ld4<NT>(m + i), v4 = ld4<NT>(v + i), t4 = ld4<NT>(target + i);
-    float4 g4 = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (live) g4 = ld4<NT>(grads + i);
-    const float g[4] = {g4.x, g4.y, g4.z, g4.w};
-    float p[4] = {p4.x, p4.y, p4.z, p4.w}, mm[4] = {m4.x, m4.y, m4.z, m4.w}, vv[4] = {v4.x, v4.y, v4.z, v4.w},
-          tt[4] = {t4.x, t4.y, t4.z, t4.w};
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      adam_ema_elem(g[k], p[k], mm[k], vv[k], tt[k], step_size, sqrt_bc2, beta1, beta2, eps, tau, omb1, omb2, omt);
+    bool live = false, go = true;
+    int k = 1;                                          // steps to run: the missed ones + this one
+    if (row < n_rows) {
+      live = row_map[row] != 0;
+      k = (int)age[row] + 1;
+      go = live || !read_next || read_next[row] != 0 || k >= CQL_ADAM_DEFER_CAP;
+      if ((i & row_lane) == 0) age[row] = go ? (uint8_t)0 : (uint8_t)k;
     }
-    st4<NT>(theta + i, p[0], p[1], p[2], p[3]);
-    st4<NT>(m + i, mm[0], mm[1], mm[2], mm[3]);
-    st4<NT>(v + i, vv[0], vv[1], vv[2], vv[3]);
-    st4<NT>(target + i, tt[0], tt[1], tt[2], tt[3]);
-    theta_b[i] = make_uint2(pack_bf16x2(p[0], p[1]), pack_bf16x2(p[2], p[3]));
-    target_b[i] = make_uint2(pack_bf16x2(tt[0], tt[1]), pack_bf16x2(tt[2], tt[3]));
+    if (go) {
+      float4 p4 = ld4<NT>(theta + i), m4 = ld4<NT>(m + i), v4 = ld4<NT>(v + i), t4 = ld4<NT>(target + i);
+      float4 g4 = make_float4(zero, zero, zero, zero);
+      if (live) g4 = ld4<NT>(grads + i);
+      const float gc[4] = {g4.x, g4.y, g4.z, g4.w};
+      float p[4] = {p4.x, p4.y, p4.z, p4.w}, mm[4] = {m4.x, m4.y, m4.z, m4.w}, vv[4] = {v4.x, v4.y, v4.z, v4.w},
+            tt[4] = {t4.x, t4.y, t4.z, t4.w};
+      for (int a = k - 1; a >= 0; --a) {
+        const float2 sc = tab_s[(step - (uint32_t)a) & (uint32_t)(CQL_ADAM_DEFER_CAP - 1)];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const float g = a == 0 ? gc[j] : zero;
+          adam_ema_elem(g, p[j], mm[j], vv[j], tt[j], sc.x, sc.y, beta1, beta2, eps, tau, omb1, omb2, omt);
+        }
+      }
+      st4<NT>(theta + i, p[0], p[1], p[2], p[3]);
+      st4<NT>(m + i, mm[0], mm[1], mm[2], mm[3]);
+      st4<NT>(v + i, vv[0], vv[1], vv[2], vv[3]);
+      st4<NT>(target + i, tt[0], tt[1], tt[2], tt[3]);
+      theta_b[i] = make_uint2(pack_bf16x2(p[0], p[1]), pack_bf16x2(p[2], p[3]));
+      target_b[i] = make_uint2(pack_bf16x2(tt[0], tt[1]), pack_bf16x2(tt[2], tt[3]));
+    }
     if (zero_grads) st4<NT>(grads + i, 0.f, 0.f, 0.f, 0.f);
   }
 }
 
-int cql_adam_ema_rows(float* theta, float* grads, float* m, float* v, float* target, uint16_t* theta_b, uint16_t* target_b,
-                      int64_t n, float step_size, float sqrt_bc2, float beta1, float beta2, float eps, float tau,
-                      int32_t zero_grads, const uint8_t* row_map, int32_t d, int64_t n_rows, hipStream_t stream) {
-  CQL_REQUIRE(theta && grads && m && v && target && theta_b && target_b && row_map, "adam_ema_rows: NULL pointer");
-  CQL_REQUIRE(n > 0 && n % 4 == 0, "adam_ema_rows: n=%lld must be a positive multiple of 4", (long long)n);
-  CQL_REQUIRE(d == 64 || d == 128 || d == 256, "adam_ema_rows: d=%d unsupported", d);
-  CQL_REQUIRE(n_rows >= 0 && n_rows * d <= n, "adam_ema_rows: %lld rows of %d do not fit n=%lld", (long long)n_rows, d,
-              (long long)n);
+int cql_adam_ema_rows_deferred(float* theta, float* grads, float* m, float* v, float* target, uint16_t* theta_b,
+                               uint16_t* target_b, int64_t n, const CqlAdamSteps& tab, uint64_t step, float beta1, float beta2,
+                               float eps, float tau, int32_t zero_grads, const uint8_t* row_map, const uint8_t* read_next,
+                               uint8_t* age, int32_t d, int64_t n_rows, hipStream_t stream) {
+  CQL_REQUIRE(theta && grads && m && v && target && theta_b && target_b && row_map && age,
+              "adam_ema_rows_deferred: NULL pointer");
+  CQL_REQUIRE(n > 0 && n % 4 == 0, "adam_ema_rows_deferred: n=%lld must be a positive multiple of 4", (long long)n);
+  CQL_REQUIRE(d == 64 || d == 128 || d == 256, "adam_ema_rows_deferred: d=%d unsupported", d);
+  CQL_REQUIRE(n_rows >= 0 && n_rows * d <= n, "adam_ema_rows_deferred: %lld rows of %d do not fit n=%lld", (long long)n_rows,
+              d, (long long)n);
   const int64_t n4 = n / 4;
   int blocks = (int)((n4 + 255) / 256);
   if (blocks > 8192) blocks = 8192;
   CqlProfScope prof(CQLREC_PH_ADAM, stream);
-  hipLaunchKernelGGL(adam_ema_rows_kernel<true>, dim3(blocks), dim3(256), 0, stream, (float4*)theta, (float4*)grads,
-                     (float4*)m, (float4*)v, (float4*)target, (uint2*)theta_b, (uint2*)target_b, n4, step_size, sqrt_bc2,
-                     beta1, beta2, eps, tau, zero_grads, row_map, __builtin_ctz((unsigned)d) - 2, n_rows);
-  CQL_LAUNCH_CHECK("adam_ema (row map)");
+  hipLaunchKernelGGL(adam_ema_rows_deferred_kernel<true>, dim3(blocks), dim3(256), 0, stream, (float4*)theta, (float4*)grads,
+                     (float4*)m, (float4*)v, (float4*)target, (uint2*)theta_b, (uint2*)target_b, n4, tab, (uint32_t)step,
+                     beta1, beta2, eps, tau, zero_grads, row_map, read_next, age, __builtin_ctz((unsigned)d) - 2, n_rows);
+  CQL_LAUNCH_CHECK("adam_ema (deferred rows)");
   return CQLREC_OK;
 }
 

@@ -55,6 +55,8 @@ struct StepWs {
   uint16_t *h0b, *zb, *hb, *h0b_t, *zb_t, *hb_t;
   void *ws_q, *ws_q2, *ws_qb, *ws_qb2, *ws_enc, *ws_gb, *ws_oh;
   uint8_t* row_map;      // [n_items] which rows of g_E_in this step's window-gather backward writes (cqlrec_train_steps)
+  uint8_t* read_map;     // [n_items] which rows of E_in this step's forward gathers (windows of s and of s')
+  uint8_t* age;          // [n_items] steps each E_in row is behind inside a cqlrec_train_steps call (one copy, not by parity)
   int64_t ws_q_bytes, ws_qb_bytes, ws_qf_bytes, ws_enc_bytes, ws_gb_bytes, ws_oh_bytes;
   int64_t total;
 };
@@ -119,6 +121,10 @@ StepWs carve_step(void* ws, int32_t B, int64_t N, int32_t d, int32_t L, uint64_t
   uint8_t* rm0 = c.take<uint8_t>(N);         // by parity like the pairs it is built from: the map of step t+1 is made
   uint8_t* rm1 = c.take<uint8_t>(N);         // while the optimizer of step t has not read its own yet
   w.row_map = (step & 1) ? rm1 : rm0;
+  uint8_t* rd0 = c.take<uint8_t>(N);         // the read map of step t+1 is made while step t runs, too
+  uint8_t* rd1 = c.take<uint8_t>(N);
+  w.read_map = (step & 1) ? rd1 : rd0;
+  w.age = c.take<uint8_t>(N);
   w.total = c.off;
   return w;
 }
@@ -166,6 +172,7 @@ struct SideStream {
   hipEvent_t sorted[2] = {nullptr, nullptr};   // sorted pairs of the step with this parity are in place
   hipEvent_t forked = nullptr, fork2 = nullptr, join2 = nullptr;
   hipEvent_t loss = nullptr, items = nullptr, dh = nullptr, eout = nullptr, presample = nullptr, fwd_done = nullptr;
+  hipEvent_t read_map = nullptr;   // the read map of the step sampled ahead is in place (the E_in optimizer waits for it)
   bool ok = false;
   bool tried = false;
 };
@@ -303,6 +310,7 @@ SideStream& side_stream() {
             hipEventCreateWithFlags(&ss.dh, hipEventDisableTiming) == hipSuccess &&
             hipEventCreateWithFlags(&ss.eout, hipEventDisableTiming) == hipSuccess &&
             hipEventCreateWithFlags(&ss.presample, hipEventDisableTiming) == hipSuccess &&
+            hipEventCreateWithFlags(&ss.read_map, hipEventDisableTiming) == hipSuccess &&
             hipEventCreateWithFlags(&ss.fwd_done, hipEventDisableTiming) == hipSuccess;
   }
   return ss;
@@ -377,13 +385,18 @@ namespace {
 // Q-head kernels (sample, window gathers, encoder) reads only E_in / W1 / W2 and may start earlier.
 // `presampled`: event after which this step's transitions are already in place (sample_ahead); the sorted pairs the
 // backward needs follow under ss.sorted[step & 1].
-int sample_ahead(const cqlrec_train_ctx* c, uint64_t step, cqlrec_stream stream, hipEvent_t sampled_ev) {
+// `read_map_ev`: recorded behind the step's read map, which needs users / tpos only and so sits in front of the pair sorts
+int sample_ahead(const cqlrec_train_ctx* c, uint64_t step, cqlrec_stream stream, hipEvent_t sampled_ev,
+                 hipEvent_t read_map_ev) {
   const cqlrec_layout& L = c->layout;
   StepWs w = carve_step(c->ws, c->batch, L.n_items, L.d, c->window, step);
   CQL_TRY(cqlrec_sample_transitions(c->offsets, c->items, c->rewards, c->n_users, c->seed, step,
                                     (uint64_t)c->rank * (uint64_t)c->batch, c->batch, w.users, w.tpos, w.act, w.rew,
                                     w.done, stream));
   CQL_HIP_TRY(hipEventRecord(sampled_ev, (hipStream_t)stream), "train_steps");
+  CQL_TRY(cql_mark_read_rows(c->offsets, c->items, w.users, w.tpos, c->batch, c->window, L.n_items, w.read_map,
+                             (hipStream_t)stream));
+  CQL_HIP_TRY(hipEventRecord(read_map_ev, (hipStream_t)stream), "train_steps");
   CQL_TRY(cqlrec_gather_pool_bwd_prepare(c->offsets, c->items, w.users, w.tpos, 0, c->batch, c->window, L.d, L.n_items,
                                          w.ws_gb, w.ws_gb_bytes, stream));
   CQL_TRY(cql_gather_pool_bwd_mark_rows(w.ws_gb, c->batch, c->window, L.d, L.n_items, w.row_map, (hipStream_t)stream));
@@ -653,8 +666,24 @@ extern "C" int cqlrec_train_step_fwd_bwd(const cqlrec_train_ctx* c, uint64_t ste
 //     left in them is dead.
 // The last step of a call runs the zeroing forms (E_in still through its map, so that stale rows count as zero and are
 // cleared), which leaves ctx->grads all zeros as the phase entry points expect.  A single-step call runs the full forms only.
+//
+// The E_in launch is also deferred per row (misc.hip, adam_ema_rows_deferred_kernel): a row without a gradient that the
+// NEXT step's forward does not gather is left behind and only its age (workspace, zero when a call starts) moves on; the
+// launch that needs it replays the missed steps.  The next step's read map comes from sample_ahead under an event of its
+// own; a step whose successor was not sampled ahead, and the last step of a call, bring every row up to date, so the
+// caller finds all six buffers complete.  After an error return from the middle of a call E_in may be behind (cqlrec.h).
 int update_range_impl(const cqlrec_train_ctx* c, uint64_t step, int64_t lo, int64_t hi, cqlrec_stream stream,
-                      const CqlAdamFix* fix, int zero_grads = 1, const uint8_t* row_map = nullptr);
+                      const CqlAdamFix* fix, int zero_grads = 1);
+namespace {
+// the two per-step scalars of the optimizer, formed in double and rounded once: these float values are normative
+void adam_step_scalars(const cqlrec_train_ctx* c, uint64_t step, float* step_size, float* sqrt_bc2) {
+  const double t = (double)(step + 1);
+  const double bc1 = 1.0 - pow((double)c->beta1, t);
+  const double bc2 = 1.0 - pow((double)c->beta2, t);
+  *step_size = (float)((double)c->lr / bc1);
+  *sqrt_bc2 = (float)sqrt(bc2);
+}
+}  // namespace
 extern "C" int cqlrec_train_steps(const cqlrec_train_ctx* c, uint64_t step0, int32_t n_steps, float* loss_out,
                                   cqlrec_stream stream) {
   CQL_TRY(check_ctx(c));
@@ -666,6 +695,11 @@ extern "C" int cqlrec_train_steps(const cqlrec_train_ctx* c, uint64_t step0, int
   hipEvent_t sampled = nullptr;   // transitions + sorted pairs of this step, prepared during the previous backward
   need_side_streams(side_stream(), true);
   const bool use_map = n_steps > 1 && L.off_E_in == 0;
+  CqlAdamSteps adam_tab = {};     // (step_size, sqrt_bc2) of the steps of this call, slot = step % CQL_ADAM_DEFER_CAP
+  if (use_map) {                  // every E_in row is up to date when a call starts
+    const StepWs w0 = carve_step(c->ws, c->batch, L.n_items, L.d, c->window, step0);
+    CQL_HIP_TRY(hipMemsetAsync(w0.age, 0, (size_t)L.n_items, s), "train_steps");
+  }
   bool grads_dirty = false;       // a lean step has run: the gradient buffer holds dead data until the last step clears it
   for (int32_t i = 0; i < n_steps; ++i) {
     const uint64_t step = step0 + (uint64_t)i;
@@ -695,7 +729,7 @@ extern "C" int cqlrec_train_steps(const cqlrec_train_ctx* c, uint64_t step0, int
         }
         // the next step's transitions depend on (seed, step) only: sample them now, on a stream of their own, and sort
         // the pairs its backward will need (two radix sorts, ~35 small launches) behind that
-        CQL_TRY(sample_ahead(c, step + 1, (cqlrec_stream)ss.s3, ss.presample));
+        CQL_TRY(sample_ahead(c, step + 1, (cqlrec_stream)ss.s3, ss.presample, ss.read_map));
         CQL_HIP_TRY(hipEventRecord(ss.sorted[(step + 1) & 1], ss.s3), "train_steps");
         if (g_mark_phase == 1) mark(MK_SORT_NEXT, ss.s3);
         sampled = ss.presample;
@@ -715,7 +749,16 @@ extern "C" int cqlrec_train_steps(const cqlrec_train_ctx* c, uint64_t step0, int
       CQL_TRY(cqlrec_train_step_update_range(c, step, L.off_W1, L.total, stream));
       if (use_map) {
         const StepWs w = carve_step(c->ws, c->batch, L.n_items, L.d, c->window, step);
-        CQL_TRY(update_range_impl(c, step, 0, L.off_E_out, stream, nullptr, lean ? 0 : 1, w.row_map));
+        const int slot = (int)(step % CQL_ADAM_DEFER_CAP);
+        adam_step_scalars(c, step, &adam_tab.step_size[slot], &adam_tab.sqrt_bc2[slot]);
+        const uint8_t* read_next = nullptr;      // NULL: bring every row up to date
+        if (lean && sampled) {
+          CQL_HIP_TRY(hipStreamWaitEvent(s, ss.read_map, 0), "train_steps");
+          read_next = carve_step(c->ws, c->batch, L.n_items, L.d, c->window, step + 1).read_map;
+        }
+        CQL_TRY(cql_adam_ema_rows_deferred(c->theta, c->grads, c->adam_m, c->adam_v, c->target, c->theta_b, c->target_b,
+                                           L.off_E_out, adam_tab, step, (float)c->beta1, (float)c->beta2, (float)c->eps,
+                                           (float)c->tau, lean ? 0 : 1, w.row_map, read_next, w.age, L.d, L.n_items, s));
       } else {
         CQL_TRY(cqlrec_train_step_update_range(c, step, 0, L.off_E_out, stream));
       }
@@ -751,21 +794,12 @@ extern "C" int cqlrec_train_step_update_range(const cqlrec_train_ctx* c, uint64_
 }
 
 int update_range_impl(const cqlrec_train_ctx* c, uint64_t step, int64_t lo, int64_t hi, cqlrec_stream stream,
-                      const CqlAdamFix* fix, int zero_grads, const uint8_t* row_map) {
+                      const CqlAdamFix* fix, int zero_grads) {
   CQL_TRY(check_ctx(c));
   CQL_REQUIRE(lo >= 0 && hi <= c->layout.total && lo < hi && lo % 4 == 0 && hi % 4 == 0,
               "train_step_update_range: bad range [%lld, %lld)", (long long)lo, (long long)hi);
-  const double t = (double)(step + 1);
-  const double bc1 = 1.0 - pow((double)c->beta1, t);
-  const double bc2 = 1.0 - pow((double)c->beta2, t);
-  const float step_size = (float)((double)c->lr / bc1);
-  const float sqrt_bc2 = (float)sqrt(bc2);
-  if (row_map) {      // rows of E_in: the range starts at row 0 of the table
-    CQL_REQUIRE(lo == c->layout.off_E_in && !fix, "train_step_update_range: the row map belongs to the E_in range");
-    return cql_adam_ema_rows(c->theta + lo, c->grads + lo, c->adam_m + lo, c->adam_v + lo, c->target + lo, c->theta_b + lo,
-                             c->target_b + lo, hi - lo, step_size, sqrt_bc2, (float)c->beta1, (float)c->beta2, (float)c->eps,
-                             (float)c->tau, zero_grads, row_map, c->layout.d, c->layout.n_items, (hipStream_t)stream);
-  }
+  float step_size, sqrt_bc2;
+  adam_step_scalars(c, step, &step_size, &sqrt_bc2);
   return cql_adam_ema_fix(c->theta + lo, c->grads + lo, c->adam_m + lo, c->adam_v + lo, c->target + lo, c->theta_b + lo,
                           c->target_b + lo, hi - lo, step_size, sqrt_bc2, (float)c->beta1, (float)c->beta2, (float)c->eps,
                           (float)c->tau, zero_grads, fix, (hipStream_t)stream);
