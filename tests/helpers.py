@@ -1,6 +1,8 @@
 """Shared test helpers: device buffers for the C ABI, oracle model <-> device state."""
 from __future__ import annotations
 
+import ctypes
+
 import numpy as np
 import torch
 
@@ -316,15 +318,19 @@ class TopkDevice:
         self.n_cand = E_c.shape[0]
         self.H, self.E, self.b = bf16_dev(Hb), bf16_dev(E_c), dev(np.asarray(b_c, dtype=np.float32))
         self.ids = None if ids is None else dev(np.asarray(ids, dtype=np.int32))
-        self.so = self.si = self.rows = None
+        self.so = self.si = self.rows = self.seen_form = None
         if seen is not None:
             self.so = dev(np.asarray(seen[0], dtype=np.int64))
             self.si = dev(np.concatenate([np.asarray(seen[1], dtype=np.int32), np.zeros(1, np.int32)]))
             self.rows = None if seen_rows is None else dev(np.asarray(seen_rows, dtype=np.int32))
 
-    def run(self, k, use_ids=True, guard_bytes=0):
+    def run(self, k, use_ids=True, guard_bytes=0, phases=None, query_form=False):
         """(idx, val, cnt) as numpy.  Outputs are pre-filled with sentinels, so an entry the pass left unwritten shows;
-        guard_bytes > 0: a poisoned region right behind the declared workspace size must come back intact."""
+        guard_bytes > 0: a poisoned region right behind the declared workspace size must come back intact.
+        phases: the CQLREC_TOPK_* phases of cqlrec_score_topk_phase to run in that order on the (fresh) workspace instead
+        of cqlrec_score_topk; query_form: self.seen_form = what cqlrec_topk_seen_form says of that workspace afterwards
+        (-1 without asking when the problem has no seen CSR: the function reports the word that the seen phase leaves in
+        the workspace, and no seen phase ran, so the word was never written)."""
         nb = int(self.lib.cqlrec_topk_ws_bytes(self.n_users, self.n_cand, self.d, k))
         ws = ws_bytes_tensor(nb + guard_bytes)
         if guard_bytes:
@@ -332,10 +338,20 @@ class TopkDevice:
         out_idx = torch.full((self.n_users, k), TOPK_IDX_SENTINEL, dtype=torch.int32, device=DEV)
         out_val = torch.full((self.n_users, k), TOPK_VAL_SENTINEL, dtype=torch.float32, device=DEV)
         out_cnt = torch.full((self.n_users,), TOPK_CNT_SENTINEL, dtype=torch.int32, device=DEV)
-        N.check(self.lib.cqlrec_score_topk(ptr(self.H), self.n_users, ptr(self.E), ptr(self.b), self.n_cand, self.d,
-                                           ptr(self.ids) if use_ids else None, ptr(self.so), ptr(self.si), ptr(self.rows), k,
-                                           ptr(ws), nb, ptr(out_idx), ptr(out_val), ptr(out_cnt), stream()))
+        args = (ptr(self.H), self.n_users, ptr(self.E), ptr(self.b), self.n_cand, self.d, ptr(self.ids) if use_ids else None,
+                ptr(self.so), ptr(self.si), ptr(self.rows), k, ptr(ws), nb, ptr(out_idx), ptr(out_val), ptr(out_cnt))
+        if phases is None:
+            N.check(self.lib.cqlrec_score_topk(*args, stream()))
+        else:
+            for phase in phases:
+                N.check(self.lib.cqlrec_score_topk_phase(*args, phase, stream()))
         sync()
+        if query_form and self.so is None:
+            self.seen_form = -1
+        elif query_form:
+            form = ctypes.c_int32(-2)
+            N.check(self.lib.cqlrec_topk_seen_form(ptr(ws), self.n_users, self.n_cand, self.d, k, ctypes.byref(form), stream()))
+            self.seen_form = form.value
         if guard_bytes:
             assert bool((ws[nb:] == 0xFF).all()), "the pass wrote behind the workspace size it asked for"
         return out_idx.cpu().numpy(), out_val.cpu().numpy(), out_cnt.cpu().numpy()
@@ -391,9 +407,15 @@ def topk_inputs(kind, n_users, Nn, d, seed, k_ref=16):
     plain     qhead_inputs(..., dyadic=False)
     neg       plain, b -= 40: every score negative
     straddle  plain, b shifted so that the k_ref-th best score changes sign across users (median of them at 0)
-    wide      plain, every E row scaled by exp(1.5 N(0,1)): group maxima spread over many exponents"""
+    wide      plain, every E row scaled by exp(1.5 N(0,1)): group maxima spread over many exponents
+    and, beside TOPK_KINDS (for the one-pass d = 128 kernels, whose running k-th best gates a slow path):
+    ramp      plain, b += 0.05 item id: the running k-th best keeps being beaten all through the pass
+    down      plain, b -= 0.05 item id: the bound is final after the first items; nothing later may enter"""
     Hb, Eb, b = qhead_inputs(n_users, Nn, d, False, seed)
-    if kind == "neg":
+    if kind in ("ramp", "down"):
+        step = np.float32(0.05 if kind == "ramp" else -0.05)
+        b = (b + step * np.arange(Nn, dtype=np.float32)).astype(np.float32)
+    elif kind == "neg":
         b = (b - np.float32(40.0)).astype(np.float32)
     elif kind == "wide":
         s = np.exp(1.5 * np.random.default_rng(seed + 1).standard_normal(Nn)).astype(np.float32)
@@ -420,6 +442,20 @@ def tk_geometry(n_cand, k):
     if k <= 16:
         return "small", kpl, 0, tg, ngroups
     return "select", kpl, (1024 if k <= 512 else 4096), tg, ngroups
+
+
+def tk2_geometry(n_users, n_cand, k, n_cu=256):
+    """(kernel, KC, users_per_block, nsplit, split_rows) of the one-pass d = 128 family (item_ids = NULL, k <= 16) -- the
+    arithmetic of cql_topk2_supported / cql_topk4_use (default mode) / cql_topk2_split in csrc/qhead_topk2.hip and
+    qhead_topk4.hip, restated.  n_cu: the CU count the library reads from the device (256 on an MI355X)."""
+    assert 1 <= k <= 16 and n_cand * 256 < 2 ** 31, "not a shape of the one-pass family"
+    stages = (n_cand + 63) // 64
+    four = n_users >= 512 * 160 and stages * 1024 < 2 ** 31
+    upb = 512 if four else 256
+    rblks = (n_users + upb - 1) // upb
+    want = max(1, min((n_cu + rblks - 1) // rblks, stages // 8, 16))       # at least eight stages per slice, at most 16 slices
+    split_rows = (stages + want - 1) // want * 64
+    return "qtopk4" if four else "qtopk2", 10 if k <= 10 else 16, upb, (n_cand + split_rows - 1) // split_rows, split_rows
 
 
 class TopkReference:
@@ -600,3 +636,133 @@ def topk_certificate(idx, val, cnt, Hb, Eb, b, k, ids=None, seen=None, seen_rows
     if fails:
         raise AssertionError(f"top-{k} certificate (n_cand {n_cand}, tg {tg}, boundary share {share:.3f}): " + " | ".join(fails))
     return out
+
+
+# ---- case builders and bitwise comparisons shared by the top-K kernel tests (two-pass: test_gpu_topk_two_pass; one-pass
+# d = 128: test_gpu_topk_onchip, test_topk_onchip_cases_cpu) ------------------------------------------------------------
+BOOST_GROUPS = (5, 69, 133, 197, 261, 325)           # all owned by lane 5 of the selection wave (group = slot * 64 + lane)
+
+
+def _np_topk(S, k, ids, seen_mask=None):
+    """exact (score desc, id asc) top-k of fp32 scores; inadmissible entries masked; padded with -1 / -inf"""
+    S = S.astype(np.float32).copy()
+    if seen_mask is not None:
+        S[seen_mask] = -np.inf
+    kk = min(k, S.shape[1])
+    order = np.argsort(-S, axis=1, kind="stable")[:, :kk]
+    val = np.take_along_axis(S, order, 1)
+    ok = np.isfinite(val)
+    idx = np.full((S.shape[0], k), -1, np.int32)
+    out = np.full((S.shape[0], k), -np.inf, np.float32)
+    idx[:, :kk] = np.where(ok, ids[order], -1)
+    out[:, :kk] = np.where(ok, val, -np.inf)
+    return idx, out, ok.sum(1).astype(np.int32)
+
+
+def _inputs(kind, n_users, n_cat, d, seed):
+    if kind == "dyadic":
+        return qhead_inputs(n_users, n_cat, d, True, seed)
+    if kind in ("flat1", "flat3"):
+        rng = np.random.default_rng(seed)
+        Eb = qhead_inputs(1, n_cat, d, False, seed)[1]
+        b = np.full(n_cat, 0.25, np.float32) if kind == "flat1" else \
+            rng.choice(np.array([-1.5, 0.25, 2.0], np.float32), n_cat)          # no -0.0: it sorts below +0.0 here
+        return np.zeros((n_users, d), np.float32), Eb, b.astype(np.float32)
+    if kind == "plain+boost":
+        return topk_inputs("plain", n_users, n_cat, d, seed)
+    return topk_inputs(kind, n_users, n_cat, d, seed)
+
+
+def _row(rng, best, n_cat, n_best, n_other):
+    """n_best of the user's best candidates (global ids) + n_other other catalogue ids, ascending, exactly that long
+    where the catalogue allows it"""
+    top = best[:max(0, n_best)]
+    pool = rng.choice(n_cat + 8, size=min(n_cat + 8, n_other + n_other // 2 + 16), replace=False)    # + 8: ids past the catalogue
+    other = pool[~np.isin(pool, top)][:n_other]
+    return np.unique(np.concatenate([top, other])).astype(np.int32)
+
+
+def _seen_rows(rng, S, ids, n_cat):
+    """(offsets, items), seen_rows, admissibility mask -- see the module docstring"""
+    n_users, n_cand = S.shape
+    n_rows = n_users + 7
+    rows_of = rng.permutation(n_rows)[:n_users].astype(np.int32)
+    if n_users > 2:
+        rows_of[2] = rows_of[1]
+    lens = {0: 0, 3: 1, 4: 511, 5: 512, 6: 513, 7: 3000}
+    rows = [np.sort(rng.choice(n_cat, min(n_cat, 9), replace=False)).astype(np.int32) for _ in range(n_rows)]
+    for u in range(n_users):
+        if u == 2 and n_users > 2:
+            continue
+        best = ids[np.argsort(-S[u], kind="stable")]
+        if u == 8:
+            row = _row(rng, best, n_cat, n_cand - 40, 10)
+        elif u == 9:
+            row = _row(rng, best, n_cat, n_cand - 5, 10)
+        elif u == 10:
+            row = _row(rng, best, n_cat, n_cand, 10)
+        else:
+            ln = min(lens.get(u, int(rng.integers(0, 40))), n_cat)
+            row = _row(rng, best, n_cat, ln // 2, ln - ln // 2)
+        rows[rows_of[u]] = row
+    off = np.concatenate([[0], np.cumsum([len(r) for r in rows])]).astype(np.int64)
+    mask = np.stack([np.isin(ids, rows[rows_of[u]]) for u in range(n_users)])
+    return (off, np.concatenate(rows).astype(np.int32)), rows_of, mask
+
+
+def build_case(cid, d, n_cand, ids_mode, kind, n_users, with_seen):
+    """host side of a case of the table: candidate rows as CQLCore.score_topk compacts them, seen CSR, admissibility"""
+    seed = sum(map(ord, cid)) * 7 + d
+    rng = np.random.default_rng(seed)
+    n_cat = n_cand if ids_mode == "identity" else n_cand + n_cand // 4 + 17
+    Hb, Eb, b = _inputs(kind, n_users, n_cat, d, seed)
+    ids = np.arange(n_cand, dtype=np.int64) if ids_mode == "identity" else \
+        np.sort(rng.choice(n_cat, n_cand, replace=False)).astype(np.int64)
+    E_c, b_c = np.ascontiguousarray(Eb[ids]), b[ids].copy()
+    if kind == "plain+boost":
+        for g in BOOST_GROUPS:
+            b_c[g * 32 + 3] += np.float32(10.0)
+    S = (Hb @ E_c.T + b_c).astype(np.float32)
+    seen = rows_of = mask = None
+    if with_seen:
+        seen, rows_of, mask = _seen_rows(rng, S, ids, n_cat)
+    return dict(Hb=Hb, E_c=E_c, b_c=b_c, ids=ids, seen=seen, rows=rows_of, mask=mask, S=S, kind=kind, n_cat=n_cat)
+
+
+def _oracle(c, k):
+    Q = O.qvalues(c["Hb"], c["E_c"], c["b_c"])
+    if c["mask"] is not None:
+        Q[c["mask"]] = -np.inf
+    kk = min(k, Q.shape[1])
+    idx_c, v = O.topk_rows(Q, kk)
+    ok = np.isfinite(v)
+    idx = np.full((Q.shape[0], k), -1, np.int32)
+    val = np.full((Q.shape[0], k), -np.inf, np.float32)
+    idx[:, :kk] = np.where(ok, c["ids"][idx_c], -1)
+    val[:, :kk] = np.where(ok, v, -np.inf)
+    return idx, val, ok.sum(1).astype(np.int32)
+
+
+def _bits(v):
+    return np.ascontiguousarray(v, dtype=np.float32).view(np.uint32)
+
+
+def _no_sentinel(res, what):
+    idx, val, cnt = res
+    assert not (idx == TOPK_IDX_SENTINEL).any() and not (val == np.float32(TOPK_VAL_SENTINEL)).any() and \
+        not (cnt == TOPK_CNT_SENTINEL).any(), f"{what}: output entries left unwritten"
+
+
+def _assert_same(a, b, what):
+    assert np.array_equal(a[2], b[2]), f"{what}: counts differ for users {np.nonzero(a[2] != b[2])[0][:6].tolist()}"
+    bad = np.nonzero((a[0] != b[0]).any(1) | (_bits(a[1]) != _bits(b[1])).any(1))[0]
+    if bad.size:
+        u = int(bad[0])
+        j = int(np.nonzero((a[0][u] != b[0][u]) | (_bits(a[1][u]) != _bits(b[1][u])))[0][0])
+        raise AssertionError(f"{what}: {bad.size} users differ, first user {u} at rank {j}: ids {a[0][u, j]} / {b[0][u, j]}, "
+                             f"values {a[1][u, j]!r} / {b[1][u, j]!r}")
+
+
+def _assert_prefix(short, long_, k2, what):
+    want = (long_[0][:, :k2], long_[1][:, :k2], np.minimum(long_[2], k2))
+    _assert_same(short, want, what)

@@ -56,8 +56,8 @@ import torch
 from oracle import cql_oracle as O
 from replay_cql_amd import _native as N
 
-from helpers import (DEV, TOPK_CNT_SENTINEL, TOPK_IDX_SENTINEL, TOPK_KINDS, TOPK_VAL_SENTINEL, TopkDevice, TopkReference,
-                     bf16_to_np, qhead_inputs, tk_geometry, topk_certificate, topk_inputs)
+from helpers import (BOOST_GROUPS, DEV, TOPK_KINDS, TopkDevice, TopkReference, _assert_prefix, _assert_same, _no_sentinel,
+                     _oracle, bf16_to_np, build_case, tk_geometry, topk_certificate)
 
 pytestmark = pytest.mark.gpu
 
@@ -98,7 +98,6 @@ CASES = [
     ("y256_140k",  256,  140001, 64, 2, "subset",   "dyadic",        24, True,  (10, 100)),
 ]
 ORACLE_KINDS = ("flat1", "flat3", "dyadic")          # exact in every summation order: bit-identical to O.topk_rows
-BOOST_GROUPS = (5, 69, 133, 197, 261, 325)           # all owned by lane 5 of the selection wave (group = slot * 64 + lane)
 
 
 @pytest.fixture(scope="module")
@@ -125,116 +124,6 @@ def test_case_table_reaches_every_instantiation():
     # the edges of the candidate buffers and of the two kernels
     assert [tk_geometry(3000, k)[:3:2] for k in (16, 17, 512, 513)] == [("small", 0), ("select", 1024), ("select", 1024),
                                                                          ("select", 4096)]
-
-
-# ---------------------------------------------------------------------------------------------------------------- inputs
-def _inputs(kind, n_users, n_cat, d, seed):
-    if kind == "dyadic":
-        return qhead_inputs(n_users, n_cat, d, True, seed)
-    if kind in ("flat1", "flat3"):
-        rng = np.random.default_rng(seed)
-        Eb = qhead_inputs(1, n_cat, d, False, seed)[1]
-        b = np.full(n_cat, 0.25, np.float32) if kind == "flat1" else \
-            rng.choice(np.array([-1.5, 0.25, 2.0], np.float32), n_cat)          # no -0.0: it sorts below +0.0 here
-        return np.zeros((n_users, d), np.float32), Eb, b.astype(np.float32)
-    if kind == "plain+boost":
-        return topk_inputs("plain", n_users, n_cat, d, seed)
-    return topk_inputs(kind, n_users, n_cat, d, seed)
-
-
-def _row(rng, best, n_cat, n_best, n_other):
-    """n_best of the user's best candidates (global ids) + n_other other catalogue ids, ascending, exactly that long
-    where the catalogue allows it"""
-    top = best[:max(0, n_best)]
-    pool = rng.choice(n_cat + 8, size=min(n_cat + 8, n_other + n_other // 2 + 16), replace=False)    # + 8: ids past the catalogue
-    other = pool[~np.isin(pool, top)][:n_other]
-    return np.unique(np.concatenate([top, other])).astype(np.int32)
-
-
-def _seen_rows(rng, S, ids, n_cat):
-    """(offsets, items), seen_rows, admissibility mask -- see the module docstring"""
-    n_users, n_cand = S.shape
-    n_rows = n_users + 7
-    rows_of = rng.permutation(n_rows)[:n_users].astype(np.int32)
-    if n_users > 2:
-        rows_of[2] = rows_of[1]
-    lens = {0: 0, 3: 1, 4: 511, 5: 512, 6: 513, 7: 3000}
-    rows = [np.sort(rng.choice(n_cat, min(n_cat, 9), replace=False)).astype(np.int32) for _ in range(n_rows)]
-    for u in range(n_users):
-        if u == 2 and n_users > 2:
-            continue
-        best = ids[np.argsort(-S[u], kind="stable")]
-        if u == 8:
-            row = _row(rng, best, n_cat, n_cand - 40, 10)
-        elif u == 9:
-            row = _row(rng, best, n_cat, n_cand - 5, 10)
-        elif u == 10:
-            row = _row(rng, best, n_cat, n_cand, 10)
-        else:
-            ln = min(lens.get(u, int(rng.integers(0, 40))), n_cat)
-            row = _row(rng, best, n_cat, ln // 2, ln - ln // 2)
-        rows[rows_of[u]] = row
-    off = np.concatenate([[0], np.cumsum([len(r) for r in rows])]).astype(np.int64)
-    mask = np.stack([np.isin(ids, rows[rows_of[u]]) for u in range(n_users)])
-    return (off, np.concatenate(rows).astype(np.int32)), rows_of, mask
-
-
-def build_case(cid, d, n_cand, ids_mode, kind, n_users, with_seen):
-    """host side of a case of the table: candidate rows as CQLCore.score_topk compacts them, seen CSR, admissibility"""
-    seed = sum(map(ord, cid)) * 7 + d
-    rng = np.random.default_rng(seed)
-    n_cat = n_cand if ids_mode == "identity" else n_cand + n_cand // 4 + 17
-    Hb, Eb, b = _inputs(kind, n_users, n_cat, d, seed)
-    ids = np.arange(n_cand, dtype=np.int64) if ids_mode == "identity" else \
-        np.sort(rng.choice(n_cat, n_cand, replace=False)).astype(np.int64)
-    E_c, b_c = np.ascontiguousarray(Eb[ids]), b[ids].copy()
-    if kind == "plain+boost":
-        for g in BOOST_GROUPS:
-            b_c[g * 32 + 3] += np.float32(10.0)
-    S = (Hb @ E_c.T + b_c).astype(np.float32)
-    seen = rows_of = mask = None
-    if with_seen:
-        seen, rows_of, mask = _seen_rows(rng, S, ids, n_cat)
-    return dict(Hb=Hb, E_c=E_c, b_c=b_c, ids=ids, seen=seen, rows=rows_of, mask=mask, S=S, kind=kind, n_cat=n_cat)
-
-
-def _oracle(c, k):
-    Q = O.qvalues(c["Hb"], c["E_c"], c["b_c"])
-    if c["mask"] is not None:
-        Q[c["mask"]] = -np.inf
-    kk = min(k, Q.shape[1])
-    idx_c, v = O.topk_rows(Q, kk)
-    ok = np.isfinite(v)
-    idx = np.full((Q.shape[0], k), -1, np.int32)
-    val = np.full((Q.shape[0], k), -np.inf, np.float32)
-    idx[:, :kk] = np.where(ok, c["ids"][idx_c], -1)
-    val[:, :kk] = np.where(ok, v, -np.inf)
-    return idx, val, ok.sum(1).astype(np.int32)
-
-
-def _bits(v):
-    return np.ascontiguousarray(v, dtype=np.float32).view(np.uint32)
-
-
-def _no_sentinel(res, what):
-    idx, val, cnt = res
-    assert not (idx == TOPK_IDX_SENTINEL).any() and not (val == np.float32(TOPK_VAL_SENTINEL)).any() and \
-        not (cnt == TOPK_CNT_SENTINEL).any(), f"{what}: output entries left unwritten"
-
-
-def _assert_same(a, b, what):
-    assert np.array_equal(a[2], b[2]), f"{what}: counts differ for users {np.nonzero(a[2] != b[2])[0][:6].tolist()}"
-    bad = np.nonzero((a[0] != b[0]).any(1) | (_bits(a[1]) != _bits(b[1])).any(1))[0]
-    if bad.size:
-        u = int(bad[0])
-        j = int(np.nonzero((a[0][u] != b[0][u]) | (_bits(a[1][u]) != _bits(b[1][u])))[0][0])
-        raise AssertionError(f"{what}: {bad.size} users differ, first user {u} at rank {j}: ids {a[0][u, j]} / {b[0][u, j]}, "
-                             f"values {a[1][u, j]!r} / {b[1][u, j]!r}")
-
-
-def _assert_prefix(short, long_, k2, what):
-    want = (long_[0][:, :k2], long_[1][:, :k2], np.minimum(long_[2], k2))
-    _assert_same(short, want, what)
 
 
 @pytest.mark.parametrize("case", CASES, ids=[c[0] for c in CASES])

@@ -9,7 +9,7 @@ import functools
 import numpy as np
 import pytest
 
-from helpers import TOPK_KINDS, TopkReference, topk_certificate, topk_inputs
+from helpers import TOPK_KINDS, TopkReference, _np_topk, topk_certificate, topk_inputs
 
 N_USERS, N_CAT, K = 24, 24000, 10
 DS = (64, 128, 256)
@@ -28,22 +28,6 @@ def _scores(Hb, Ec, bc, order):
     for i in range(d):
         acc += Hb[:, i:i + 1] * Ec[None, :, i]
     return (acc + bc).astype(np.float32)
-
-
-def _np_topk(S, k, ids, seen_mask=None):
-    """exact (score desc, id asc) top-k of fp32 scores; inadmissible entries masked; padded with -1 / -inf"""
-    S = S.astype(np.float32).copy()
-    if seen_mask is not None:
-        S[seen_mask] = -np.inf
-    kk = min(k, S.shape[1])
-    order = np.argsort(-S, axis=1, kind="stable")[:, :kk]
-    val = np.take_along_axis(S, order, 1)
-    ok = np.isfinite(val)
-    idx = np.full((S.shape[0], k), -1, np.int32)
-    out = np.full((S.shape[0], k), -np.inf, np.float32)
-    idx[:, :kk] = np.where(ok, ids[order], -1)
-    out[:, :kk] = np.where(ok, val, -np.inf)
-    return idx, out, ok.sum(1).astype(np.int32)
 
 
 @functools.lru_cache(maxsize=2)
