@@ -69,6 +69,7 @@ int cql_onehot_apply(const float* coef, const uint16_t* H_b, int64_t batch, int6
                      float* g_E_out, float* g_b_out, hipStream_t s, int accumulate = 0);
 
 static inline int cql_ceil_div(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
+static inline int64_t cql_align256(int64_t x) { return (x + 255) / 256 * 256; }   // workspace sections
 
 // ---- bf16 <-> f32 ------------------------------------------------------------------------------------------
 __device__ __forceinline__ float bf16_bits_to_f32(uint16_t b) { return __uint_as_float(((uint32_t)b) << 16); }

@@ -16,13 +16,13 @@
 //                                     (< 2^-21 relative), so the inflated product is >= every value of the group.
 //           Neither the self pair nor a zero-norm candidate nor the padding of the last stage (copies of the last
 //           candidate) is masked here: a maximum over a superset is still an upper bound.
-//   pass 2  knn_select_kernel, one wave per query, the exact threshold algorithm of topk.hip: groups are visited in
-//           descending order of their bound and re-scored with the SAME MFMA chain (acc = 0; K steps ascending;
-//           A = candidate rows, B = query) followed by the metric in the normative operation order; admissible pairs
-//           become 64-bit keys  order(value) << 32 | neighbour id  -- the id itself, not its complement: the reference
-//           orders by (value desc, neighbour id DESC), base_rec.py:911-917.  The walk stops when the best unvisited
-//           bound is below the value of the k-th best key so far.  Whatever pass 1 wrote only steers which groups are
-//           re-scored; every value that is returned comes from pass 2.
+//   pass 2  knn_select_kernel, one wave per query, the exact threshold algorithm on the pieces of select_common.h.
+//           Specific to this file: the bounds' keys live in LDS (gkey) and the groups are visited one at a time in
+//           descending order of their bound; a group is re-scored with the SAME MFMA chain (acc = 0) followed by the
+//           metric in the normative operation order; keys hold the neighbour id itself, not its complement: the
+//           reference orders by (value desc, neighbour id DESC), base_rec.py:911-917.  The walk stops when the best
+//           unvisited bound is below the value of the k-th best key so far.  Whatever pass 1 wrote only steers which
+//           groups are re-scored; every value that is returned comes from pass 2.
 //   No float atomics; the same call gives the same bits twice.  This file is compiled with -ffp-contract=off: the
 //   metric expressions are normative in their operation order (NumPy float32 doing the same gives the same bits).
 #include <stdlib.h>
@@ -30,8 +30,9 @@
 #include "select_common.h"
 
 #define KNN_MAX_K 512
-#define KNN_CB 1024             // candidate keys in LDS per query (8 KiB) >= 2 * KNN_MAX_K
-#define KNN_MAX_GROUPS 4096     // bounds per query (their keys live in 16 KiB of LDS in pass 2)
+#define KNN_CB 1024             // candidate keys in LDS per query (8 KiB)
+// sel_keep_topk leaves at most k <= KNN_MAX_K keys, so a tile of 32 more always fits behind them
+static_assert(KNN_CB >= 2 * KNN_MAX_K, "knn_select_kernel: no room to append after a tighten");
 #define KNN_UNIT 64             // candidate slices start on multiples of this many rows
 #define KNN_QPB 256             // queries per block of pass 1: 4 waves x 2 groups of 32
 #define KNN_TARGET_BLOCKS 1024
@@ -220,30 +221,6 @@ __global__ __launch_bounds__(256) void knn_bound_kernel(const uint16_t* __restri
   }
 }
 
-// [groups][queries] -> [queries][gstride]  (32x32 tiles through LDS; both sides coalesced)
-__global__ __launch_bounds__(256) void knn_transpose_kernel(const float* __restrict__ src, int ngroups, int64_t n_query,
-                                                            float* __restrict__ dst, int gstride) {
-  __shared__ float t[32][33];
-  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-  const int64_t u0 = (int64_t)blockIdx.x * 32;
-  const int g0 = blockIdx.y * 32;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int g = g0 + ty + 8 * j;
-    const int64_t u = u0 + tx;
-    t[ty + 8 * j][tx] = (g < ngroups && u < n_query) ? src[(int64_t)g * n_query + u] : NEG_INF_F;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int64_t u = u0 + ty + 8 * j;
-    const int g = g0 + tx;
-    if (u < n_query && g < gstride) dst[u * gstride + g] = t[tx][ty + 8 * j];
-  }
-}
-
-// ---- selection helpers (one wave; the scheme of topk.hip): select_common.h ----------------------------------------
-
 // ---- pass 2 ---------------------------------------------------------------------------------------------------------
 template <int D, int M>
 __global__ __launch_bounds__(64) void knn_select_kernel(const uint16_t* __restrict__ Qb, const float* __restrict__ qn,
@@ -257,13 +234,12 @@ __global__ __launch_bounds__(64) void knn_select_kernel(const uint16_t* __restri
   __shared__ uint32_t hist[256];
   __shared__ float scores[32];
   __shared__ uint64_t cand[KNN_CB];
-  __shared__ uint32_t gkey[KNN_MAX_GROUPS];     // order keys of the bounds; 0 = visited
+  __shared__ uint32_t gkey[SEL_MAX_GROUPS];      // order keys of the bounds; 0 = visited
 
   const int lane = threadIdx.x, r = lane & 31, h = lane >> 5;
   const int64_t u = blockIdx.x;
   const int32_t my_id = query_rows[u];
   const float ni = qn[u];
-  const unsigned long long lt_mask = (1ull << lane) - 1;
 
   int ncand = 0;
   const bool dead = (M == CQLREC_SIM_COSINE) && !(sqrtf(ni) != 0.0f);    // every denominator is 0: no admissible pair
@@ -293,18 +269,8 @@ __global__ __launch_bounds__(64) void knn_select_kernel(const uint16_t* __restri
     uint64_t tau = 0;        // k-th best key so far (valid once have_k)
     bool have_k = false;
     auto tighten = [&]() {
-      ncand = knn_keep_topk(cand, ncand, k, hist, lane);
-      if (ncand >= k) {
-        uint64_t m = ~0ull;
-        for (int i = lane; i < ncand; i += 64) m = cand[i] < m ? cand[i] : m;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-          const uint64_t o = __shfl_xor(m, off);
-          m = o < m ? o : m;
-        }
-        tau = m;
-        have_k = true;
-      }
+      ncand = sel_keep_topk(cand, ncand, k, hist, lane, tau);
+      have_k = ncand >= k;
     };
 
     // exact re-scoring of one group (wave-uniform g): tg tiles of 32 candidates -> admissible ones appended to cand[]
@@ -313,33 +279,21 @@ __global__ __launch_bounds__(64) void knn_select_kernel(const uint16_t* __restri
         const int64_t item0 = ((int64_t)g * tg + t) * 32;
         if (item0 >= n_cand) break;
         if (ncand + 32 > KNN_CB) tighten();
-        if (ncand + 32 > KNN_CB) ncand = KNN_CB - 32;      // only with repeated candidate rows (equal keys): stay in bounds
         const int64_t ca = (item0 + r < n_cand) ? item0 + r : n_cand - 1;
         const int64_t arow = knn_clamp_row(cand_rows ? (int64_t)cand_rows[ca] : ca, n_rows);
         f32x16 acc;
 #pragma unroll
         for (int i = 0; i < 16; ++i) acc[i] = 0.0f;
-#pragma unroll
-        for (int s = 0; s < KS; ++s) {
-          const bf16x8 af = *reinterpret_cast<const bf16x8*>(E_b + arow * D + 16 * s + 8 * h);
-          acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, hf[s], acc, 0, 0, 0);
-        }
-        if (r == 0) {
-#pragma unroll
-          for (int i = 0; i < 16; ++i) scores[mfma_row(i, h)] = acc[i];
-        }
-        __syncthreads();
+        sel_score_tile<D>(E_b, arow, hf, acc, scores, r, h);
         bool valid = false;
         uint64_t ck = 0;
         if (lane < 32 && item0 + lane < n_cand) {
           float v;
           const bool ok = knn_value<M>(scores[lane], ni, norms[arow], v);
-          ck = ((uint64_t)f32_order_key(v) << 32) | (uint64_t)(uint32_t)arow;
+          ck = sel_make_key<false>(v, (uint32_t)arow);
           valid = ok && ((int32_t)arow != my_id) && (!have_k || ck > tau);
         }
-        const unsigned long long m = __ballot(valid);
-        if (valid) cand[ncand + __popcll(m & lt_mask)] = ck;
-        ncand += __popcll(m);
+        sel_append(cand, ncand, valid, ck, lane);
         __syncthreads();
       }
     };
@@ -347,7 +301,7 @@ __global__ __launch_bounds__(64) void knn_select_kernel(const uint16_t* __restri
     const int slack = (k / 8 > 1) ? k / 8 : 1;
     for (;;) {
       const uint64_t c1 = bk ? (((uint64_t)bk << 32) | (uint64_t)(~(uint32_t)bg)) : 0ull;
-      const uint64_t cw = knn_wave_max_u64(c1);
+      const uint64_t cw = sel_wave_max_u64(c1);
       if (cw == 0) break;                                                  // every group visited
       // a key of this group is at most (bound, largest id): it can enter only if the bound reaches tau's value
       if (have_k && (uint32_t)(cw >> 32) < (uint32_t)(tau >> 32)) break;
@@ -359,10 +313,12 @@ __global__ __launch_bounds__(64) void knn_select_kernel(const uint16_t* __restri
       rescore(g);
       if (ncand >= k && (!have_k || ncand - k >= slack)) tighten();
     }
-    ncand = knn_keep_topk(cand, ncand, k, hist, lane);
-    if (ncand > k) ncand = k;                              // (equal keys again)
+    ncand = sel_keep_topk(cand, ncand, k, hist, lane);
     __syncthreads();
-    // rank the survivors
+    // The ranking epilogue is written out here, not sel_emit behind the block: with the shared form the dot-product
+    // instantiation ran 1 % slower than before (profiles/select_refactor_ab.md, "kNN").  ncand <= k, so every rank is
+    // below k.  Candidate rows listed twice (outside the ABI's contract) give equal keys, which share a rank: one slot
+    // of the row then stays unwritten, as before.
     for (int i = lane; i < ncand; i += 64) {
       const uint64_t ck = cand[i];
       int rank = 0;
@@ -379,29 +335,18 @@ __global__ __launch_bounds__(64) void knn_select_kernel(const uint16_t* __restri
 }
 
 // ---- host -----------------------------------------------------------------------------------------------------------
-static inline int64_t knn_align256(int64_t x) { return (x + 255) / 256 * 256; }
-
-static int knn_groups(int64_t n_cand, int* tg_out) {
-  const int64_t tiles = (n_cand + 31) / 32;
-  int tg = 1;
-  while ((tiles + tg - 1) / tg > KNN_MAX_GROUPS) tg *= 2;
-  *tg_out = tg;
-  return (int)((tiles + tg - 1) / tg);
-}
-
 struct KnnWs {
   int64_t off_q, off_qn, off_b, off_bt, total;
-  int ngroups, gstride, tg;
+  SelGroups g;
 };
 static KnnWs knn_ws_layout(int64_t n_query, int64_t n_cand, int32_t d) {
   KnnWs w;
-  w.ngroups = knn_groups(n_cand, &w.tg);
-  w.gstride = (w.ngroups + 63) / 64 * 64;
+  w.g = sel_groups(n_cand);
   w.off_q = 0;
-  w.off_qn = w.off_q + knn_align256(n_query * d * 2);
-  w.off_b = w.off_qn + knn_align256(n_query * 4);
-  w.off_bt = w.off_b + knn_align256((int64_t)w.ngroups * n_query * 4);
-  w.total = w.off_bt + knn_align256((int64_t)w.gstride * n_query * 4) + 256;
+  w.off_qn = w.off_q + cql_align256(n_query * d * 2);
+  w.off_b = w.off_qn + cql_align256(n_query * 4);
+  w.off_bt = w.off_b + cql_align256((int64_t)w.g.ngroups * n_query * 4);
+  w.total = w.off_bt + cql_align256((int64_t)w.g.gstride * n_query * 4) + 256;
   return w;
 }
 
@@ -435,7 +380,7 @@ static void knn_launch(const uint16_t* E_b, const float* norms, int64_t n_rows, 
   hipLaunchKernelGGL((knn_gather_kernel<D>), dim3(cql_ceil_div(n_query * (D / 8), 256)), dim3(256), 0, s, E_b, norms, n_rows,
                      query_rows, n_query, Qb, qn);
   // candidate slices: whole groups and whole stages, enough blocks to fill the chip
-  const int64_t unit = (32 * w.tg > KNN_UNIT) ? 32 * w.tg : KNN_UNIT;
+  const int64_t unit = (32 * w.g.tg > KNN_UNIT) ? 32 * w.g.tg : KNN_UNIT;
   const int64_t units = (n_cand + unit - 1) / unit;
   const int64_t qblocks = (n_query + KNN_QPB - 1) / KNN_QPB;
   int64_t nsplit = (KNN_TARGET_BLOCKS + qblocks - 1) / qblocks;
@@ -444,13 +389,12 @@ static void knn_launch(const uint16_t* E_b, const float* norms, int64_t n_rows, 
   const int64_t split_rows = (units + nsplit - 1) / nsplit * unit;
   nsplit = (n_cand + split_rows - 1) / split_rows;
   hipLaunchKernelGGL((knn_bound_kernel<D, M>), dim3((unsigned)qblocks, (unsigned)nsplit), dim3(256), 0, s,
-                     (const uint16_t*)Qb, (const float*)qn, n_query, E_b, norms, n_rows, cand_rows, n_cand, split_rows, w.tg,
+                     (const uint16_t*)Qb, (const float*)qn, n_query, E_b, norms, n_rows, cand_rows, n_cand, split_rows, w.g.tg,
                      bound);
-  hipLaunchKernelGGL(knn_transpose_kernel, dim3(cql_ceil_div(n_query, 32), cql_ceil_div(w.gstride, 32)), dim3(256), 0, s,
-                     (const float*)bound, w.ngroups, n_query, bound_t, w.gstride);
+  cql_sel_transpose(bound, w.g.ngroups, n_query, bound_t, w.g.gstride, s);
   hipLaunchKernelGGL((knn_select_kernel<D, M>), dim3((unsigned)n_query), dim3(64), 0, s, (const uint16_t*)Qb,
                      (const float*)qn, query_rows, n_query, E_b, norms, n_rows, cand_rows, n_cand, (const float*)bound_t,
-                     w.gstride, w.ngroups, w.tg, k, out_idx, out_val, out_cnt);
+                     w.g.gstride, w.g.ngroups, w.g.tg, k, out_idx, out_val, out_cnt);
 }
 
 extern "C" int cqlrec_item_knn(const uint16_t* E_b, const float* norms, int64_t n_rows, int32_t d, const int32_t* query_rows,

@@ -13,12 +13,10 @@
 //                 xor butterfly over the group, + b[item] -- the same bits, which is what lets predict_pairs(k) return
 //                 the frame the host path returned.  Scores of a chunk of 256 candidates wait in LDS.
 //   admit         all 64 lanes then take one candidate each: the score goes to out_score (coalesced), the row's seen
-//                 list (ascending) is binary-searched, admissible pairs become 64-bit keys
-//                 order(score) << 32 | ~item (larger key = better: score desc, item id asc) and are appended to an LDS
-//                 buffer of 1024 keys; once a k-th best key tau is known only keys above it are appended.
-//   select        when the buffer cannot take another chunk: radix select of the k-th largest key (select_common.h) and
-//                 compaction.  A candidate listed twice gives the same key twice, so the compaction counts multiplicity:
-//                 every key above the k-th, and of the keys equal to it exactly as many as are still missing.
+//                 list is searched, admissible pairs become keys (score desc, item id asc) in an LDS buffer of 1024;
+//                 once a k-th best key tau is known only keys above it are appended (select_common.h).
+//   select        when the buffer cannot take another chunk: sel_keep_topk.  A candidate listed twice gives the same
+//                 key twice; the shared select counts such keys as often as they occur.
 //                 At the end the survivors are ranked (rank = keys above + equal keys before) and written: to the row's
 //                 output (the only or first piece) or, as keys, to the piece's slot of the workspace.
 //   merge         one wave per cut row: the keys of its output and of its further pieces through the same buffer.
@@ -61,7 +59,7 @@ struct PtArgs {
   PtHeader* hdr;
   PtLong* long_tab;
   PtPiece* piece_tab;
-  unsigned long long* part;      // [PT_MAX_EXTRA][k] keys, 0 = none
+  uint64_t* part;                // [PT_MAX_EXTRA][k] keys, 0 = none
 };
 
 __device__ __forceinline__ int64_t pt_piece_len(unsigned long long long_total) {
@@ -92,53 +90,25 @@ __global__ __launch_bounds__(256) void pt_plan_kernel(PtArgs a) {
 // ---- the k largest keys of a buffer, duplicates counted --------------------------------------------------------------
 struct PtSel {
   int ncand;
-  unsigned long long tau;   // k-th best key so far (valid once have_k)
+  uint64_t tau;   // k-th best key so far (valid once have_k)
   bool have_k;
 };
 
-// keep the k largest keys of buf[0..n) at the front (unordered): all keys above the k-th largest and, of those equal to
-// it, as many as are missing.  knn_radix_kth counts equal keys as often as they occur, so its result is the k-th largest
-// of the multiset.
-static __device__ void pt_tighten(unsigned long long* buf, PtSel& s, int k, uint32_t* hist, int lane) {
-  const int n = s.ncand;
-  if (n <= k) return;
-  const unsigned long long thr = knn_radix_kth((const uint64_t*)buf, n, k, hist, lane);
-  const unsigned long long lt_mask = (1ull << lane) - 1;
-  int gt = 0;
-  for (int base = 0; base < n; base += 64) {
-    const int i = base + lane;
-    gt += __popcll(__ballot(i < n && buf[i] > thr));
-  }
-  const int allow_eq = k - gt;
-  int cnt = 0, eq_seen = 0;
-  for (int base = 0; base < n; base += 64) {
-    const int i = base + lane;
-    const unsigned long long key = (i < n) ? buf[i] : 0;
-    const bool is_eq = (i < n) && (key == thr);
-    const unsigned long long me = __ballot(is_eq);
-    const bool keep = (i < n) && (key > thr || (is_eq && eq_seen + __popcll(me & lt_mask) < allow_eq));
-    const unsigned long long m = __ballot(keep);
-    const int pos = cnt + __popcll(m & lt_mask);
-    __syncthreads();
-    if (keep) buf[pos] = key;
-    cnt += __popcll(m);
-    eq_seen += __popcll(me);
-    __syncthreads();
-  }
-  s.ncand = cnt;
-  s.tau = thr;
-  s.have_k = true;
+// (every caller has more than k keys in the buffer; at exactly k, tau would be their minimum: also a valid bound)
+static __device__ void pt_tighten(uint64_t* buf, PtSel& s, int k, uint32_t* hist, int lane) {
+  s.ncand = sel_keep_topk(buf, s.ncand, k, hist, lane, s.tau);
+  s.have_k = s.ncand >= k;
 }
 
 // rank the survivors and write them: to the row's output, or as keys to part_dst[0..k)
-static __device__ void pt_emit(unsigned long long* buf, PtSel& s, int k, uint32_t* hist, int lane, int32_t* out_idx,
-                               float* out_val, int32_t* out_cnt, unsigned long long* part_dst) {
+static __device__ void pt_emit(uint64_t* buf, PtSel& s, int k, uint32_t* hist, int lane, int32_t* out_idx,
+                               float* out_val, int32_t* out_cnt, uint64_t* part_dst) {
   if (s.ncand > k && s.ncand > PT_DIRECT) pt_tighten(buf, s, k, hist, lane);
   const int n = s.ncand;
   if ((n & 1) && lane == 0) buf[n] = 0;       // n odd => n < PT_CB: the pair-wise loop below reads one key past the end
   __syncthreads();
   for (int i = lane; i < n; i += 64) {
-    const unsigned long long key = buf[i];
+    const uint64_t key = buf[i];
     int rank = 0;
     for (int j = 0; j < n; j += 2) {
       const ulonglong2 kk = *reinterpret_cast<const ulonglong2*>(&buf[j]);
@@ -147,10 +117,7 @@ static __device__ void pt_emit(unsigned long long* buf, PtSel& s, int k, uint32_
     }
     if (rank < k) {
       if (part_dst) part_dst[rank] = key;
-      else {
-        out_idx[rank] = (int32_t)(~(uint32_t)(key & 0xFFFFFFFFull));
-        out_val[rank] = f32_from_order_key((uint32_t)(key >> 32));
-      }
+      else sel_write_key<true>(key, out_idx + rank, out_val + rank);
     }
   }
   const int cnt = n < k ? n : k;
@@ -164,18 +131,10 @@ static __device__ void pt_emit(unsigned long long* buf, PtSel& s, int k, uint32_
   if (!part_dst && lane == 0) *out_cnt = cnt;
 }
 
-// append this lane's key (if valid) to the buffer; the caller has made room for 64 keys
-static __device__ __forceinline__ void pt_append(unsigned long long* buf, PtSel& s, bool valid, unsigned long long key,
-                                                 int lane) {
-  const unsigned long long m = __ballot(valid);
-  if (valid) buf[s.ncand + __popcll(m & ((1ull << lane) - 1))] = key;
-  s.ncand += __popcll(m);
-}
-
 // ---- one piece: candidates [lo, lo + n) of CSR row r, state vector i -------------------------------------------------
 template <int D>
 static __device__ void pt_run_piece(const PtArgs& a, int64_t i, int64_t r, int64_t lo, int64_t n,
-                                    unsigned long long* part_dst, unsigned long long* buf, float* sc, uint32_t* hist) {
+                                    uint64_t* part_dst, uint64_t* buf, float* sc, uint32_t* hist) {
   constexpr int LPR = D / 8, RPW = 64 / LPR, U = 4, STEP = RPW * U;
   const int lane = threadIdx.x, g = lane / LPR, c = lane % LPR;
   const int k = a.k;
@@ -242,18 +201,9 @@ static __device__ void pt_run_piece(const PtArgs& a, int64_t i, int64_t r, int64
       const float s = ok ? sc[j] : 0.f;
       if (ok && a.out_score) a.out_score[lo + c0 + j] = s;
       if (k > 0) {
-        bool adm = ok;
-        if (adm && s_hi > s_lo) {
-          int64_t l = s_lo, h = s_hi;
-          while (l < h) {                      // first seen item >= item
-            const int64_t mid = (l + h) >> 1;
-            if (a.seen_items[mid] < item) l = mid + 1;
-            else h = mid;
-          }
-          adm = !(l < s_hi && a.seen_items[l] == item);
-        }
-        const unsigned long long key = ((unsigned long long)f32_order_key(s) << 32) | (unsigned long long)(~(uint32_t)item);
-        pt_append(buf, sel, adm && (!sel.have_k || key > sel.tau), key, lane);
+        const bool adm = ok && !sel_seen(a.seen_items, s_lo, s_hi, item);
+        const uint64_t key = sel_make_key<true>(s, (uint32_t)item);
+        sel_append(buf, sel.ncand, adm && (!sel.have_k || key > sel.tau), key, lane);
       }
     }
     __syncthreads();
@@ -265,7 +215,7 @@ static __device__ void pt_run_piece(const PtArgs& a, int64_t i, int64_t r, int64
 // one wave per selected row: the whole row, or the first piece of a cut row (whose further pieces it registers)
 template <int D>
 __global__ __launch_bounds__(64) void pt_row_kernel(PtArgs a) {
-  __shared__ __attribute__((aligned(16))) unsigned long long buf[PT_CB];
+  __shared__ __attribute__((aligned(16))) uint64_t buf[PT_CB];
   __shared__ float sc[PT_CHUNK];
   __shared__ uint32_t hist[256];
   const int lane = threadIdx.x;
@@ -298,7 +248,7 @@ __global__ __launch_bounds__(64) void pt_row_kernel(PtArgs a) {
 // the further pieces of the cut rows
 template <int D>
 __global__ __launch_bounds__(64) void pt_piece_kernel(PtArgs a) {
-  __shared__ __attribute__((aligned(16))) unsigned long long buf[PT_CB];
+  __shared__ __attribute__((aligned(16))) uint64_t buf[PT_CB];
   __shared__ float sc[PT_CHUNK];
   __shared__ uint32_t hist[256];
   const int p = blockIdx.x;
@@ -316,7 +266,7 @@ __global__ __launch_bounds__(64) void pt_piece_kernel(PtArgs a) {
 
 // one wave per cut row: its output (the first piece's list) and the lists of its further pieces -> its output
 __global__ __launch_bounds__(64) void pt_merge_kernel(PtArgs a) {
-  __shared__ __attribute__((aligned(16))) unsigned long long buf[PT_CB];
+  __shared__ __attribute__((aligned(16))) uint64_t buf[PT_CB];
   __shared__ uint32_t hist[256];
   const int lane = threadIdx.x;
   if (blockIdx.x >= a.hdr->n_long) return;
@@ -326,17 +276,16 @@ __global__ __launch_bounds__(64) void pt_merge_kernel(PtArgs a) {
   PtSel sel = {0, 0ull, false};
   const int cnt0 = a.out_cnt[i];
   for (int t = lane; t < cnt0; t += 64)
-    buf[t] = ((unsigned long long)f32_order_key(a.out_val[i * k + t]) << 32) |
-             (unsigned long long)(~(uint32_t)a.out_idx[i * k + t]);
+    buf[t] = sel_make_key<true>(a.out_val[i * k + t], (uint32_t)a.out_idx[i * k + t]);
   sel.ncand = cnt0;
   __syncthreads();
-  const unsigned long long* __restrict__ src = a.part + (int64_t)e.pbase * k;
+  const uint64_t* __restrict__ src = a.part + (int64_t)e.pbase * k;
   const int64_t total = (int64_t)e.extra * k;
   for (int64_t t0 = 0; t0 < total; t0 += 64) {
     if (sel.ncand + 64 > PT_CB) pt_tighten(buf, sel, k, hist, lane);
     const int64_t t = t0 + lane;
-    const unsigned long long key = (t < total) ? src[t] : 0ull;
-    pt_append(buf, sel, key != 0ull && (!sel.have_k || key > sel.tau), key, lane);
+    const uint64_t key = (t < total) ? src[t] : 0ull;
+    sel_append(buf, sel.ncand, key != 0ull && (!sel.have_k || key > sel.tau), key, lane);
     __syncthreads();
   }
   pt_emit(buf, sel, k, hist, lane, a.out_idx + i * k, a.out_val + i * k, a.out_cnt + i, nullptr);
@@ -392,7 +341,7 @@ extern "C" int cqlrec_pairs_topk(const uint16_t* H_b, const uint16_t* E_b, const
   a.hdr = (PtHeader*)base;
   a.long_tab = (PtLong*)(base + w.off_long);
   a.piece_tab = (PtPiece*)(base + w.off_piece);
-  a.part = (unsigned long long*)(base + w.off_part);
+  a.part = (uint64_t*)(base + w.off_part);
   if (hipMemsetAsync(base, 0, 256, s) != hipSuccess ||
       hipMemsetAsync(base + w.off_piece, 0xFF, (size_t)PT_MAX_EXTRA * sizeof(PtPiece), s) != hipSuccess) {
     cql_set_error("pairs_topk: hipMemsetAsync failed");

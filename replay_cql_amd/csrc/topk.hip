@@ -3,126 +3,21 @@
 //   pass 1  qstream_kernel<TILEMAX>: the MFMA Q-head; per (user, group of G = 32*tg items) only the group maximum
 //           is written, tilemax[group][user] (n_cand/G floats per user instead of n_cand), then transposed to
 //           [user][group] so that the per-user pass reads whole lines.
-//   pass 2  topk_select_kernel, one wave per user, exact "threshold algorithm":
-//           round 1: radix-select the k best groups by (max desc, group asc) from keys held in REGISTERS, re-score
-//                    those groups with the same MFMA chain as pass 1 (bit-identical scores), drop seen / out-of-range
-//                    items, keep candidates as 64-bit keys (order-preserving score bits << 32 | ~item id);
-//           round n: tau = k-th best candidate so far.  Only a group whose upper bound (its maximum, at its first item
-//                    id) still beats tau can change the answer; re-score exactly those, update tau, repeat.  Stops
-//                    when no unprocessed group can beat tau -- usually after k + (a few) groups of 32 items.
-//           finally rank the k survivors and write (item id, score).
-//   Ordering is exactly (score desc, item id asc) -- the tie rule of SURVEY.md F7 / 8.0 S7.
+//   pass 2  one wave per user, the exact threshold algorithm on the pieces of select_common.h.  Specific to this file:
+//           topk_select_kernel (k > 16) holds the group keys in REGISTERS and visits the groups in batched rounds: a
+//           radix select of the k best unprocessed groups by (max desc, group asc), of which those whose upper bound
+//           (the maximum, at the group's first item id) still beats tau are re-scored with the MFMA chain of pass 1
+//           (bit-identical scores); seen / out-of-range items are dropped.  Stops when no unprocessed group can beat
+//           tau -- usually after k + (a few) groups of 32 items.  topk_select_small_kernel (k <= 16): see there.
+//   Ordering is exactly (score desc, item id asc) -- the tie rule of SURVEY.md F7 / 8.0 S7: keys hold ~item id.
 #include <stdlib.h>
 #include "qhead_internal.h"
+#include "select_common.h"
 
 #define TK_CB_SMALL 1024    // candidate buffer entries (LDS, 8 KiB): k <= 512
 #define TK_CB_LARGE 4096    // 32 KiB: k <= 2048 (rare; lower occupancy)
 #define TK_MAX_K 2048
-#define TK_MAX_GROUPS 4096
 #define TK_SEEN_LDS 512      // seen-list entries kept in LDS per user
-
-__device__ __forceinline__ uint64_t make_key(float score, uint32_t id) {
-  return ((uint64_t)f32_order_key(score) << 32) | (uint64_t)(~id);
-}
-
-// digit selection shared by the two radix selects: with the histogram of the current digit in hist[], find the digit
-// that holds the `need`-th largest element; returns (digit, rank inside that digit's bin) wave-uniformly.
-__device__ __forceinline__ void radix_pick(const uint32_t* hist, int lane, int& need, int& digit) {
-  uint32_t bins[4];
-  uint32_t local = 0;
-#pragma unroll
-  for (int b = 0; b < 4; ++b) {
-    bins[b] = hist[lane * 4 + b];
-    local += bins[b];
-  }
-  uint32_t suf = local;  // inclusive suffix sum over lanes >= lane
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const uint32_t t = __shfl_down(suf, off);
-    if (lane + off < 64) suf += t;
-  }
-  const uint32_t above = suf - local;
-  const bool mine = (above < (uint32_t)need) && ((uint32_t)need <= suf);
-  int dg = 0, need_new = need;
-  if (mine) {
-    uint32_t c = above;
-#pragma unroll
-    for (int b = 3; b >= 0; --b) {
-      if (c + bins[b] >= (uint32_t)need) {
-        dg = lane * 4 + b;
-        need_new = need - (int)c;
-        break;
-      }
-      c += bins[b];
-    }
-  }
-  const unsigned long long m = __ballot(mine);
-  const int src = __ffsll((long long)m) - 1;
-  digit = __shfl(dg, src);
-  need = __shfl(need_new, src);
-}
-
-// k-th largest (1-based) of n distinct 64-bit keys in LDS `buf`; whole wave participates; hist = 256 LDS words.
-__device__ uint64_t radix_kth(const uint64_t* buf, int n, int kth, uint32_t* hist, int lane) {
-  uint64_t prefix = 0;
-  int need = kth;
-  for (int shift = 56; shift >= 0; shift -= 8) {
-    for (int i = lane; i < 256; i += 64) hist[i] = 0;
-    __syncthreads();
-    for (int i = lane; i < n; i += 64) {
-      const uint64_t key = buf[i];
-      const bool match = (shift == 56) || ((key >> (shift + 8)) == (prefix >> (shift + 8)));
-      if (match) atomicAdd(&hist[(key >> shift) & 255], 1u);
-    }
-    __syncthreads();
-    int digit;
-    radix_pick(hist, lane, need, digit);
-    prefix |= (uint64_t)digit << shift;
-    __syncthreads();
-  }
-  return prefix;
-}
-
-// keep the k largest keys of buf[0..n) at the front (unordered); returns the new count
-__device__ int select_topk_inplace(uint64_t* buf, int n, int k, uint32_t* hist, int lane) {
-  if (n <= k) return n;
-  const uint64_t thr = radix_kth(buf, n, k, hist, lane);
-  int cnt = 0;
-  for (int base = 0; base < n; base += 64) {
-    const int i = base + lane;
-    const uint64_t key = (i < n) ? buf[i] : 0;
-    const bool keep = (i < n) && (key >= thr);
-    const unsigned long long m = __ballot(keep);
-    const int pos = cnt + __popcll(m & ((1ull << lane) - 1));
-    __syncthreads();
-    if (keep) buf[pos] = key;
-    cnt += __popcll(m);
-    __syncthreads();
-  }
-  return cnt;
-}
-
-// [groups][users] -> [users][gstride]  (32x32 tiles through LDS; both sides coalesced)
-__global__ __launch_bounds__(256) void tilemax_transpose_kernel(const float* __restrict__ src, int ngroups,
-                                                                int64_t n_users, float* __restrict__ dst, int gstride) {
-  __shared__ float t[32][33];
-  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;   // 32 x 8
-  const int64_t u0 = (int64_t)blockIdx.x * 32;
-  const int g0 = blockIdx.y * 32;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int g = g0 + ty + 8 * j;
-    const int64_t u = u0 + tx;
-    t[ty + 8 * j][tx] = (g < ngroups && u < n_users) ? src[(int64_t)g * n_users + u] : NEG_INF_F;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int64_t u = u0 + ty + 8 * j;
-    const int g = g0 + tx;
-    if (u < n_users && g < gstride) dst[u * gstride + g] = t[tx][ty + 8 * j];
-  }
-}
 
 template <int D, int KPL, int TK_CB>
 __global__ __launch_bounds__(64) void topk_select_kernel(const uint16_t* __restrict__ H_b, int64_t n_users,
@@ -195,7 +90,7 @@ __global__ __launch_bounds__(64) void topk_select_kernel(const uint16_t* __restr
       }
       __syncthreads();
       int digit;
-      radix_pick(hist, lane, need, digit);
+      sel_radix_pick(hist, lane, need, digit);
       T |= (uint32_t)digit << shift;
       __syncthreads();
     }
@@ -214,6 +109,10 @@ __global__ __launch_bounds__(64) void topk_select_kernel(const uint16_t* __restr
   for (int s = 0; s < KS; ++s) hf[s] = *reinterpret_cast<const bf16x8*>(H_b + u * D + 16 * s + 8 * h);
 
   int ncand = 0;
+  // This kernel inlines rescore once per key slot (64 copies at KPL = 64).  Its tile, search, append and ranking are
+  // written out, its keeps are the distinct-key form and tau (which moves only between rounds) is the minimum of the
+  // survivors: with the shared pieces topk_bench --k 100 "no seen" ran 0.2 - 1.4 % slower than before (the table
+  // "How topk_select_kernel got there" of profiles/select_refactor_ab.md).  topk_select_small_kernel and item_knn.hip use the shared ones.
   // exact re-scoring of one group (wave-uniform g): tg tiles of 32 candidates -> admissible ones appended to cand[]
   auto rescore = [&](int g) {
     for (int t = 0; t < tg; ++t) {
@@ -245,7 +144,7 @@ __global__ __launch_bounds__(64) void topk_select_kernel(const uint16_t* __restr
           const float sc = scores[lane];
           const int32_t gid = item_ids ? item_ids[c] : (int32_t)c;
           valid = true;
-          if (ns > 0) {  // binary search in the user's ascending seen list
+          if (ns > 0) {
             int lo = 0, hi = ns;
             while (lo < hi) {
               const int mid = (lo + hi) >> 1;
@@ -254,7 +153,7 @@ __global__ __launch_bounds__(64) void topk_select_kernel(const uint16_t* __restr
             }
             if (lo < ns && (seen_in_lds ? seen_lds[lo] : seen_items[so + lo]) == gid) valid = false;
           }
-          ck = make_key(sc, (uint32_t)gid);
+          ck = sel_make_key<true>(sc, (uint32_t)gid);
         }
       }
       const unsigned long long m = __ballot(valid);
@@ -262,7 +161,7 @@ __global__ __launch_bounds__(64) void topk_select_kernel(const uint16_t* __restr
       if (valid) cand[pos] = ck;
       ncand += __popcll(m);
       __syncthreads();
-      if (ncand + 32 > TK_CB) ncand = select_topk_inplace(cand, ncand, k, hist, lane);
+      if (ncand + 32 > TK_CB) ncand = sel_keep_topk<false>(cand, ncand, k, hist, lane);
     }
   };
 
@@ -318,20 +217,10 @@ __global__ __launch_bounds__(64) void topk_select_kernel(const uint16_t* __restr
       }
     }
     if (!any) break;   // the best remaining groups cannot change the answer, nor can any worse one
-    ncand = select_topk_inplace(cand, ncand, k, hist, lane);
-    if (ncand >= k) {
-      tau = ~0ull;
-      for (int i = lane; i < ncand; i += 64) tau = cand[i] < tau ? cand[i] : tau;
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) {
-        const uint64_t o = __shfl_xor(tau, off);
-        tau = o < tau ? o : tau;
-      }
-    }
+    ncand = sel_keep_topk<false>(cand, ncand, k, hist, lane);
+    if (ncand >= k) tau = sel_buf_min(cand, ncand, lane);
   }
-  ncand = select_topk_inplace(cand, ncand, k, hist, lane);
-
-  // ---- rank the survivors -------------------------------------------------------------------------------------------
+  ncand = sel_keep_topk<false>(cand, ncand, k, hist, lane);
   for (int i = lane; i < ncand; i += 64) {
     const uint64_t ck = cand[i];
     int rank = 0;
@@ -359,15 +248,6 @@ __global__ __launch_bounds__(64) void topk_select_kernel(const uint16_t* __restr
 #define TKS_MAX_K 16
 #define TKS_CB 512           // candidate capacity in LDS = 8 register slots per lane
 
-__device__ __forceinline__ uint64_t wave_max_u64(uint64_t v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const uint64_t o = __shfl_xor(v, off);
-    v = o > v ? o : v;
-  }
-  return v;
-}
-
 template <int D, int KPL>
 __global__ __launch_bounds__(64) void topk_select_small_kernel(const uint16_t* __restrict__ H_b, int64_t n_users,
                                                                const uint16_t* __restrict__ E_b,
@@ -390,7 +270,6 @@ __global__ __launch_bounds__(64) void topk_select_small_kernel(const uint16_t* _
   const int64_t srow = seen_rows ? (int64_t)seen_rows[u] : u;
   const int64_t so = seen_off ? seen_off[srow] : 0;
   const int ns = seen_off ? (int)(seen_off[srow + 1] - so) : 0;
-  const unsigned long long lt_mask = (1ull << lane) - 1;
 
   const bool seen_in_lds = ns <= TK_SEEN_LDS;
   if (seen_in_lds) {
@@ -441,7 +320,7 @@ __global__ __launch_bounds__(64) void topk_select_small_kernel(const uint16_t* _
       uint64_t m = 0;
 #pragma unroll
       for (int q = 0; q < TKS_CB / 64; ++q) m = ck[q] > m ? ck[q] : m;
-      const uint64_t w = wave_max_u64(m);
+      const uint64_t w = sel_wave_max_u64(m);
 #pragma unroll
       for (int q = 0; q < TKS_CB / 64; ++q) ck[q] = (ck[q] == w) ? 0ull : ck[q];   // keys are distinct
       if (lane == 0) best[j] = w;
@@ -459,6 +338,7 @@ __global__ __launch_bounds__(64) void topk_select_small_kernel(const uint16_t* _
       const int64_t item0 = ((int64_t)g * tg + t) * 32;
       if (item0 >= n_cand) break;
       if (ncand + 32 > TKS_CB) take_top_k();
+      // not sel_score_tile: the candidate rows are loaded ahead of the bias's trip through LDS, which hides that trip
       int64_t arow = item0 + r;
       if (arow >= n_cand) arow = n_cand - 1;
       bf16x8 af[KS];
@@ -489,22 +369,12 @@ __global__ __launch_bounds__(64) void topk_select_small_kernel(const uint16_t* _
         const int64_t c = item0 + lane;
         if (c < n_cand) {
           const int32_t gid = item_ids ? item_ids[c] : (int32_t)c;
-          ck = make_key(scores[lane], (uint32_t)gid);
+          ck = sel_make_key<true>(scores[lane], (uint32_t)gid);
           valid = !have_k || ck > tau;            // below the current k-th best: cannot enter the answer
-          if (valid && ns > 0) {                  // binary search in the user's ascending seen list
-            int lo = 0, hi = ns;
-            while (lo < hi) {
-              const int mid = (lo + hi) >> 1;
-              const int32_t v = seen_in_lds ? seen_lds[mid] : seen_items[so + mid];
-              if (v < gid) lo = mid + 1; else hi = mid;
-            }
-            if (lo < ns && (seen_in_lds ? seen_lds[lo] : seen_items[so + lo]) == gid) valid = false;
-          }
+          if (valid) valid = !(seen_in_lds ? sel_seen(seen_lds, 0, ns, gid) : sel_seen(seen_items + so, 0, ns, gid));
         }
       }
-      const unsigned long long m = __ballot(valid);
-      if (valid) cand[ncand + __popcll(m & lt_mask)] = ck;
-      ncand += __popcll(m);
+      sel_append(cand, ncand, valid, ck, lane);
       __syncthreads();
     }
   };
@@ -513,7 +383,7 @@ __global__ __launch_bounds__(64) void topk_select_small_kernel(const uint16_t* _
   int visited = 0;
   for (;;) {
     const uint64_t c1 = b1k ? (((uint64_t)b1k << 32) | (uint64_t)(~(uint32_t)(b1s * 64 + lane))) : 0ull;
-    const uint64_t cw = wave_max_u64(c1);
+    const uint64_t cw = sel_wave_max_u64(c1);
     if (cw == 0) break;                                  // every group processed
     const int g = (int)(~(uint32_t)(cw & 0xFFFFFFFFull));
     if (have_k) {
@@ -543,16 +413,8 @@ __global__ __launch_bounds__(64) void topk_select_small_kernel(const uint16_t* _
     }
   }
   take_top_k();
-  if (lane < ncand) {
-    const uint64_t ck = best[lane];
-    out_idx[u * k + lane] = (int32_t)(~(uint32_t)(ck & 0xFFFFFFFFull));
-    out_val[u * k + lane] = f32_from_order_key((uint32_t)(ck >> 32));
-  }
-  for (int i = ncand + lane; i < k; i += 64) {
-    out_idx[u * k + i] = -1;
-    out_val[u * k + i] = NEG_INF_F;
-  }
-  if (lane == 0) out_cnt[u] = ncand;
+  if (lane < ncand) sel_write_key<true>(best[lane], out_idx + u * k + lane, out_val + u * k + lane);   // best[] is sorted
+  sel_pad(ncand, k, lane, out_idx + u * k, out_val + u * k, out_cnt + u);
 }
 
 // =============================================================================================================
@@ -682,7 +544,6 @@ static void tk_launch_merge(const unsigned long long* keys, int nsplit, int64_t 
                        k, out_idx, out_val, out_cnt);
 }
 
-static inline int64_t align256(int64_t x) { return (x + 255) / 256 * 256; }
 static inline int64_t tk_bits_words(int64_t n_cand) { return ((n_cand + 31) / 32 + 3) / 4 * 4; }
 #define TK_FUSED_MAX_SPLIT 32
 static QSplit tk_fused_split(int64_t n_cand, int64_t n_users, int d) {
@@ -697,28 +558,20 @@ static QSplit tk_fused_split(int64_t n_cand, int64_t n_users, int d) {
   return sp;
 }
 
-static int tk_tile_groups(int64_t n_cand, int* tg_out) {
-  const int64_t tiles = (n_cand + 31) / 32;
-  int tg = 1;
-  while ((tiles + tg - 1) / tg > TK_MAX_GROUPS) tg *= 2;
-  *tg_out = tg;
-  return (int)((tiles + tg - 1) / tg);
-}
-
 extern "C" int64_t cqlrec_topk_ws_bytes(int64_t n_users, int64_t n_cand, int32_t d, int32_t k) {
   (void)d;
   (void)k;
-  int tg;
-  const int ngroups = tk_tile_groups(n_cand, &tg);
-  const int gstride = (ngroups + 63) / 64 * 64;
-  const int64_t two_pass = align256((int64_t)ngroups * n_users * 4) + align256((int64_t)gstride * n_users * 4);
-  int64_t fused = align256((int64_t)tk_fused_split(n_cand, n_users, d).nsplit * n_users * 2 * QS_TOPK_K * 8) +
-                  align256(n_users * tk_bits_words(n_cand) * 4);
+  const SelGroups sg = sel_groups(n_cand);
+  const int64_t two_pass =
+      cql_align256((int64_t)sg.ngroups * n_users * 4) + cql_align256((int64_t)sg.gstride * n_users * 4);
+  int64_t fused = cql_align256((int64_t)tk_fused_split(n_cand, n_users, d).nsplit * n_users * 2 * QS_TOPK_K * 8) +
+                  cql_align256(n_users * tk_bits_words(n_cand) * 4);
   if (cql_topk2_supported(d, k, n_cand)) {
     int ns;
     int64_t sr;
     cql_topk2_split(n_users, n_cand, &ns, &sr);
-    const int64_t f2 = align256((int64_t)ns * n_users * 2 * QS_TOPK_K * 8) + align256(cql_topk2_bits_bytes(n_users, n_cand));
+    const int64_t f2 =
+        cql_align256((int64_t)ns * n_users * 2 * QS_TOPK_K * 8) + cql_align256(cql_topk2_bits_bytes(n_users, n_cand));
     if (f2 > fused) fused = f2;
   }
   return (two_pass > fused ? two_pass : fused) + 256;
@@ -746,7 +599,7 @@ extern "C" int cqlrec_topk_seen_form(const void* ws, int64_t n_users, int64_t n_
   int ns;
   int64_t sr;
   cql_topk2_split(n_users, n_cand, &ns, &sr);
-  const uint32_t* bits = (const uint32_t*)((const char*)ws + align256((int64_t)ns * n_users * 2 * QS_TOPK_K * 8));
+  const uint32_t* bits = (const uint32_t*)((const char*)ws + cql_align256((int64_t)ns * n_users * 2 * QS_TOPK_K * 8));
   const uint32_t* word = cql_topk2_lists_word(bits, n_users, n_cand);
   if (!word) return CQLREC_OK;
   uint32_t v = 0;
@@ -774,7 +627,7 @@ extern "C" int cqlrec_score_topk_phase(const uint16_t* H_b, int64_t n_users, con
     int ns;
     int64_t sr;
     cql_topk2_split(n_users, n_cand, &ns, &sr);
-    uint32_t* bits = (uint32_t*)((char*)ws + align256((int64_t)ns * n_users * 2 * QS_TOPK_K * 8));
+    uint32_t* bits = (uint32_t*)((char*)ws + cql_align256((int64_t)ns * n_users * 2 * QS_TOPK_K * 8));
     CqlProfScope prof(CQLREC_PH_TOPK_SELECT, (hipStream_t)stream);
     return cql_topk2_seen_bits(seen_off, seen_items, seen_rows, n_users, n_cand, bits, (hipStream_t)stream,
                                phase == CQLREC_TOPK_SEEN_BESIDE);
@@ -798,7 +651,7 @@ extern "C" int cqlrec_score_topk_phase(const uint16_t* H_b, int64_t n_users, con
     cql_topk2_split(n_users, n_cand, &a2.nsplit, &a2.split_rows);
     a2.keys = (unsigned long long*)ws;
     if (seen_off) {
-      uint32_t* bits = (uint32_t*)((char*)ws + align256((int64_t)a2.nsplit * n_users * 2 * QS_TOPK_K * 8));
+      uint32_t* bits = (uint32_t*)((char*)ws + cql_align256((int64_t)a2.nsplit * n_users * 2 * QS_TOPK_K * 8));
       if (phase == CQLREC_TOPK_ALL) {
         CqlProfScope prof(CQLREC_PH_TOPK_SELECT, s);
         const int rc = cql_topk2_seen_bits(seen_off, seen_items, seen_rows, n_users, n_cand, bits, s);
@@ -824,7 +677,7 @@ extern "C" int cqlrec_score_topk_phase(const uint16_t* H_b, int64_t n_users, con
     uint32_t* bits = nullptr;
     const int64_t W = tk_bits_words(n_cand);
     if (seen_off) {
-      bits = (uint32_t*)((char*)ws + align256((int64_t)sp.nsplit * n_users * 2 * QS_TOPK_K * 8));
+      bits = (uint32_t*)((char*)ws + cql_align256((int64_t)sp.nsplit * n_users * 2 * QS_TOPK_K * 8));
       CqlProfScope prof(CQLREC_PH_TOPK_SELECT, s);
       if (hipMemsetAsync(bits, 0, (size_t)n_users * W * 4, s) != hipSuccess) {
         cql_set_error("score_topk: hipMemsetAsync failed");
@@ -852,11 +705,10 @@ extern "C" int cqlrec_score_topk_phase(const uint16_t* H_b, int64_t n_users, con
     CQL_LAUNCH_CHECK("score_topk (fused)");
     return CQLREC_OK;
   }
-  int tg;
-  const int ngroups = tk_tile_groups(n_cand, &tg);
-  const int gstride = (ngroups + 63) / 64 * 64;
+  const SelGroups sg = sel_groups(n_cand);
+  const int tg = sg.tg, ngroups = sg.ngroups, gstride = sg.gstride;
   float* tm = (float*)ws;
-  float* tm_t = (float*)((char*)ws + align256((int64_t)ngroups * n_users * 4));
+  float* tm_t = (float*)((char*)ws + cql_align256((int64_t)ngroups * n_users * 4));
   // pass 1
   const int unit = (32 * tg > QS_TI) ? 32 * tg : QS_TI;
   const QSplit sp = qs_choose_split(n_cand, n_users, QS_SPW_FWD, unit, QS_TARGET_BLOCKS);
@@ -873,8 +725,7 @@ extern "C" int cqlrec_score_topk_phase(const uint16_t* H_b, int64_t n_users, con
   qs_launch(QM_TILEMAX, a, d, sp.rblks, s);
   // pass 2
   CqlProfScope prof(CQLREC_PH_TOPK_SELECT, s);
-  hipLaunchKernelGGL(tilemax_transpose_kernel, dim3(cql_ceil_div(n_users, 32), cql_ceil_div(gstride, 32)), dim3(256), 0,
-                     s, tm, ngroups, n_users, tm_t, gstride);
+  cql_sel_transpose(tm, ngroups, n_users, tm_t, gstride, s);
   dim3 grid((unsigned)n_users), block(64);
 #define TK_LAUNCH_CB(DD, KP, CB)                                                                                      \
   hipLaunchKernelGGL((topk_select_kernel<DD, KP, CB>), grid, block, 0, s, H_b, n_users, E_b, b, n_cand, item_ids,        \

@@ -431,8 +431,8 @@ def topk_inputs(kind, n_users, Nn, d, seed, k_ref=16):
 
 
 def tk_geometry(n_cand, k):
-    """(kernel, KPL, CB, tg, ngroups) of the two-pass family for n_cand candidates at k -- the arithmetic of tk_tile_groups /
-    TK_BY_KPL / TK_LAUNCH in csrc/topk.hip, restated (the tests assert their case tables against it)."""
+    """(kernel, KPL, CB, tg, ngroups) of the two-pass family for n_cand candidates at k -- the arithmetic of sel_groups
+    (csrc/select_common.h, SEL_MAX_GROUPS = 4096) and TK_BY_KPL / TK_LAUNCH in csrc/topk.hip, restated (the tests assert their case tables against it)."""
     tiles = (n_cand + 31) // 32
     tg = 1
     while (tiles + tg - 1) // tg > 4096:

@@ -103,6 +103,21 @@ def test_exact_on_grid_tables(lib, n, d):
             assert not np.any(ridx == query[:, None])             # the reference itself: never its own neighbour
 
 
+def test_k_at_the_limit_keeps_exactly_k(lib):
+    """k = 512 = KNN_MAX_K over 2 048 candidates (64 groups, tg = 1): every tighten has to leave exactly k survivors,
+    half of the 1 024-entry buffer, and all k output slots are filled.  At this shape the slack tighten fires at
+    k + k / 8 = 576 keys, so the buffer-full branch (reached only with tg >= 16) is not what this pins.  Dot product on
+    the grid table: ids and value bits of the reference."""
+    n, d, k = 2048, 64, 512
+    V, dup, zero = grid_table(n, d, seed=77)
+    query = np.unique(np.concatenate([[zero], dup[:8], np.arange(0, n, 97)]))
+    ridx, rval, rcnt = R.nearest_items(V, query, np.arange(n), k, "dot_product", dtype=np.float32)
+    idx, val, cnt = run_abi(lib, bf16_dev(V), query, None, "dot_product", k)
+    assert np.array_equal(cnt, rcnt) and np.all(cnt == k)
+    assert np.array_equal(idx, ridx)
+    assert np.array_equal(val.view(np.uint32), rval.view(np.uint32))
+
+
 def trained_like(n, d, seed):
     g = torch.Generator().manual_seed(seed)
     G1, G2, G3 = torch.randn(n, 16, generator=g), torch.randn(16, d, generator=g), torch.randn(n, d, generator=g)
