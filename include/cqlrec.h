@@ -593,6 +593,74 @@ int cqlrec_split_compact(const uint8_t* is_train, const uint8_t* is_test, int64_
                          int64_t* train_rows, int64_t* test_rows, int64_t* counts, cqlrec_stream stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * f6  Log preparation on the device: the filters of replay/filters.py (k-core by minimum count, rating threshold,
+ * first / last N events or days of a user, global day windows, a time period) and the Indexer of
+ * replay/data_preparator.py (raw integer ids <-> dense indices).  The rules of f5 carry over: integer work throughout,
+ * integer atomics only (atomicAdd / atomicMin / atomicMax / atomicOr), the same input gives the same bytes; group ids
+ * (user_idx, item_idx, any group column) are dense non-negative ids below n_groups which the CALLER range-checks;
+ * n_rows < 2^31; arguments are validated on the host before any HIP call.
+ * --------------------------------------------------------------------------------------------------------- */
+/* rank [n_rows] = 1-based row number inside the user ordered by (key DESCENDING, key2 DESCENDING, input row index
+ * DESCENDING); count [n_users] = rows per user.  The ascending row number is count[u] + 1 - rank.  key: as in
+ * cqlrec_split_rank.  key2: NULL, or non-negative values below n_key2 (the item of take_num_user_interactions).  Stable
+ * LSD radix sorts over a reversed row permutation: key2, key, user.  n_rows == 0: count = 0. */
+int64_t cqlrec_prepare_rank_ws_bytes(int64_t n_rows, int64_t n_users);
+int cqlrec_prepare_rank(const int32_t* user_idx, const int64_t* key, const int32_t* key2, int64_t n_rows, int64_t n_users,
+                        int64_t n_key2, void* ws, int64_t ws_bytes, int32_t* rank, int32_t* count, cqlrec_stream stream);
+
+/* count [n_groups] = rows whose id is g (integer atomicAdd). */
+int cqlrec_prepare_count(const int32_t* ids, int64_t n_rows, int64_t n_groups, int32_t* count, cqlrec_stream stream);
+
+/* gmin / gmax [n_groups] = least / greatest key of the group's rows (INT64_MAX / INT64_MIN for a group without rows).
+ * group == NULL: the whole column is one group (n_groups must be 1; block reductions, one pair of atomics per block). */
+int cqlrec_prepare_minmax(const int32_t* group, const int64_t* key, int64_t n_rows, int64_t n_groups, int64_t* gmin,
+                          int64_t* gmax, cqlrec_stream stream);
+
+/* keep [n_rows]: one byte per row, 1 = the row stays.
+ *   MIN_COUNT         count[group] >= n                                              (filter_by_min_count)
+ *   MIN_VALUE         value >= x, IEEE: a NaN row goes                               (filter_out_low_ratings)
+ *   NUM_INTERACTIONS  first ? count[group] + 1 - rank <= n : rank <= n               (take_num_user_interactions)
+ *   DAYS_USER         first ? t < extreme[group] (+) span : t > extreme[group] (-) span   (take_num_days_of_user_hist;
+ *                     extreme = the group's min when first, its max otherwise)
+ *   DAYS_GLOBAL       the same with extreme[0]                                       (take_num_days_of_global_hist)
+ *   PERIOD            lo <= key && (open_end || key < hi)                            (take_time_period)
+ * The span of the DAYS rules: float_key == 0: n, in the key's unit, added / subtracted in int64 SATURATING at the int64
+ * limits; float_key != 0: key and extreme are data.timestamp_key images of doubles, decoded back, the bound is ONE
+ * double add / subtract of x and the comparison is made in double.  Arrays a rule does not read may be NULL. */
+#define CQLREC_KEEP_MIN_COUNT 0
+#define CQLREC_KEEP_MIN_VALUE 1
+#define CQLREC_KEEP_NUM_INTERACTIONS 2
+#define CQLREC_KEEP_DAYS_USER 3
+#define CQLREC_KEEP_DAYS_GLOBAL 4
+#define CQLREC_KEEP_PERIOD 5
+int cqlrec_prepare_keep(int32_t rule, const int32_t* group, const int64_t* key, const double* value, const int32_t* rank,
+                        const int32_t* count, const int64_t* extreme, int64_t n_rows, int64_t n, int32_t first,
+                        int32_t float_key, int64_t lo, int64_t hi, int32_t open_end, double x, uint8_t* keep,
+                        cqlrec_stream stream);
+
+/* Stable compaction: rows [n_rows] receives the ascending indices of the rows whose byte is non-zero, *n_kept (device)
+ * how many.  n_rows == 0: *n_kept = 0. */
+int64_t cqlrec_prepare_compact_ws_bytes(int64_t n_rows);
+int cqlrec_prepare_compact(const uint8_t* keep, int64_t n_rows, void* ws, int64_t ws_bytes, int64_t* rows,
+                           int64_t* n_kept, cqlrec_stream stream);
+
+/* Indexer.  distinct: out [n] receives the distinct values of ids[n] in ascending signed order, *n_out (device) how
+ * many (radix sort + unique).  sort_labels: sorted [m] = labels ascending, sorted_idx [m] = the position each had in
+ * labels (labels are distinct).  lookup: out[i] = the label index of ids[i] (binary search over sorted), or -1 and
+ * *miss = 1 (device; 0 when every id was found).  gather: out[i] = labels[idx[i]]; an index outside [0, m) gives 0
+ * and *bad = 1 (device). */
+int64_t cqlrec_prepare_distinct_ws_bytes(int64_t n);
+int cqlrec_prepare_distinct(const int64_t* ids, int64_t n, void* ws, int64_t ws_bytes, int64_t* out, int64_t* n_out,
+                            cqlrec_stream stream);
+int64_t cqlrec_prepare_sort_labels_ws_bytes(int64_t m);
+int cqlrec_prepare_sort_labels(const int64_t* labels, int64_t m, void* ws, int64_t ws_bytes, int64_t* sorted,
+                               int32_t* sorted_idx, cqlrec_stream stream);
+int cqlrec_prepare_lookup(const int64_t* ids, int64_t n_rows, const int64_t* sorted, const int32_t* sorted_idx, int64_t m,
+                          int32_t* out, int32_t* miss, cqlrec_stream stream);
+int cqlrec_prepare_gather(const int64_t* idx, int64_t n_rows, const int64_t* labels, int64_t m, int64_t* out,
+                          int32_t* bad, cqlrec_stream stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * Measurement hooks (bench.py): when enabled, every launcher brackets its kernel with a pair of HIP events on
  * the stream it launches on; cqlrec_prof_read synchronises those events and returns, per phase, the summed
  * kernel time in ms and the number of launches, then resets the pool.  Not capturable in a hipGraph; off by

@@ -4,14 +4,23 @@ Only what the path needs: csrc/ (HIP kernels + C ABI, built into libcqlrec.so), 
 core (device driver).  The HIP library is loaded lazily; nothing here falls back to a CPU implementation."""
 __version__ = "0.1.0"
 
-# the train/test splitters (splitters.py), importable from the package without loading torch until they are asked for
+# the train/test splitters (splitters.py), the filters (filters.py) and the Indexer (indexer.py), importable from the
+# package without loading torch until they are asked for
 _SPLITTERS = ("Splitter", "UserSplitter", "DateSplitter", "RandomSplitter", "NewUsersSplitter", "ColdUserRandomSplitter",
               "k_folds")
-__all__ = list(_SPLITTERS)
+_FILTERS = ("filter_by_min_count", "filter_out_low_ratings", "take_num_user_interactions", "take_num_days_of_user_hist",
+            "take_time_period", "take_num_days_of_global_hist")
+__all__ = list(_SPLITTERS) + list(_FILTERS) + ["Indexer"]
 
 
 def __getattr__(name):
     if name in _SPLITTERS:
         from . import splitters          # pylint: disable=import-outside-toplevel
         return getattr(splitters, name)
+    if name in _FILTERS:
+        from . import filters            # pylint: disable=import-outside-toplevel
+        return getattr(filters, name)
+    if name == "Indexer":
+        from . import indexer            # pylint: disable=import-outside-toplevel
+        return indexer.Indexer
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -152,6 +152,19 @@ SIGNATURES = {
     "cqlrec_split_filter_test": (i32, [vp, vp, vp, vp, i64, i64, i64, i32, i32, i32, vp, i64, vp, vp]),
     "cqlrec_split_compact_ws_bytes": (i64, [i64]),
     "cqlrec_split_compact": (i32, [vp, vp, i64, vp, i64, vp, vp, vp, vp]),
+    "cqlrec_prepare_rank_ws_bytes": (i64, [i64, i64]),
+    "cqlrec_prepare_rank": (i32, [vp, vp, vp, i64, i64, i64, vp, i64, vp, vp, vp]),
+    "cqlrec_prepare_count": (i32, [vp, i64, i64, vp, vp]),
+    "cqlrec_prepare_minmax": (i32, [vp, vp, i64, i64, vp, vp, vp]),
+    "cqlrec_prepare_keep": (i32, [i32, vp, vp, vp, vp, vp, vp, i64, i64, i32, i32, i64, i64, i32, f64, vp, vp]),
+    "cqlrec_prepare_compact_ws_bytes": (i64, [i64]),
+    "cqlrec_prepare_compact": (i32, [vp, i64, vp, i64, vp, vp, vp]),
+    "cqlrec_prepare_distinct_ws_bytes": (i64, [i64]),
+    "cqlrec_prepare_distinct": (i32, [vp, i64, vp, i64, vp, vp, vp]),
+    "cqlrec_prepare_sort_labels_ws_bytes": (i64, [i64]),
+    "cqlrec_prepare_sort_labels": (i32, [vp, i64, vp, i64, vp, vp, vp]),
+    "cqlrec_prepare_lookup": (i32, [vp, i64, vp, vp, i64, vp, vp, vp]),
+    "cqlrec_prepare_gather": (i32, [vp, i64, vp, i64, vp, vp, vp]),
     "cqlrec_prof_enable": (i32, [i32]),
     "cqlrec_prof_select": (i32, [C.c_uint32]),
     "cqlrec_debug_marks_enable": (i32, [i32]),
