@@ -661,6 +661,103 @@ int cqlrec_prepare_gather(const int64_t* idx, int64_t n_rows, const int64_t* lab
                           int32_t* bad, cqlrec_stream stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * f7  History-based features on the device (replay/history_based_fp.py): what LogStatFeaturesProcessor and
+ * ConditionalPopularityProcessor compute with group-bys and joins is sorted segments, fixed-order fp64 sums, binary
+ * searches and one fused gather here.  The rules of f5 / f6 carry over: integer atomics only, no floating-point
+ * atomics, the same input gives the same bytes; ids are dense non-negative ids below n_groups which the CALLER
+ * range-checks; n_rows < 2^31; arguments are validated on the host before any HIP call.
+ *
+ * A floating-point sum over a segment is formed in an order fixed by position: pieces of 1024 consecutive sorted rows
+ * counted from the segment's first row, each summed by one wave (lane l takes rows l, l + 64, ..., then a butterfly
+ * over the lanes), and the pieces of a group summed by one wave the same way.  Work per thread is bounded whatever
+ * the group sizes are.
+ * --------------------------------------------------------------------------------------------------------- */
+/* day [n] = floor(key / unit) (floor division: keys before 1970 work), unit > 0. */
+int cqlrec_features_day(const int64_t* key, int64_t n, int64_t unit, int64_t* day, cqlrec_stream stream);
+
+/* perm [n_rows] = the rows ordered by (group, key, input row index) ascending; offsets [n_groups + 1] = the first
+ * sorted position of every group (offsets[n_groups] = n_rows).  key == NULL: by (group, input row index).  Stable LSD
+ * radix sorts: key, then group.  n_rows == 0: offsets = 0. */
+int64_t cqlrec_features_segments_ws_bytes(int64_t n_rows, int64_t n_groups);
+int cqlrec_features_segments(const int32_t* group, const int64_t* key, int64_t n_rows, int64_t n_groups, void* ws,
+                             int64_t ws_bytes, int32_t* perm, int64_t* offsets, cqlrec_stream stream);
+
+/* out [n_groups][CQLREC_FEATURES_STATS] = count, mean, sample std (n - 1; 0 for a group of one row), and the elements
+ * of the group's rows at the 1-based ranks clamp(ceil(p * n), 1, n) for p = 0.05, 0.5, 0.95 -- quantiles when perm
+ * orders every group by value ascending (cqlrec_features_segments with the order-preserving key of the value).  The
+ * variance is two-pass: the mean first, then the squared deviations around it.  A group without rows gets zeros. */
+#define CQLREC_FEATURES_STATS 6
+int64_t cqlrec_features_segment_stats_ws_bytes(int64_t n_rows, int64_t n_groups);
+int cqlrec_features_segment_stats(const int32_t* perm, const int64_t* offsets, const double* value, int64_t n_rows,
+                                  int64_t n_groups, void* ws, int64_t ws_bytes, double* out, cqlrec_stream stream);
+
+/* out [n_groups] = the mean over the group's rows of an expression of the row (0 for a group without rows), over any
+ * ordering by group.  o = other[row] * tab_stride:
+ *   GATHER          tab_a[o]
+ *   ABNORMALITY     |value - tab_a[o]|
+ *   ABNORMALITY_CR  (|value - tab_a[o]| * (1 - (tab_b[o] - min_std) / (max_std - min_std)))^2, min_std < max_std */
+#define CQLREC_FEATURES_MEAN_GATHER 0
+#define CQLREC_FEATURES_MEAN_ABNORMALITY 1
+#define CQLREC_FEATURES_MEAN_ABNORMALITY_CR 2
+int64_t cqlrec_features_segment_mean_ws_bytes(int64_t n_rows, int64_t n_groups);
+int cqlrec_features_segment_mean(int32_t rule, const int32_t* perm, const int64_t* offsets, const double* value,
+                                 const int32_t* other, const double* tab_a, const double* tab_b, int64_t tab_stride,
+                                 double min_std, double max_std, int64_t n_rows, int64_t n_groups, void* ws,
+                                 int64_t ws_bytes, double* out, cqlrec_stream stream);
+
+/* out [n_groups] = the number of distinct keys among the group's rows, over an ordering by (group, key): the heads of
+ * the runs are counted (integer atomicAdd). */
+int cqlrec_features_segment_distinct(const int32_t* group, const int32_t* perm, const int64_t* offsets, const int64_t* key,
+                                     int64_t n_rows, int64_t n_groups, int32_t* out, cqlrec_stream stream);
+
+/* Conditional popularity.  The composite key of a row is entity * (n_cat + 1) + code[other], code [ids of the other
+ * entity] in [0, n_cat] with n_cat = the null category.  keys [n_rows] receives the distinct keys ascending, pop
+ * [n_rows] the rows with that key divided by entity_count[entity], *n_out (device) how many.  n_rows == 0: *n_out = 0. */
+int64_t cqlrec_features_pair_counts_ws_bytes(int64_t n_rows);
+int cqlrec_features_pair_counts(const int32_t* entity, const int32_t* other, const int32_t* code,
+                                const int32_t* entity_count, int64_t n_rows, int64_t n_entity, int64_t n_cat, void* ws,
+                                int64_t ws_bytes, int64_t* keys, double* pop, int64_t* entity_off, int64_t* n_out,
+                                cqlrec_stream stream);
+
+/* One fitted popularity table as the block kernel reads it (device pointers).  The category of a pair comes from
+ * pair_code [n_pairs] when given, otherwise from code [n_code] indexed by the other entity's id (an id beyond it has
+ * the null category).  A category outside [0, n_cat) -- null or unseen -- and a key that is not in keys [m] are `na`.  The search
+ * for a key runs over the entity's own keys, keys[entity_off[e] .. entity_off[e + 1]): at most n_cat + 1 of them. */
+typedef struct cqlrec_features_pop {
+  const int32_t* code;
+  const int32_t* pair_code;
+  const int64_t* keys;
+  const double* pop;
+  const int64_t* entity_off;
+  int64_t n_code, n_entity, n_cat, m;
+  int32_t entity_is_item, reserved;
+} cqlrec_features_pop;
+
+/* block [n_pairs][n_cols], row-major float or double, written once by one launch.  colmap (HOST) [n_cols][3] =
+ * (kind, a, b); a cold id -- outside the table, or with count 0 -- reads 0 from its table:
+ *   COL_USER / COL_ITEM        column a of utab [n_users][fu] / itab [n_items][fi]
+ *   COL_NA_USER / COL_NA_ITEM  1 for a cold id, else 0
+ *   COL_DIFF_USER              user column a - item column b, after the zero fill;  COL_DIFF_ITEM: item a - user b
+ *   COL_POP / COL_POP_NA       the popularity of table a (0 where na) / 1 where na, else 0 */
+#define CQLREC_FEATURES_MAX_COLS 64
+#define CQLREC_FEATURES_MAX_POP 8
+#define CQLREC_FEATURES_F32 0
+#define CQLREC_FEATURES_F64 1
+#define CQLREC_FEATURES_COL_USER 0
+#define CQLREC_FEATURES_COL_ITEM 1
+#define CQLREC_FEATURES_COL_NA_USER 2
+#define CQLREC_FEATURES_COL_NA_ITEM 3
+#define CQLREC_FEATURES_COL_DIFF_USER 4
+#define CQLREC_FEATURES_COL_DIFF_ITEM 5
+#define CQLREC_FEATURES_COL_POP 6
+#define CQLREC_FEATURES_COL_POP_NA 7
+int cqlrec_features_block(const int64_t* user_idx, const int64_t* item_idx, int64_t n_pairs, const double* utab,
+                          const int32_t* ucount, int64_t n_users, int32_t fu, const double* itab, const int32_t* icount,
+                          int64_t n_items, int32_t fi, const int32_t* colmap, int32_t n_cols,
+                          const cqlrec_features_pop* pops, int32_t n_pop, int32_t dtype, void* block,
+                          cqlrec_stream stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * Measurement hooks (bench.py): when enabled, every launcher brackets its kernel with a pair of HIP events on
  * the stream it launches on; cqlrec_prof_read synchronises those events and returns, per phase, the summed
  * kernel time in ms and the number of launches, then resets the pool.  Not capturable in a hipGraph; off by

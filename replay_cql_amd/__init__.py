@@ -4,13 +4,16 @@ Only what the path needs: csrc/ (HIP kernels + C ABI, built into libcqlrec.so), 
 core (device driver).  The HIP library is loaded lazily; nothing here falls back to a CPU implementation."""
 __version__ = "0.1.0"
 
-# the train/test splitters (splitters.py), the filters (filters.py) and the Indexer (indexer.py), importable from the
+# the train/test splitters (splitters.py), the filters (filters.py), the Indexer (indexer.py) and the history-based
+# feature processors (history_based_fp.py), importable from the
 # package without loading torch until they are asked for
 _SPLITTERS = ("Splitter", "UserSplitter", "DateSplitter", "RandomSplitter", "NewUsersSplitter", "ColdUserRandomSplitter",
               "k_folds")
 _FILTERS = ("filter_by_min_count", "filter_out_low_ratings", "take_num_user_interactions", "take_num_days_of_user_hist",
             "take_time_period", "take_num_days_of_global_hist")
-__all__ = list(_SPLITTERS) + list(_FILTERS) + ["Indexer"]
+_FEATURES = ("EmptyFeatureProcessor", "LogStatFeaturesProcessor", "ConditionalPopularityProcessor",
+             "HistoryBasedFeaturesProcessor")
+__all__ = list(_SPLITTERS) + list(_FILTERS) + ["Indexer"] + list(_FEATURES)
 
 
 def __getattr__(name):
@@ -20,6 +23,9 @@ def __getattr__(name):
     if name in _FILTERS:
         from . import filters            # pylint: disable=import-outside-toplevel
         return getattr(filters, name)
+    if name in _FEATURES:
+        from . import history_based_fp   # pylint: disable=import-outside-toplevel
+        return getattr(history_based_fp, name)
     if name == "Indexer":
         from . import indexer            # pylint: disable=import-outside-toplevel
         return indexer.Indexer

@@ -70,6 +70,17 @@ class TrainViews(C.Structure):
         "hb_s", "hb_sn", "hb_tn")]
 
 
+class FeaturesPop(C.Structure):
+    """cqlrec_features_pop: one fitted conditional-popularity table as cqlrec_features_block reads it"""
+    _fields_ = [("code", vp), ("pair_code", vp), ("keys", vp), ("pop", vp), ("entity_off", vp), ("n_code", i64), ("n_entity", i64),
+                ("n_cat", i64), ("m", i64), ("entity_is_item", i32), ("reserved", i32)]
+
+
+FEATURES_STATS, FEATURES_MAX_COLS, FEATURES_MAX_POP = 6, 64, 8
+FEAT_MEAN_GATHER, FEAT_MEAN_ABNORMALITY, FEAT_MEAN_ABNORMALITY_CR = 0, 1, 2
+(FEAT_COL_USER, FEAT_COL_ITEM, FEAT_COL_NA_USER, FEAT_COL_NA_ITEM, FEAT_COL_DIFF_USER, FEAT_COL_DIFF_ITEM, FEAT_COL_POP,
+ FEAT_COL_POP_NA) = range(8)
+
 # name -> (restype, argtypes); every symbol include/cqlrec.h declares
 SIGNATURES = {
     "cqlrec_abi_version": (i32, []),
@@ -165,6 +176,18 @@ SIGNATURES = {
     "cqlrec_prepare_sort_labels": (i32, [vp, i64, vp, i64, vp, vp, vp]),
     "cqlrec_prepare_lookup": (i32, [vp, i64, vp, vp, i64, vp, vp, vp]),
     "cqlrec_prepare_gather": (i32, [vp, i64, vp, i64, vp, vp, vp]),
+    "cqlrec_features_day": (i32, [vp, i64, i64, vp, vp]),
+    "cqlrec_features_segments_ws_bytes": (i64, [i64, i64]),
+    "cqlrec_features_segments": (i32, [vp, vp, i64, i64, vp, i64, vp, vp, vp]),
+    "cqlrec_features_segment_stats_ws_bytes": (i64, [i64, i64]),
+    "cqlrec_features_segment_stats": (i32, [vp, vp, vp, i64, i64, vp, i64, vp, vp]),
+    "cqlrec_features_segment_mean_ws_bytes": (i64, [i64, i64]),
+    "cqlrec_features_segment_mean": (i32, [i32, vp, vp, vp, vp, vp, vp, i64, f64, f64, i64, i64, vp, i64, vp, vp]),
+    "cqlrec_features_segment_distinct": (i32, [vp, vp, vp, vp, i64, i64, vp, vp]),
+    "cqlrec_features_pair_counts_ws_bytes": (i64, [i64]),
+    "cqlrec_features_pair_counts": (i32, [vp, vp, vp, vp, i64, i64, i64, vp, i64, vp, vp, vp, vp, vp]),
+    "cqlrec_features_block": (i32, [vp, vp, i64, vp, vp, i64, i32, vp, vp, i64, i32, C.POINTER(i32), i32,
+                                    C.POINTER(FeaturesPop), i32, i32, vp, vp]),
     "cqlrec_prof_enable": (i32, [i32]),
     "cqlrec_prof_select": (i32, [C.c_uint32]),
     "cqlrec_debug_marks_enable": (i32, [i32]),

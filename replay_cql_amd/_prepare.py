@@ -191,3 +191,96 @@ class Prep:
         self.N.check(self.lib.cqlrec_prepare_gather(idx.data_ptr(), idx.numel(), labels.data_ptr(), labels.numel(),
                                                     out.data_ptr(), bad.data_ptr(), self.stream), "prepare_gather")
         return out, bool(bad.item())
+
+
+class Feat(Prep):
+    """The calls into csrc/features.hip (section f7 of include/cqlrec.h) on one device."""
+
+    def day(self, key, unit: int):
+        out = self._empty(key.numel(), torch.int64)
+        self.N.check(self.lib.cqlrec_features_day(key.data_ptr(), key.numel(), int(unit), out.data_ptr(), self.stream),
+                     "features_day")
+        return out
+
+    def segments(self, group, n_groups: int, key=None):
+        """(perm int32[n], offsets int64[n_groups + 1]) of the rows ordered by (group, key, row) ascending"""
+        n = group.numel()
+        perm, offsets = self._empty(n, torch.int32), self._empty(n_groups + 1, torch.int64)
+        nb = int(self.lib.cqlrec_features_segments_ws_bytes(n, n_groups))
+        ws = self._ws(nb)
+        self.N.check(self.lib.cqlrec_features_segments(group.data_ptr(), self._p(key), n, n_groups, ws.data_ptr(), nb,
+                                                       perm.data_ptr(), offsets.data_ptr(), self.stream),
+                     "features_segments")
+        return perm, offsets
+
+    def segment_stats(self, perm, offsets, value, n_groups: int):
+        """float64 [n_groups, 6]: count, mean, std, quantile_05, quantile_5, quantile_95"""
+        n = perm.numel()
+        out = torch.empty((n_groups, self.N.FEATURES_STATS), dtype=torch.float64, device=self.dev)
+        nb = int(self.lib.cqlrec_features_segment_stats_ws_bytes(n, n_groups))
+        ws = self._ws(nb)
+        self.N.check(self.lib.cqlrec_features_segment_stats(perm.data_ptr(), offsets.data_ptr(), value.data_ptr(), n,
+                                                            n_groups, ws.data_ptr(), nb, out.data_ptr(), self.stream),
+                     "features_segment_stats")
+        return out
+
+    def segment_mean(self, rule: int, perm, offsets, n_groups: int, other, tab_a, tab_b=None, value=None,
+                     min_std: float = 0.0, max_std: float = 0.0):
+        """float64 [n_groups]: the mean over the group's rows; tab_a / tab_b are columns of ONE row-major table"""
+        n = perm.numel()
+        out = self._empty(n_groups, torch.float64)
+        stride = int(tab_a.stride(0)) if tab_a.numel() else 1
+        if tab_b is not None and tab_b.numel() and int(tab_b.stride(0)) != stride:
+            raise ValueError("tab_a and tab_b differ in stride")
+        nb = int(self.lib.cqlrec_features_segment_mean_ws_bytes(n, n_groups))
+        ws = self._ws(nb)
+        self.N.check(self.lib.cqlrec_features_segment_mean(rule, perm.data_ptr(), offsets.data_ptr(), self._p(value),
+                                                           other.data_ptr(), tab_a.data_ptr(), self._p(tab_b), stride,
+                                                           float(min_std), float(max_std), n, n_groups, ws.data_ptr(), nb,
+                                                           out.data_ptr(), self.stream), "features_segment_mean")
+        return out
+
+    def segment_distinct(self, group, perm, offsets, key, n_groups: int):
+        out = self._empty(n_groups, torch.int32)
+        self.N.check(self.lib.cqlrec_features_segment_distinct(group.data_ptr(), perm.data_ptr(), offsets.data_ptr(),
+                                                               key.data_ptr(), perm.numel(), n_groups, out.data_ptr(),
+                                                               self.stream), "features_segment_distinct")
+        return out
+
+    def pair_counts(self, entity, other, code, entity_count, n_entity: int, n_cat: int):
+        """(sorted distinct keys int64[m], popularity float64[m], first key of every entity int64[n_entity + 1])"""
+        n = entity.numel()
+        keys, pop, m = self._empty(n, torch.int64), self._empty(n, torch.float64), self._empty(1, torch.int64)
+        off = self._empty(n_entity + 1, torch.int64)
+        nb = int(self.lib.cqlrec_features_pair_counts_ws_bytes(n))
+        ws = self._ws(nb)
+        self.N.check(self.lib.cqlrec_features_pair_counts(entity.data_ptr(), other.data_ptr(), code.data_ptr(),
+                                                          entity_count.data_ptr(), n, n_entity, n_cat, ws.data_ptr(), nb,
+                                                          keys.data_ptr(), pop.data_ptr(), off.data_ptr(), m.data_ptr(),
+                                                          self.stream), "features_pair_counts")
+        m = int(m.item())
+        return keys[:m].clone(), pop[:m].clone(), off
+
+    def block(self, user, item, utab, ucount, itab, icount, colmap, pops, dtype):
+        """[n_pairs, len(colmap)] of `dtype` in one launch.  utab / itab: float64 [n, f] or None; colmap: (kind, a, b)
+        triples; pops: dicts with code, pair_code, keys, pop, entity_off, n_entity, n_cat, entity_is_item."""
+        import ctypes as C
+        N = self.N
+        n, f = user.numel(), len(colmap)
+        if not 0 < f <= N.FEATURES_MAX_COLS or len(pops) > N.FEATURES_MAX_POP:
+            raise ValueError(f"a feature block takes 1..{N.FEATURES_MAX_COLS} columns and at most {N.FEATURES_MAX_POP} "
+                             f"conditional-popularity tables, not {f} and {len(pops)}")
+        out = torch.empty((n, f), dtype=dtype, device=self.dev)
+        cm = (C.c_int32 * (3 * f))(*[int(x) for t in colmap for x in t])
+        ps = (N.FeaturesPop * max(1, len(pops)))()
+        for q, d in enumerate(pops):
+            ps[q] = N.FeaturesPop(self._p(d["code"]), self._p(d.get("pair_code")), self._p(d["keys"]), self._p(d["pop"]),
+                                  self._p(d["entity_off"]), d["code"].numel(), int(d["n_entity"]), int(d["n_cat"]), d["keys"].numel(),
+                                  int(d["entity_is_item"]), 0)
+        nu, fu = (0, 0) if utab is None else utab.shape
+        ni, fi = (0, 0) if itab is None else itab.shape
+        N.check(self.lib.cqlrec_features_block(user.data_ptr(), item.data_ptr(), n, self._p(utab), self._p(ucount), int(nu),
+                                               int(fu), self._p(itab), self._p(icount), int(ni), int(fi), cm, f, ps,
+                                               len(pops), 0 if dtype == torch.float32 else 1, out.data_ptr(), self.stream),
+                "features_block")
+        return out
