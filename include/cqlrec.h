@@ -758,6 +758,79 @@ int cqlrec_features_block(const int64_t* user_idx, const int64_t* item_idx, int6
                           cqlrec_stream stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * f8  Neighbourhood models on the device (replay/models/knn.py, NeighbourRec of replay/models/base_rec.py): the row-wise
+ * top-k of a sparse x sparse product, so that the n x n similarity matrix is never formed, and the small kernels around
+ * it.  ItemKNN.fit (C = A^T A, the k best per row) and NeighbourRec.predict (R = B S, the k best unseen per row) are the
+ * same operation with two epilogues.  The rules of f5 - f7 carry over: integer atomics only, no floating-point atomics,
+ * the same input gives the same bytes; ids are dense non-negative ids which the CALLER range-checks; arguments are
+ * validated on the host before any HIP call.  Both matrices are CSR: int64 offsets, int32 column ids, fp64 values.
+ *
+ * Shape: expand, sort, reduce, select.  Query rows are taken in chunks of consecutive rows whose expansion -- the
+ * number of (L entry, R entry) combinations -- fits max_tuples (a larger row is a chunk of its own).  One thread per
+ * tuple finds its L entry by binary search in the entry prefix and writes the key (local row, j) and the product; a
+ * stable radix sort over the bits the key uses brings the terms of one (row, j) together in (L entry, R entry) order;
+ * a sum of up to 32 terms is added left to right by one thread, a longer one by one wave (lane l takes the terms
+ * l, l + 64, ... in that order, then a butterfly over the lanes): the order is fixed by the position inside the sum, so
+ * the result does not depend on max_tuples, bit for bit.  The k best of a row come out of two more stable sorts (the
+ * order-preserving image of the fp64 value, then the row).  No buffer of n_q x n_cols elements exists.
+ * --------------------------------------------------------------------------------------------------------- */
+#define CQLREC_NEIGHBOUR_FIT 0
+#define CQLREC_NEIGHBOUR_PREDICT 1
+#define CQLREC_NEIGHBOUR_MAX_K 1024
+#define CQLREC_NEIGHBOUR_WEIGHT_NONE 0
+#define CQLREC_NEIGHBOUR_WEIGHT_TF_IDF 1
+#define CQLREC_NEIGHBOUR_WEIGHT_BM25 2
+
+/* w [n_rows]: the weight of a log row (knn.py:76-154).  rel = relevance[row], or 1 when relevance is NULL.
+ *   NONE    rel
+ *   TF_IDF  rel * log1p(n_items / ucount[user])
+ *   BM25    (rel * (k1 + 1) / (rel + k1 * (1 - b + b * (icount[item] / avgdl)))) * log1p((n_items - DF + 0.5) / (DF + 0.5)),
+ *           DF = ucount[user], avgdl = n_rows / n_items (one fp64 division)
+ * n_items is the number of DISTINCT items of the log; every expression is evaluated in fp64 exactly as written. */
+int cqlrec_neighbour_weights(const int32_t* user_idx, const int32_t* item_idx, const double* relevance,
+                             const int32_t* ucount, const int32_t* icount, int64_t n_rows, int64_t n_items,
+                             int32_t weighting, double k1, double b, double* w, cqlrec_stream stream);
+
+/* norm [n_groups] = sqrt(sum of w[row]^2 over the group's rows), over an ordering by group (cqlrec_features_segments);
+ * one wave per group sums in an order fixed by position.  A group without rows gets 0. */
+int cqlrec_neighbour_norms(const int32_t* perm, const int64_t* offsets, const double* w, int64_t n_rows, int64_t n_groups,
+                           double* norm, cqlrec_stream stream);
+
+/* The count pass.  entry_prefix [nnz_l + 1]: the exclusive int64 prefix of the R row lengths of the L entries, the total
+ * at the end; row_prefix [n_q + 1] = entry_prefix[l_off[q]]; stats [2] (device) = the total expansion and the largest
+ * expansion of one row.  l_col holds ids below n_mid, r_off has n_mid + 1 entries. */
+int64_t cqlrec_neighbour_count_ws_bytes(int64_t nnz_l);
+int cqlrec_neighbour_count(const int64_t* l_off, const int32_t* l_col, int64_t n_q, int64_t nnz_l, const int64_t* r_off,
+                           int64_t n_mid, void* ws, int64_t ws_bytes, int64_t* entry_prefix, int64_t* row_prefix,
+                           int64_t* stats, cqlrec_stream stream);
+
+/* For every query row q: C[q][j] = sum of a * b over the L entries (m, a) of row q and the R entries (j, b) of row m,
+ * then the k best j.  ids [n_q][k] (padded with -1), vals [n_q][k] (padded with 0), count [n_q].  A j that no
+ * combination reaches is never a candidate; a reached j whose sum is 0 is one.
+ *   FIT      drops j == q; value = C / (norm_q[q] * norm_j[j] + shrink); drops a pair whose denominator is 0;
+ *            order: value descending, j DESCENDING (knn.py:214-217)
+ *   PREDICT  value = C; drops j with mask[j] == 0 (mask: NULL or one byte per column); drops j found in the ascending
+ *            list seen_col[seen_off[q] .. seen_off[q + 1]) (NULL: none); order: value descending, j ASCENDING
+ * row_prefix_host: the row prefix of the count pass, copied to the HOST (the chunks are cut there).  The workspace
+ * holds max(max_tuples, largest_row) tuples; 1 <= k <= CQLREC_NEIGHBOUR_MAX_K; the result does not depend on
+ * max_tuples.  No synchronisation. */
+int64_t cqlrec_neighbour_topk_ws_bytes(int64_t n_q, int64_t n_cols, int64_t max_tuples, int64_t largest_row, int32_t k);
+int cqlrec_neighbour_topk(int32_t mode, const int64_t* l_off, const int32_t* l_col, const double* l_val, int64_t n_q,
+                          int64_t nnz_l, const int64_t* r_off, const int32_t* r_col, const double* r_val, int64_t n_mid,
+                          int64_t n_cols, const int64_t* entry_prefix, const int64_t* row_prefix_host, int64_t max_tuples,
+                          int64_t largest_row, int32_t k, const double* norm_q, const double* norm_j, double shrink,
+                          const uint8_t* mask, const int64_t* seen_off, const int32_t* seen_col, void* ws,
+                          int64_t ws_bytes, int32_t* ids, double* vals, int32_t* count, cqlrec_stream stream);
+
+/* score [n_pairs] = sum over the history rows i of pair_user (h_item[h_off[u] .. h_off[u + 1]), in that order) of
+ * S[i -> pair_item], S a CSR whose rows are sorted by column ascending (binary search); present [n_pairs] = 1 when at
+ * least one i contributes.  A user beyond n_users or a history item beyond n_s_rows contributes nothing. */
+int cqlrec_neighbour_pair_scores(const int32_t* pair_user, const int32_t* pair_item, int64_t n_pairs, const int64_t* h_off,
+                                 const int32_t* h_item, int64_t n_users, const int64_t* s_off, const int32_t* s_col,
+                                 const double* s_val, int64_t n_s_rows, double* score, uint8_t* present,
+                                 cqlrec_stream stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * Measurement hooks (bench.py): when enabled, every launcher brackets its kernel with a pair of HIP events on
  * the stream it launches on; cqlrec_prof_read synchronises those events and returns, per phase, the summed
  * kernel time in ms and the number of launches, then resets the pool.  Not capturable in a hipGraph; off by

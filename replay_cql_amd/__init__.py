@@ -5,7 +5,7 @@ core (device driver).  The HIP library is loaded lazily; nothing here falls back
 __version__ = "0.1.0"
 
 # the train/test splitters (splitters.py), the filters (filters.py), the Indexer (indexer.py) and the history-based
-# feature processors (history_based_fp.py), importable from the
+# feature processors (history_based_fp.py) and the neighbourhood models (neighbour.py), importable from the
 # package without loading torch until they are asked for
 _SPLITTERS = ("Splitter", "UserSplitter", "DateSplitter", "RandomSplitter", "NewUsersSplitter", "ColdUserRandomSplitter",
               "k_folds")
@@ -13,7 +13,8 @@ _FILTERS = ("filter_by_min_count", "filter_out_low_ratings", "take_num_user_inte
             "take_time_period", "take_num_days_of_global_hist")
 _FEATURES = ("EmptyFeatureProcessor", "LogStatFeaturesProcessor", "ConditionalPopularityProcessor",
              "HistoryBasedFeaturesProcessor")
-__all__ = list(_SPLITTERS) + list(_FILTERS) + ["Indexer"] + list(_FEATURES)
+_NEIGHBOUR = ("NeighbourRec", "ItemKNN")
+__all__ = list(_SPLITTERS) + list(_FILTERS) + ["Indexer"] + list(_FEATURES) + list(_NEIGHBOUR)
 
 
 def __getattr__(name):
@@ -26,6 +27,9 @@ def __getattr__(name):
     if name in _FEATURES:
         from . import history_based_fp   # pylint: disable=import-outside-toplevel
         return getattr(history_based_fp, name)
+    if name in _NEIGHBOUR:
+        from . import neighbour          # pylint: disable=import-outside-toplevel
+        return getattr(neighbour, name)
     if name == "Indexer":
         from . import indexer            # pylint: disable=import-outside-toplevel
         return indexer.Indexer

@@ -81,6 +81,10 @@ FEAT_MEAN_GATHER, FEAT_MEAN_ABNORMALITY, FEAT_MEAN_ABNORMALITY_CR = 0, 1, 2
 (FEAT_COL_USER, FEAT_COL_ITEM, FEAT_COL_NA_USER, FEAT_COL_NA_ITEM, FEAT_COL_DIFF_USER, FEAT_COL_DIFF_ITEM, FEAT_COL_POP,
  FEAT_COL_POP_NA) = range(8)
 
+NEIGHBOUR_FIT, NEIGHBOUR_PREDICT = 0, 1
+NEIGHBOUR_MAX_K = 1024
+NEIGHBOUR_WEIGHTINGS = {None: 0, "tf_idf": 1, "bm25": 2}
+
 # name -> (restype, argtypes); every symbol include/cqlrec.h declares
 SIGNATURES = {
     "cqlrec_abi_version": (i32, []),
@@ -188,6 +192,14 @@ SIGNATURES = {
     "cqlrec_features_pair_counts": (i32, [vp, vp, vp, vp, i64, i64, i64, vp, i64, vp, vp, vp, vp, vp]),
     "cqlrec_features_block": (i32, [vp, vp, i64, vp, vp, i64, i32, vp, vp, i64, i32, C.POINTER(i32), i32,
                                     C.POINTER(FeaturesPop), i32, i32, vp, vp]),
+    "cqlrec_neighbour_weights": (i32, [vp, vp, vp, vp, vp, i64, i64, i32, f64, f64, vp, vp]),
+    "cqlrec_neighbour_norms": (i32, [vp, vp, vp, i64, i64, vp, vp]),
+    "cqlrec_neighbour_count_ws_bytes": (i64, [i64]),
+    "cqlrec_neighbour_count": (i32, [vp, vp, i64, i64, vp, i64, vp, i64, vp, vp, vp, vp]),
+    "cqlrec_neighbour_topk_ws_bytes": (i64, [i64, i64, i64, i64, i32]),
+    "cqlrec_neighbour_topk": (i32, [i32, vp, vp, vp, i64, i64, vp, vp, vp, i64, i64, vp, vp, i64, i64, i32, vp, vp, f64, vp,
+                                    vp, vp, vp, i64, vp, vp, vp, vp]),
+    "cqlrec_neighbour_pair_scores": (i32, [vp, vp, i64, vp, vp, i64, vp, vp, vp, i64, vp, vp, vp]),
     "cqlrec_prof_enable": (i32, [i32]),
     "cqlrec_prof_select": (i32, [C.c_uint32]),
     "cqlrec_debug_marks_enable": (i32, [i32]),

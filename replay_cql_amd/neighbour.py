@@ -1,0 +1,360 @@
+"""Neighbourhood models on the device: `NeighbourRec` (replay/models/base_rec.py:1433-1609) and `ItemKNN`
+(replay/models/knn.py) over csrc/neighbour.hip (section f8 of include/cqlrec.h).
+
+`fit` is C = A^T A with the k best per row and `predict` is R = B S with the k best unseen per row: one engine -- the
+row-wise top-k of a sparse x sparse product -- with two epilogues, so the n_items x n_items matrix is never formed.  The
+two CSR views of the log come from cqlrec_features_segments: rows by (user, item, row) and rows by (item, user, row);
+duplicated (user, item) rows stay separate entries, as the reference's self-join keeps them.
+
+Deviations from the reference, both stated in DESIGN.md section 3.9: a pair whose denominator norm * norm + shrink is 0
+is dropped (the reference divides by zero), and predict breaks ties by item_idx ascending (the reference leaves them to
+Spark; get_top_k_recs of this package uses the same rule).
+
+Nothing here has a CPU path: without a GPU every call that computes raises CqlrecError."""
+from __future__ import annotations
+
+from typing import Any, Dict, Optional
+
+import numpy as np
+import pandas as pd
+import torch
+
+from . import _prepare as P
+from .recommender_api import REC_COLUMNS, PandasRecommender, to_pandas
+
+__all__ = ["NeighbourRec", "ItemKNN"]
+
+DEFAULT_MAX_TUPLES = 1 << 27          # about 12 GB of workspace: 88 bytes per tuple, see cqlrec_neighbour_topk_ws_bytes
+
+
+class Neigh(P.Feat):
+    """The calls into csrc/neighbour.hip on one device."""
+
+    def weights(self, user, item, relevance, ucount, icount, n_items: int, weighting, k1: float, b: float):
+        n = user.numel()
+        out = self._empty(n, torch.float64)
+        self.N.check(self.lib.cqlrec_neighbour_weights(user.data_ptr(), item.data_ptr(), self._p(relevance),
+                                                       ucount.data_ptr(), icount.data_ptr(), n, int(n_items),
+                                                       self.N.NEIGHBOUR_WEIGHTINGS[weighting], float(k1), float(b),
+                                                       out.data_ptr(), self.stream), "neighbour_weights")
+        return out
+
+    def norms(self, perm, offsets, w, n_groups: int):
+        out = self._empty(n_groups, torch.float64)
+        self.N.check(self.lib.cqlrec_neighbour_norms(perm.data_ptr(), offsets.data_ptr(), w.data_ptr(), perm.numel(),
+                                                     n_groups, out.data_ptr(), self.stream), "neighbour_norms")
+        return out
+
+    def topk(self, mode: int, L, R, n_mid: int, n_cols: int, k: int, max_tuples: int, norm_q=None, norm_j=None,
+             shrink: float = 0.0, mask=None, seen=None):
+        """(ids int32 [n_q, k] padded with -1, vals float64 [n_q, k], count int32 [n_q]) of the product of the CSR
+        matrices L and R = (offsets int64, columns int32, values float64); seen = (offsets, ascending columns) per row.
+        `self.expansion` = (total tuples, the largest row's) of the call."""
+        l_off, l_col, l_val = L
+        r_off, r_col, r_val = R
+        n_q, nnz = l_off.numel() - 1, l_col.numel()
+        ids = torch.empty((n_q, k), dtype=torch.int32, device=self.dev)
+        vals = torch.empty((n_q, k), dtype=torch.float64, device=self.dev)
+        count = self._empty(n_q, torch.int32)
+        self.expansion = (0, 0)
+        if n_q == 0:
+            return ids, vals, count
+        eprefix, rprefix, stats = self._empty(nnz + 1, torch.int64), self._empty(n_q + 1, torch.int64), self._empty(2, torch.int64)
+        nb = int(self.lib.cqlrec_neighbour_count_ws_bytes(nnz))
+        ws = self._ws(nb)
+        self.N.check(self.lib.cqlrec_neighbour_count(l_off.data_ptr(), self._p(l_col), n_q, nnz, r_off.data_ptr(), n_mid,
+                                                     ws.data_ptr(), nb, eprefix.data_ptr(), rprefix.data_ptr(),
+                                                     stats.data_ptr(), self.stream), "neighbour_count")
+        total, largest = stats.cpu().tolist()
+        host_prefix = rprefix.cpu()                      # the chunks are cut on the host: 8 (n_q + 1) bytes
+        self.expansion = (int(total), int(largest))
+        if int(max_tuples) < 1:
+            raise ValueError(f"max_tuples must be positive, got {max_tuples}")
+        max_tuples = max(1, min(int(max_tuples), int(total)))   # no workspace beyond the expansion; the result is the same
+        nb = int(self.lib.cqlrec_neighbour_topk_ws_bytes(n_q, n_cols, int(max_tuples), int(largest), int(k)))
+        if nb == 0:
+            raise ValueError(f"neighbour top-k: k={k} (1..{self.N.NEIGHBOUR_MAX_K}), max_tuples={max_tuples} or a row of "
+                             f"{largest} tuples (below 2^31) is out of range")
+        del ws
+        ws = self._ws(nb if total else 0)
+        s_off, s_col = seen if seen is not None else (None, None)
+        self.N.check(self.lib.cqlrec_neighbour_topk(
+            int(mode), l_off.data_ptr(), self._p(l_col), self._p(l_val), n_q, nnz, r_off.data_ptr(), self._p(r_col),
+            self._p(r_val), n_mid, n_cols, eprefix.data_ptr(), host_prefix.data_ptr(), int(max_tuples), int(largest), int(k),
+            self._p(norm_q), self._p(norm_j), float(shrink), self._p(mask), self._p(s_off), self._p(s_col),
+            ws.data_ptr() if total else None, nb, ids.data_ptr(), vals.data_ptr(), count.data_ptr(), self.stream),
+            "neighbour_topk")
+        return ids, vals, count
+
+    def pair_scores(self, pair_user, pair_item, h_off, h_item, n_users: int, S, n_s_rows: int):
+        """(score float64 [n_pairs], present uint8 [n_pairs]); S = a CSR whose rows are sorted by column"""
+        s_off, s_col, s_val = S
+        n = pair_user.numel()
+        score, present = self._empty(n, torch.float64), self._empty(n, torch.uint8)
+        self.N.check(self.lib.cqlrec_neighbour_pair_scores(pair_user.data_ptr(), pair_item.data_ptr(), n, h_off.data_ptr(),
+                                                           self._p(h_item), n_users, s_off.data_ptr(), self._p(s_col),
+                                                           self._p(s_val), n_s_rows, score.data_ptr(), present.data_ptr(),
+                                                           self.stream), "neighbour_pair_scores")
+        return score, present
+
+
+def _id_tensor(ids, device) -> Optional[torch.Tensor]:
+    """distinct non-negative ids as an int64 device tensor, in the order given"""
+    if ids is None:
+        return None
+    if torch.is_tensor(ids):
+        t = ids.to(device=device, dtype=torch.int64).flatten()
+    else:
+        if isinstance(ids, pd.DataFrame):
+            ids = ids.iloc[:, 0]
+        t = torch.as_tensor(np.asarray(pd.unique(pd.Series(ids)), dtype=np.int64), device=device)
+    return t[t >= 0]
+
+
+class NeighbourRec(PandasRecommender):
+    """Base of the models that hold an item-to-item similarity table and need the log at prediction time.
+
+    The score of (u, j) is the sum over the LOG ROWS (u, i) of S[i -> j]: duplicated rows count, the log's relevance does
+    not enter, only j among `items` and only the users in `users` are scored; users without rows and rows whose item
+    has no similarity row contribute nothing, so a user may get fewer than k rows, or none.
+
+    `_predict` returns at most k rows per user, already without the user's seen items when `filter_seen_items` is set.
+    The template's `_filter_seen` (the k + seen best, then an anti-join with the log) and `get_top_k_recs` (the k best by
+    relevance descending, item_idx ascending) then change nothing: the first finds no seen pair among at most k rows,
+    the second is handed at most k rows per user in exactly its own order."""
+
+    can_predict_item_to_item: bool = True
+    can_predict_cold_users: bool = True
+    can_change_metric: bool = False
+    item_to_item_metrics = ["similarity"]
+    _similarity_metric = "similarity"
+    max_tuples: int = DEFAULT_MAX_TUPLES
+
+    # -------------------------------------------------------------------------------- bookkeeping
+    @property
+    def _dataframes(self) -> Dict[str, Any]:
+        return {"similarity": self.similarity}
+
+    def _clear_cache(self) -> None:
+        """the reference unpersists its cached frame; here the derived copies of the device table are dropped"""
+        self.__dict__.pop("_similarity_frame", None)
+        self.__dict__.pop("_csr_cache", None)
+
+    @property
+    def similarity_metric(self):
+        return self._similarity_metric
+
+    @similarity_metric.setter
+    def similarity_metric(self, value):
+        if not self.can_change_metric:
+            raise ValueError("This class does not support changing similarity metrics")
+        if value not in self.item_to_item_metrics:
+            raise ValueError(f"Select one of the valid metrics for predict: {self.item_to_item_metrics}")
+        self._similarity_metric = value
+
+    # -------------------------------------------------------------------------------- the table
+    def _fitted(self):
+        if "_sim" not in self.__dict__:
+            raise RuntimeError(f"{self} model is not fitted")
+        return self._sim
+
+    @property
+    def similarity_device(self):
+        """(ids int32 [n_items, K] padded with -1, values float64 [n_items, K], counts int32 [n_items]) on the device;
+        row i holds the neighbours of item i, best first"""
+        return self._fitted()
+
+    @property
+    def similarity(self) -> pd.DataFrame:
+        """[item_idx_one, item_idx_two, similarity], by item_idx_one ascending, then rank"""
+        if "_similarity_frame" not in self.__dict__:
+            ids, vals, count = self._fitted()
+            keep = (torch.arange(ids.shape[1], device=ids.device)[None, :] < count[:, None]).cpu().numpy()
+            one = np.broadcast_to(np.arange(ids.shape[0], dtype=np.int32)[:, None], keep.shape)[keep]
+            self._similarity_frame = pd.DataFrame({"item_idx_one": one, "item_idx_two": ids.cpu().numpy()[keep],
+                                                   "similarity": vals.cpu().numpy()[keep]})
+        return self._similarity_frame
+
+    def _csr(self, n_rows: int):
+        """the table as CSR with n_rows >= n_items rows: (offsets, columns, values) in rank order, and sorted by column"""
+        cache = self.__dict__.setdefault("_csr_cache", {})
+        if n_rows not in cache:
+            ids, vals, count = self._fitted()
+            off = torch.zeros(n_rows + 1, dtype=torch.int64, device=ids.device)
+            off[1:ids.shape[0] + 1] = torch.cumsum(count.to(torch.int64), 0)
+            off[ids.shape[0] + 1:] = off[ids.shape[0]]
+            keep = torch.arange(ids.shape[1], device=ids.device)[None, :] < count[:, None]
+            col, val = ids[keep].contiguous(), vals[keep].contiguous()
+            row = torch.arange(ids.shape[0], device=ids.device, dtype=torch.int64)[:, None].expand_as(ids)[keep]
+            by_col = torch.argsort(row * max(1, ids.shape[0]) + col.to(torch.int64))
+            cache.clear()
+            cache[n_rows] = ((off, col, val), (off, col[by_col].contiguous(), val[by_col].contiguous()))
+        return cache[n_rows]
+
+    # -------------------------------------------------------------------------------- predict on the device
+    def _history(self, lg):
+        """(engine, users' CSR offsets, items of the rows ordered by (user, item, row), n_users, largest item + 1)"""
+        (user, n_users), (item, n_items) = P.dense_ids(lg, ["user_idx", "item_idx"])
+        eng = Neigh(lg.device)
+        perm, off = eng.segments(user, n_users, item.to(torch.int64))
+        return eng, off, item[perm.long()].contiguous(), n_users, n_items
+
+    def _recommend(self, log, k: int, users, items, filter_seen_items: bool):
+        """(users int64 [m], ids int32 [m, k], vals float64 [m, k], count int32 [m]) on the device"""
+        sim_ids = self._fitted()[0]
+        if log is None:
+            raise ValueError("log is not provided, but it is required for prediction")
+        lg = P.open_log(P.normalise(log), str(self))
+        dev, n_cols = lg.device, int(sim_ids.shape[0])
+        users, items = _id_tensor(users, dev), _id_tensor(items, dev)
+        if lg.n == 0:
+            users = users if users is not None else torch.empty(0, dtype=torch.int64, device=dev)
+            m = users.numel()
+            return (users, torch.full((m, k), -1, dtype=torch.int32, device=dev),
+                    torch.zeros((m, k), dtype=torch.float64, device=dev), torch.zeros(m, dtype=torch.int32, device=dev))
+        eng, off, h_item, n_users, n_log_items = self._history(lg)
+        lens_all = off[1:] - off[:-1]
+        if users is None:
+            users = torch.nonzero(lens_all > 0).flatten()
+        known = users < n_users
+        uc = torch.where(known, users, torch.zeros_like(users))
+        lens = torch.where(known, lens_all[uc], torch.zeros_like(uc))
+        l_off = torch.zeros(users.numel() + 1, dtype=torch.int64, device=dev)
+        l_off[1:] = torch.cumsum(lens, 0)
+        nnz = int(l_off[-1].item()) if users.numel() else 0
+        within = torch.arange(nnz, dtype=torch.int64, device=dev) - torch.repeat_interleave(l_off[:-1], lens)
+        l_col = h_item[torch.repeat_interleave(off[uc], lens) + within].contiguous()
+        l_val = torch.ones(nnz, dtype=torch.float64, device=dev)
+        n_mid = max(n_cols, n_log_items)
+        mask = None
+        if items is not None:
+            mask = torch.zeros(n_cols, dtype=torch.uint8, device=dev)
+            mask[items[items < n_cols]] = 1
+        seen = (l_off, l_col) if filter_seen_items else None
+        ids, vals, count = eng.topk(eng.N.NEIGHBOUR_PREDICT, (l_off, l_col, l_val), self._csr(n_mid)[0], n_mid, n_cols, int(k),
+                                    self.max_tuples, mask=mask, seen=seen)
+        self.expansion = eng.expansion
+        return users, ids, vals, count
+
+    def recommend(self, log, k: int, users=None, items=None, filter_seen_items: bool = True) -> Dict[str, torch.Tensor]:
+        """The k best items of every user as device columns {user_idx int32, item_idx int32, relevance float64}, in the
+        order of `users` (None: the users of the log, ascending), then rank.  `log`: pandas, pyarrow or a dict of device
+        tensors; `users` / `items`: tensors, iterables or None (every item that has a similarity row)."""
+        users, ids, vals, count = self._recommend(log, int(k), users, items, filter_seen_items)
+        keep = torch.arange(ids.shape[1], device=ids.device)[None, :] < count[:, None]
+        return {"user_idx": users.to(torch.int32)[:, None].expand_as(ids)[keep], "item_idx": ids[keep], "relevance": vals[keep]}
+
+    def _predict(self, log, k: int, users: pd.DataFrame, items: pd.DataFrame, user_features=None, item_features=None,
+                 filter_seen_items: bool = True) -> pd.DataFrame:
+        out = self.recommend(log, k, users["user_idx"], items["item_idx"], filter_seen_items)
+        return pd.DataFrame({c: out[c].cpu().numpy() for c in REC_COLUMNS})
+
+    def _predict_pairs(self, pairs: pd.DataFrame, log=None, user_features=None, item_features=None) -> pd.DataFrame:
+        sim_ids = self._fitted()[0]
+        if log is None:
+            raise ValueError("log is not provided, but it is required for prediction")
+        lg = P.open_log(P.normalise(log), str(self))
+        if lg.n == 0 or len(pairs) == 0:
+            return pd.DataFrame({"user_idx": np.empty(0, np.int32), "item_idx": np.empty(0, np.int32),
+                                 "relevance": np.empty(0, np.float64)})
+        eng, off, h_item, n_users, _ = self._history(lg)
+        pu = torch.as_tensor(pairs["user_idx"].to_numpy().astype(np.int32), device=lg.device)
+        pi = torch.as_tensor(pairs["item_idx"].to_numpy().astype(np.int32), device=lg.device)
+        n_rows = int(sim_ids.shape[0])
+        score, present = eng.pair_scores(pu, pi, off, h_item, n_users, self._csr(n_rows)[1], n_rows)
+        keep = present.bool().cpu().numpy()
+        return pd.DataFrame({"user_idx": pairs["user_idx"].to_numpy()[keep].astype(np.int32),
+                             "item_idx": pairs["item_idx"].to_numpy()[keep].astype(np.int32),
+                             "relevance": score.cpu().numpy()[keep]})
+
+    # -------------------------------------------------------------------------------- item to item
+    def get_nearest_items(self, items, k: int, metric: Optional[str] = None, candidates=None):
+        """The k most similar items of each of `items` among `candidates` (None: every item); `metric` is ignored.
+        Columns [item_idx, neighbour_item_idx, similarity] (base_rec.py:1554-1609)."""
+        if metric is not None:
+            self.logger.debug("Metric is not used to determine nearest items in %s model", str(self))
+        return self._get_nearest_items_wrap(items=items, k=k, metric=None, candidates=candidates)
+
+    def _get_nearest_items(self, items: pd.DataFrame, metric: Optional[str] = None,
+                           candidates: Optional[pd.DataFrame] = None) -> pd.DataFrame:
+        sim = self.similarity
+        sim = sim[sim["item_idx_one"].isin(items["item_idx"])]
+        if candidates is not None:
+            sim = sim[sim["item_idx_two"].isin(candidates["item_idx"])]
+        return sim[["item_idx_one", "item_idx_two", "similarity"]]
+
+
+class ItemKNN(NeighbourRec):
+    """Item-based k nearest neighbours with a shrunk cosine similarity (replay/models/knn.py)."""
+
+    bm25_k1 = 1.2
+    bm25_b = 0.75
+    _search_space = {
+        "num_neighbours": {"type": "int", "args": [1, 100]},
+        "shrink": {"type": "int", "args": [0, 100]},
+        "weighting": {"type": "categorical", "args": [None, "tf_idf", "bm25"]},
+    }
+
+    def __init__(self, num_neighbours: int = 10, use_relevance: bool = False, shrink: float = 0.0,
+                 weighting: Optional[str] = None, *, max_tuples: int = DEFAULT_MAX_TUPLES):
+        """num_neighbours: neighbours kept per item; use_relevance: the relevance as the weight of a row instead of 1;
+        shrink: added to the denominator; weighting: None, 'tf_idf' or 'bm25'; max_tuples: the tuples of the sparse
+        product held in memory at once (88 bytes each) -- it does not change the result."""
+        self.shrink = shrink
+        self.use_relevance = use_relevance
+        self.num_neighbours = num_neighbours
+        valid_weightings = self._search_space["weighting"]["args"]
+        if weighting not in valid_weightings:
+            raise ValueError(f"weighting must be one of {valid_weightings}")
+        self.weighting = weighting
+        self.max_tuples = int(max_tuples)
+
+    @property
+    def _init_args(self):
+        return {"shrink": self.shrink, "use_relevance": self.use_relevance, "num_neighbours": self.num_neighbours,
+                "weighting": self.weighting}
+
+    def _fit_wrap(self, log, user_features=None, item_features=None) -> None:
+        """pandas and Spark logs go through the template; a pyarrow log or a dict of device tensors stays on the device"""
+        src = P.normalise(log)
+        if isinstance(src, pd.DataFrame) or type(src).__module__.startswith("pyspark"):
+            super()._fit_wrap(src, user_features, item_features)
+            return
+        lg = P.open_log(src, str(self))
+        if lg.n == 0:
+            raise ValueError("cannot fit an empty log")
+        users, items = torch.unique(lg.ids("user_idx")).cpu().numpy(), torch.unique(lg.ids("item_idx")).cpu().numpy()
+        self.fit_users, self.fit_items = pd.DataFrame({"user_idx": users}), pd.DataFrame({"item_idx": items})
+        self._num_users, self._num_items = len(users), len(items)
+        self._user_dim_size, self._item_dim_size = int(users.max()) + 1, int(items.max()) + 1
+        self._fit_device(lg)
+
+    def _fit(self, log: pd.DataFrame, user_features=None, item_features=None) -> None:
+        self._fit_device(P.open_log(log, str(self)))
+
+    def _fit_device(self, lg) -> None:
+        if self.weighting not in self._search_space["weighting"]["args"]:
+            raise ValueError("weighting must be one of ['tf_idf', 'bm25']")
+        N = Neigh(lg.device)
+        k = int(self.num_neighbours)
+        if not 1 <= k <= N.N.NEIGHBOUR_MAX_K:
+            raise ValueError(f"num_neighbours must be in 1..{N.N.NEIGHBOUR_MAX_K}, got {self.num_neighbours}")
+        (user, n_users), (item, n_items) = P.dense_ids(lg, ["user_idx", "item_idx"])
+        rel = None
+        if self.use_relevance:
+            rel = P.float_column(lg, "relevance")
+            if bool(torch.isnan(rel).any()):
+                raise ValueError("relevance contains NaN")
+        ucount, icount = N.count(user, n_users), N.count(item, n_items)
+        distinct = int((icount > 0).sum().item())
+        w = N.weights(user, item, rel, ucount, icount, distinct, self.weighting, self.bm25_k1, self.bm25_b)
+        perm_i, off_i = N.segments(item, n_items, user.to(torch.int64))
+        perm_u, off_u = N.segments(user, n_users, item.to(torch.int64))
+        norm = N.norms(perm_i, off_i, w, n_items)
+        perm_i, perm_u = perm_i.long(), perm_u.long()
+        L = (off_i, user[perm_i].contiguous(), w[perm_i].contiguous())
+        R = (off_u, item[perm_u].contiguous(), w[perm_u].contiguous())
+        self._clear_cache()
+        self._sim = N.topk(N.N.NEIGHBOUR_FIT, L, R, n_users, n_items, k, self.max_tuples, norm_q=norm, norm_j=norm,
+                           shrink=float(self.shrink))
+        self.row_weights, self.item_norms, self.expansion = w, norm, N.expansion
