@@ -831,6 +831,72 @@ int cqlrec_neighbour_pair_scores(const int32_t* pair_user, const int32_t* pair_i
                                  cqlrec_stream stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * f9  Alternating least squares on the device (ALSWrap of replay/models/als.py; the solver is Spark ML's ALS at the
+ * settings that wrapper uses; DESIGN.md section 3.10 is the normative text).  Factors are fp32 [n][rank], 1 <= rank <=
+ * CQLREC_ALS_MAX_RANK; normal equations and the solve are fp64.  A side is a CSR over its destination rows in the order
+ * of cqlrec_features_segments: int64 offsets, int32 source ids, fp64 ratings.  With (s, rho) the entries of a row:
+ *   IMPLICIT  c = alpha |rho|;  A = G + sum c y_s y_s^T;  b = sum over rho > 0 of (1 + c) y_s;  n_expl = #{rho > 0}
+ *   EXPLICIT  A = sum y_s y_s^T;  b = sum rho y_s;  n_expl = the number of entries;  no G
+ * Sum order: the entries of a row are cut into pieces of CQLREC_ALS_PIECE consecutive entries; inside a piece the terms
+ * are added left to right from +0.0 (element (i, j), j <= i: acc = fma(c y_i, y_j, acc); b_j: acc = fma(w, y_j, acc)),
+ * the pieces are added in piece order, G is added last.  A row longer than a piece is always spread over one workgroup
+ * per piece, with the partial matrices in the workspace; nothing depends on the grid, on the other rows of a call or on
+ * the order of a row list.  Integer atomics only; the same input gives the same bytes.  A source id outside [0, n_src)
+ * reads a zero row.  The rules of f5 - f8 carry over: arguments are validated on the host before any HIP call.
+ *
+ * rows [n_list]: the destination rows to work on (NULL: all of them, n_list = n_dst).  n_pieces: the number of pieces
+ * of the listed rows that are longer than CQLREC_ALS_PIECE -- the sum of ceil(len / CQLREC_ALS_PIECE) over them --
+ * which the caller knows from the offsets; it sizes the workspace and two of the three launches.  A long row beyond the
+ * announced pieces is not computed: the half step counts it as failed, the normal equations return NaN and n_expl = -1.
+ * --------------------------------------------------------------------------------------------------------- */
+#define CQLREC_ALS_PIECE 1024
+#define CQLREC_ALS_GRAM_BLOCK 4096
+#define CQLREC_ALS_MAX_RANK 128
+#define CQLREC_ALS_MAX_K 512
+#define CQLREC_ALS_EXPLICIT 0
+#define CQLREC_ALS_IMPLICIT 1
+
+/* G [rank][rank] = F^T F in fp64, F [n_rows][rank] fp32: blocks of CQLREC_ALS_GRAM_BLOCK consecutive rows are summed
+ * left to right (acc = fma(y_i, y_j, acc)), then the blocks in block order.  n_rows == 0: zeros. */
+int64_t cqlrec_als_gram_ws_bytes(int64_t n_rows, int32_t rank);
+int cqlrec_als_gram(const float* F, int64_t n_rows, int32_t rank, void* ws, int64_t ws_bytes, double* G,
+                    cqlrec_stream stream);
+
+/* A [n_list][rank][rank] (symmetric, G included when given, the regulariser not), b [n_list][rank], n_expl [n_list], by
+ * position in the list.  A row without entries gets A = G (or zeros), b = 0, n_expl = 0. */
+int64_t cqlrec_als_normal_equations_ws_bytes(int64_t n_list, int64_t n_pieces, int32_t rank);
+int cqlrec_als_normal_equations(const int64_t* offsets, const int32_t* src, const double* rating, int64_t n_dst,
+                                const float* F, int64_t n_src, int32_t rank, const double* G, int32_t mode, double alpha,
+                                const int32_t* rows, int64_t n_list, int64_t n_pieces, void* ws, int64_t ws_bytes, double* A,
+                                double* b, int32_t* n_expl, cqlrec_stream stream);
+
+/* The update of one side: for every listed row, X[row] = fp32 of the solution of (A + reg n_expl I) x = b by an fp64
+ * Cholesky factorisation (L L^T, forward and back substitution) on chip, has_factor[row] = 1.  A row without entries
+ * gets a zero row and has_factor = 0.  A pivot that is not positive leaves the row zero with has_factor = 0 and adds 1
+ * to *n_failed (device int32, which the caller zeroes).  G: the Gram matrix of F (IMPLICIT; ignored for EXPLICIT). */
+int64_t cqlrec_als_half_step_ws_bytes(int64_t n_list, int64_t n_pieces, int32_t rank);
+int cqlrec_als_half_step(const int64_t* offsets, const int32_t* src, const double* rating, int64_t n_dst, const float* F,
+                         int64_t n_src, int32_t rank, const double* G, int32_t mode, double alpha, double reg,
+                         const int32_t* rows, int64_t n_list, int64_t n_pieces, void* ws, int64_t ws_bytes, float* X,
+                         uint8_t* has_factor, int32_t* n_failed, cqlrec_stream stream);
+
+/* score(u, i) = the fmaf chain s = fmaf(U[u][c], V[i][c], s) over c ascending from s = 0, in fp32: the one function of
+ * both entry points below.
+ * ids [n_q][k] (padded with -1), vals [n_q][k] (padded with -inf), count [n_q]: the k best items of users[q] by score
+ * descending, then item id ascending, among the items with v_has != 0, mask != 0 (mask: NULL or one byte per item) and
+ * not in the ascending list seen_col[seen_off[u] .. seen_off[u + 1]) (seen_off [n_users + 1], indexed by the user id;
+ * NULL: none).  A user outside [0, n_users) or with u_has == 0 gets count 0.  1 <= k <= CQLREC_ALS_MAX_K.  V is 16-byte
+ * aligned.  No scratch. */
+int cqlrec_als_topk(const int32_t* users, int64_t n_q, const float* U, const uint8_t* u_has, int64_t n_users, const float* V,
+                    const uint8_t* v_has, int64_t n_items, int32_t rank, const uint8_t* mask, const int64_t* seen_off,
+                    const int32_t* seen_col, int32_t k, int32_t* ids, float* vals, int32_t* count, cqlrec_stream stream);
+
+/* score [n_pairs] and valid [n_pairs] = 0 where either id is out of range or has no factor (the score is then 0) */
+int cqlrec_als_pair_scores(const int32_t* pair_user, const int32_t* pair_item, int64_t n_pairs, const float* U,
+                           const uint8_t* u_has, int64_t n_users, const float* V, const uint8_t* v_has, int64_t n_items,
+                           int32_t rank, float* score, uint8_t* valid, cqlrec_stream stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * Measurement hooks (bench.py): when enabled, every launcher brackets its kernel with a pair of HIP events on
  * the stream it launches on; cqlrec_prof_read synchronises those events and returns, per phase, the summed
  * kernel time in ms and the number of launches, then resets the pool.  Not capturable in a hipGraph; off by

@@ -5,7 +5,7 @@ core (device driver).  The HIP library is loaded lazily; nothing here falls back
 __version__ = "0.1.0"
 
 # the train/test splitters (splitters.py), the filters (filters.py), the Indexer (indexer.py) and the history-based
-# feature processors (history_based_fp.py) and the neighbourhood models (neighbour.py), importable from the
+# feature processors (history_based_fp.py), the neighbourhood models (neighbour.py) and ALS (als.py), importable from the
 # package without loading torch until they are asked for
 _SPLITTERS = ("Splitter", "UserSplitter", "DateSplitter", "RandomSplitter", "NewUsersSplitter", "ColdUserRandomSplitter",
               "k_folds")
@@ -14,7 +14,7 @@ _FILTERS = ("filter_by_min_count", "filter_out_low_ratings", "take_num_user_inte
 _FEATURES = ("EmptyFeatureProcessor", "LogStatFeaturesProcessor", "ConditionalPopularityProcessor",
              "HistoryBasedFeaturesProcessor")
 _NEIGHBOUR = ("NeighbourRec", "ItemKNN")
-__all__ = list(_SPLITTERS) + list(_FILTERS) + ["Indexer"] + list(_FEATURES) + list(_NEIGHBOUR)
+__all__ = list(_SPLITTERS) + list(_FILTERS) + ["Indexer"] + list(_FEATURES) + list(_NEIGHBOUR) + ["ALSWrap"]
 
 
 def __getattr__(name):
@@ -30,6 +30,9 @@ def __getattr__(name):
     if name in _NEIGHBOUR:
         from . import neighbour          # pylint: disable=import-outside-toplevel
         return getattr(neighbour, name)
+    if name == "ALSWrap":
+        from . import als                # pylint: disable=import-outside-toplevel
+        return als.ALSWrap
     if name == "Indexer":
         from . import indexer            # pylint: disable=import-outside-toplevel
         return indexer.Indexer

@@ -85,6 +85,9 @@ NEIGHBOUR_FIT, NEIGHBOUR_PREDICT = 0, 1
 NEIGHBOUR_MAX_K = 1024
 NEIGHBOUR_WEIGHTINGS = {None: 0, "tf_idf": 1, "bm25": 2}
 
+ALS_PIECE, ALS_GRAM_BLOCK, ALS_MAX_RANK, ALS_MAX_K = 1024, 4096, 128, 512
+ALS_EXPLICIT, ALS_IMPLICIT = 0, 1
+
 # name -> (restype, argtypes); every symbol include/cqlrec.h declares
 SIGNATURES = {
     "cqlrec_abi_version": (i32, []),
@@ -200,6 +203,14 @@ SIGNATURES = {
     "cqlrec_neighbour_topk": (i32, [i32, vp, vp, vp, i64, i64, vp, vp, vp, i64, i64, vp, vp, i64, i64, i32, vp, vp, f64, vp,
                                     vp, vp, vp, i64, vp, vp, vp, vp]),
     "cqlrec_neighbour_pair_scores": (i32, [vp, vp, i64, vp, vp, i64, vp, vp, vp, i64, vp, vp, vp]),
+    "cqlrec_als_gram_ws_bytes": (i64, [i64, i32]),
+    "cqlrec_als_gram": (i32, [vp, i64, i32, vp, i64, vp, vp]),
+    "cqlrec_als_normal_equations_ws_bytes": (i64, [i64, i64, i32]),
+    "cqlrec_als_normal_equations": (i32, [vp, vp, vp, i64, vp, i64, i32, vp, i32, f64, vp, i64, i64, vp, i64, vp, vp, vp, vp]),
+    "cqlrec_als_half_step_ws_bytes": (i64, [i64, i64, i32]),
+    "cqlrec_als_half_step": (i32, [vp, vp, vp, i64, vp, i64, i32, vp, i32, f64, f64, vp, i64, i64, vp, i64, vp, vp, vp, vp]),
+    "cqlrec_als_topk": (i32, [vp, i64, vp, vp, i64, vp, vp, i64, i32, vp, vp, vp, i32, vp, vp, vp, vp]),
+    "cqlrec_als_pair_scores": (i32, [vp, vp, i64, vp, vp, i64, vp, vp, i64, i32, vp, vp, vp]),
     "cqlrec_prof_enable": (i32, [i32]),
     "cqlrec_prof_select": (i32, [C.c_uint32]),
     "cqlrec_debug_marks_enable": (i32, [i32]),
