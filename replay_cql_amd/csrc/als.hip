@@ -18,8 +18,8 @@
 //                Row `rank` comes out as z = L^-1 b, so the forward substitution costs nothing; the back
 //                substitution runs on one wave with z in registers and the reciprocals of the diagonal from LDS.
 // Nothing depends on the grid, on which wave takes a row or on the other rows of a launch.
-#include <rocprim/device/device_scan.hpp>
 
+#include "segment_common.h"
 #include "select_common.h"
 
 static const int64_t ALS_MAX = 1ll << 31;
@@ -27,8 +27,6 @@ static const int64_t ALS_MAX = 1ll << 31;
 #define ALS_TOPK_ROWS 4             // query rows per wave of the top-k kernel: they share the loads of the item table
 static inline int als_topk_cb(int k) { return 2 * k < 128 ? 128 : 2 * k; }   // keys per selection buffer: k and room for batches of 64
 
-static inline int64_t als_a256(int64_t x) { return (x + 255) / 256 * 256; }
-static inline int64_t als_scan_cap(int64_t n) { return als_a256(n * 8) + (1ll << 20); }
 
 enum { ALS_SHORT = 0, ALS_PIECE = 1, ALS_FINISH = 2 };
 
@@ -418,11 +416,11 @@ struct AlsWs {
 static AlsWs als_ws(int64_t n_list, int64_t n_pieces, int rank) {
   AlsWs w;
   int64_t o = 0;
-  w.np = o; o += als_a256((n_list + 1) * 8);
-  w.piece_off = o; o += als_a256((n_list + 1) * 8);
-  w.temp = o; o += als_scan_cap(n_list + 1);
-  w.part = o; o += als_a256(n_pieces * als_shape(rank).part_stride() * 8);
-  w.part_n = o; o += als_a256(n_pieces * 4);
+  w.np = o; o += cql_align256((n_list + 1) * 8);
+  w.piece_off = o; o += cql_align256((n_list + 1) * 8);
+  w.temp = o; o += cql_scan_temp_cap(n_list + 1);
+  w.part = o; o += cql_align256(n_pieces * als_shape(rank).part_stride() * 8);
+  w.part_n = o; o += cql_align256(n_pieces * 4);
   w.total = o;
   return w;
 }
@@ -441,24 +439,16 @@ static int als_rows(AlsArgs a, void* ws, int64_t ws_bytes, const char* what, hip
   hipLaunchKernelGGL(als_npieces_kernel, dim3(cql_ceil_div(a.n_list + 1, 256)), dim3(256), 0, s, a.offsets, a.rows, a.n_list,
                      a.n_dst, (int64_t)CQLREC_ALS_PIECE, np);
   CQL_LAUNCH_CHECK(what);
-  size_t need = 0;
-  hipError_t e = rocprim::exclusive_scan(nullptr, need, np, piece_off, (int64_t)0, (size_t)(a.n_list + 1),
-                                         rocprim::plus<int64_t>(), s);
-  if (e == hipSuccess && need > (size_t)als_scan_cap(a.n_list + 1)) e = hipErrorOutOfMemory;
-  if (e == hipSuccess)
-    e = rocprim::exclusive_scan(base + w.temp, need, np, piece_off, (int64_t)0, (size_t)(a.n_list + 1),
-                                rocprim::plus<int64_t>(), s);
-  if (e != hipSuccess) {
-    cql_set_error("%s: rocPRIM scan failed: %s", what, hipGetErrorString(e));
-    return CQLREC_ERR_HIP;
-  }
+  int rc = cql_exclusive_scan(what, base + w.temp, (size_t)cql_scan_temp_cap(a.n_list + 1), np, piece_off, (int64_t)0,
+                              a.n_list + 1, s);
+  if (rc != CQLREC_OK) return rc;
   a.piece_off = piece_off;
   a.part = reinterpret_cast<double*>(base + w.part);
   a.part_n = reinterpret_cast<int32_t*>(base + w.part_n);
   a.part_stride = sh.part_stride();
   a.piece = CQLREC_ALS_PIECE;
   a.nb = sh.nb;
-  int rc = als_launch(sh, a, ALS_SHORT, a.n_list, s);
+  rc = als_launch(sh, a, ALS_SHORT, a.n_list, s);
   if (rc == CQLREC_OK) rc = als_launch(sh, a, ALS_PIECE, a.n_pieces, s);
   if (rc == CQLREC_OK) rc = als_launch(sh, a, ALS_FINISH, a.n_pieces, s);
   return rc;
@@ -473,7 +463,7 @@ static inline int64_t als_gram_pieces(int64_t n) {
 extern "C" int64_t cqlrec_als_gram_ws_bytes(int64_t n_rows, int32_t rank) {
   if (n_rows < 0 || n_rows >= ALS_MAX || rank < 1 || rank > CQLREC_ALS_MAX_RANK) return 0;
   const int64_t np = als_gram_pieces(n_rows);
-  return 256 + 256 + als_a256(np * als_shape(rank).part_stride() * 8) + als_a256(np * 4);
+  return 256 + 256 + cql_align256(np * als_shape(rank).part_stride() * 8) + cql_align256(np * 4);
 }
 extern "C" int cqlrec_als_gram(const float* F, int64_t n_rows, int32_t rank, void* ws, int64_t ws_bytes, double* G,
                                cqlrec_stream stream) {
@@ -496,7 +486,7 @@ extern "C" int cqlrec_als_gram(const float* F, int64_t n_rows, int32_t rank, voi
   a.F = F;
   a.piece_off = piece_off;
   a.part = reinterpret_cast<double*>(base + 512);
-  a.part_n = reinterpret_cast<int32_t*>(base + 512 + als_a256(np * sh.part_stride() * 8));
+  a.part_n = reinterpret_cast<int32_t*>(base + 512 + cql_align256(np * sh.part_stride() * 8));
   a.A = G;
   a.n_src = n_rows;
   a.n_dst = 1;

@@ -10,46 +10,10 @@
 // takes the rows l, l + 64, ... in that order, then a butterfly over the lanes), and one wave per group sums the
 // group's pieces the same way.  No thread walks more than FEAT_SUB / 64 rows, nor more than n_rows / (64 * FEAT_SUB)
 // pieces (< 2^15 for n_rows < 2^31), whatever the group sizes are.
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_run_length_encode.hpp>
-#include <rocprim/device/device_scan.hpp>
+#include "segment_common.h"
 
-#include "common.h"
-
-static inline int64_t a256(int64_t x) { return (x + 255) / 256 * 256; }
 static const int64_t FEAT_MAX_ROWS = 1ll << 31;
 static const int FEAT_SUB = 1024;
-static inline int64_t sort_temp_cap(int64_t n) { return a256(4 * n * 8) + (16ll << 20); }
-static inline int64_t scan_temp_cap(int64_t n) { return a256(n * 8) + (1ll << 20); }
-
-#define FEAT_ROCPRIM(call, what)                                                         \
-  do {                                                                                   \
-    hipError_t e__ = (call);                                                             \
-    if (e__ != hipSuccess) {                                                             \
-      cql_set_error("%s: rocPRIM failed: %s", what, hipGetErrorString(e__));             \
-      return CQLREC_ERR_HIP;                                                             \
-    }                                                                                    \
-  } while (0)
-#define FEAT_TEMP_FITS(need, cap, what)                                                  \
-  do {                                                                                   \
-    if ((need) > (size_t)(cap)) {                                                        \
-      cql_set_error("%s: rocPRIM needs %zu bytes of scratch (have %zu)", what, (size_t)(need), (size_t)(cap)); \
-      return CQLREC_ERR_HIP;                                                             \
-    }                                                                                    \
-  } while (0)
-#define FEAT_MEMSET(ptr, val, bytes, what)                                               \
-  do {                                                                                   \
-    if (hipMemsetAsync(ptr, val, bytes, s) != hipSuccess) {                              \
-      cql_set_error("%s: memset failed", what);                                          \
-      return CQLREC_ERR_HIP;                                                             \
-    }                                                                                    \
-  } while (0)
-
-static inline unsigned bits_for(int64_t n) {
-  unsigned bits = 1;
-  while (bits < 62 && (1ll << bits) < n) ++bits;
-  return bits;
-}
 
 // =============================================================================================================
 // day = floor(key / unit)
@@ -77,32 +41,14 @@ extern "C" int cqlrec_features_day(const int64_t* key, int64_t n, int64_t unit, 
 // =============================================================================================================
 // segments: rows ordered by (group, key, input row index) ascending
 // =============================================================================================================
-__global__ void features_iota_kernel(int64_t n, uint32_t* __restrict__ perm) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) perm[i] = (uint32_t)i;
-}
 __global__ void features_sort_key_kernel(const int64_t* __restrict__ key, int64_t n, uint64_t* __restrict__ out) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) out[i] = (uint64_t)key[i] ^ (1ull << 63);
 }
-__global__ void features_group_key_kernel(const int32_t* __restrict__ group, const uint32_t* __restrict__ perm, int64_t n,
-                                          uint32_t* __restrict__ out) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) out[i] = (uint32_t)group[perm[i]];
-}
-// offsets[g] = first sorted position whose group >= g
-__global__ void features_bounds_kernel(const int32_t* __restrict__ group, const int32_t* __restrict__ perm, int64_t n,
-                                       int64_t n_groups, int64_t* __restrict__ offsets) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i > n) return;
-  const int64_t cur = (i < n) ? (int64_t)group[perm[i]] : n_groups;
-  const int64_t prev = (i > 0) ? (int64_t)group[perm[i - 1]] : -1;
-  for (int64_t g = prev + 1; g <= cur; ++g) offsets[g] = i;
-}
 
 extern "C" int64_t cqlrec_features_segments_ws_bytes(int64_t n_rows, int64_t n_groups) {
   if (n_rows < 0 || n_groups < 0) return 0;
-  return 2 * a256(n_rows * 4) + 2 * a256(n_rows * 8) + sort_temp_cap(n_rows) + 256;
+  return CqlPermSort::bytes(n_rows) + cql_sort_temp_cap(n_rows) + 256;
 }
 
 extern "C" int cqlrec_features_segments(const int32_t* group, const int64_t* key, int64_t n_rows, int64_t n_groups,
@@ -113,41 +59,24 @@ extern "C" int cqlrec_features_segments(const int32_t* group, const int64_t* key
   CQL_REQUIRE(offsets, "features_segments: NULL pointer");
   hipStream_t s = (hipStream_t)stream;
   if (n_rows == 0) {
-    FEAT_MEMSET(offsets, 0, (size_t)(n_groups + 1) * 8, "features_segments");
+    CQL_MEMSET(offsets, 0, (size_t)(n_groups + 1) * 8, s, "features_segments");
     return CQLREC_OK;
   }
   CQL_REQUIRE(group && ws && perm, "features_segments: NULL pointer");
   CQL_REQUIRE(ws_bytes >= cqlrec_features_segments_ws_bytes(n_rows, n_groups), "features_segments: workspace too small");
   char* p = (char*)ws;
-  uint32_t* cur = (uint32_t*)p;    p += a256(n_rows * 4);
-  uint32_t* other = (uint32_t*)p;  p += a256(n_rows * 4);
-  uint64_t* key_a = (uint64_t*)p;  p += a256(n_rows * 8);
-  uint64_t* key_b = (uint64_t*)p;  p += a256(n_rows * 8);
-  void* temp = p;
-  const size_t temp_cap = (size_t)sort_temp_cap(n_rows);
-  const dim3 grid(cql_ceil_div(n_rows, 256)), block(256);
-  uint32_t* k32_a = (uint32_t*)key_a;
-  uint32_t* k32_b = (uint32_t*)key_b;
-  size_t need = 0;
-  hipLaunchKernelGGL(features_iota_kernel, grid, block, 0, s, n_rows, cur);
+  CqlPermSort ps(p, n_rows, s);
+  ps.temp = p;
+  int rc;
+  cql_iota(ps.perm, n_rows, false, s);
   if (key) {  // least significant: the key, over all 64 bits (the permutation is still the identity)
-    hipLaunchKernelGGL(features_sort_key_kernel, grid, block, 0, s, key, n_rows, key_a);
-    FEAT_ROCPRIM(rocprim::radix_sort_pairs(nullptr, need, key_a, key_b, cur, other, (size_t)n_rows, 0u, 64u, s),
-                 "features_segments");
-    FEAT_TEMP_FITS(need, temp_cap, "features_segments");
-    FEAT_ROCPRIM(rocprim::radix_sort_pairs(temp, need, key_a, key_b, cur, other, (size_t)n_rows, 0u, 64u, s),
-                 "features_segments");
-    uint32_t* t = cur;  cur = other;  other = t;
+    hipLaunchKernelGGL(features_sort_key_kernel, dim3(cql_ceil_div(n_rows, 256)), dim3(256), 0, s, key, n_rows,
+                       ps.keys<uint64_t>());
+    if ((rc = ps.pass<uint64_t>("features_segments", 64)) != CQLREC_OK) return rc;
   }
-  const unsigned gbits = bits_for(n_groups);
-  hipLaunchKernelGGL(features_group_key_kernel, grid, block, 0, s, group, cur, n_rows, k32_a);
-  FEAT_ROCPRIM(rocprim::radix_sort_pairs(nullptr, need, k32_a, k32_b, cur, (uint32_t*)perm, (size_t)n_rows, 0u, gbits, s),
-               "features_segments");
-  FEAT_TEMP_FITS(need, temp_cap, "features_segments");
-  FEAT_ROCPRIM(rocprim::radix_sort_pairs(temp, need, k32_a, k32_b, cur, (uint32_t*)perm, (size_t)n_rows, 0u, gbits, s),
-               "features_segments");
-  hipLaunchKernelGGL(features_bounds_kernel, dim3(cql_ceil_div(n_rows + 1, 256)), block, 0, s, group, perm, n_rows,
-                     n_groups, offsets);
+  cql_group_key(group, ps.perm, n_rows, ps.keys<uint32_t>(), s);
+  if ((rc = ps.pass<uint32_t>("features_segments", cql_bits_for(n_groups), (uint32_t*)perm)) != CQLREC_OK) return rc;
+  cql_segment_bounds(CqlGroupOfPerm{group, ps.perm}, n_rows, n_groups, offsets, nullptr, s);
   CQL_LAUNCH_CHECK("features_segments");
   return CQLREC_OK;
 }
@@ -273,7 +202,8 @@ __global__ void features_pick_kernel(const int32_t* __restrict__ perm, const int
 static inline int64_t feat_max_pieces(int64_t n_rows, int64_t n_groups) { return n_rows / FEAT_SUB + n_groups; }
 
 static int64_t feat_sum_ws_bytes(int64_t n_rows, int64_t n_groups) {
-  return 2 * a256((n_groups + 1) * 8) + a256(feat_max_pieces(n_rows, n_groups) * 8) + scan_temp_cap(n_groups + 1) + 256;
+  return 2 * cql_align256((n_groups + 1) * 8) + cql_align256(feat_max_pieces(n_rows, n_groups) * 8) +
+         cql_scan_temp_cap(n_groups + 1) + 256;
 }
 
 struct FeatSumWs {
@@ -284,9 +214,9 @@ struct FeatSumWs {
 static FeatSumWs feat_sum_carve(void* ws, int64_t n_rows, int64_t n_groups) {
   FeatSumWs w;
   char* p = (char*)ws;
-  w.nsub = (int64_t*)p;     p += a256((n_groups + 1) * 8);
-  w.sub_off = (int64_t*)p;  p += a256((n_groups + 1) * 8);
-  w.partial = (double*)p;   p += a256(feat_max_pieces(n_rows, n_groups) * 8);
+  w.nsub = (int64_t*)p;     p += cql_align256((n_groups + 1) * 8);
+  w.sub_off = (int64_t*)p;  p += cql_align256((n_groups + 1) * 8);
+  w.partial = (double*)p;   p += cql_align256(feat_max_pieces(n_rows, n_groups) * 8);
   w.temp = p;
   return w;
 }
@@ -294,13 +224,8 @@ static FeatSumWs feat_sum_carve(void* ws, int64_t n_rows, int64_t n_groups) {
 static int feat_pieces(const int64_t* offsets, int64_t n_groups, const FeatSumWs& w, hipStream_t s, const char* what) {
   hipLaunchKernelGGL(features_nsub_kernel, dim3(cql_ceil_div(n_groups + 1, 256)), dim3(256), 0, s, offsets, n_groups,
                      w.nsub);
-  size_t need = 0;
-  FEAT_ROCPRIM(rocprim::exclusive_scan(nullptr, need, w.nsub, w.sub_off, (int64_t)0, (size_t)(n_groups + 1),
-                                       rocprim::plus<int64_t>(), s), what);
-  FEAT_TEMP_FITS(need, scan_temp_cap(n_groups + 1), what);
-  FEAT_ROCPRIM(rocprim::exclusive_scan(w.temp, need, w.nsub, w.sub_off, (int64_t)0, (size_t)(n_groups + 1),
-                                       rocprim::plus<int64_t>(), s), what);
-  return CQLREC_OK;
+  return cql_exclusive_scan(what, w.temp, (size_t)cql_scan_temp_cap(n_groups + 1), w.nsub, w.sub_off, (int64_t)0, n_groups + 1,
+                            s);
 }
 static void feat_sum(const FeatExpr& E, const int32_t* perm, const int64_t* offsets, int64_t n_rows, int64_t n_groups,
                      const FeatSumWs& w, int finish, double* out, int64_t ostride, double* count_out, hipStream_t s) {
@@ -323,7 +248,7 @@ extern "C" int cqlrec_features_segment_stats(const int32_t* perm, const int64_t*
   CQL_REQUIRE(out, "features_segment_stats: NULL pointer");
   hipStream_t s = (hipStream_t)stream;
   if (n_rows == 0) {
-    FEAT_MEMSET(out, 0, (size_t)n_groups * CQLREC_FEATURES_STATS * 8, "features_segment_stats");
+    CQL_MEMSET(out, 0, (size_t)n_groups * CQLREC_FEATURES_STATS * 8, s, "features_segment_stats");
     return CQLREC_OK;
   }
   CQL_REQUIRE(perm && offsets && value && ws, "features_segment_stats: NULL pointer");
@@ -363,7 +288,7 @@ extern "C" int cqlrec_features_segment_mean(int32_t rule, const int32_t* perm, c
   CQL_REQUIRE(out, "features_segment_mean: NULL pointer");
   hipStream_t s = (hipStream_t)stream;
   if (n_rows == 0) {
-    FEAT_MEMSET(out, 0, (size_t)n_groups * 8, "features_segment_mean");
+    CQL_MEMSET(out, 0, (size_t)n_groups * 8, s, "features_segment_mean");
     return CQLREC_OK;
   }
   CQL_REQUIRE(perm && offsets && ws && other && tab_a && tab_stride > 0, "features_segment_mean: NULL pointer");
@@ -409,7 +334,7 @@ extern "C" int cqlrec_features_segment_distinct(const int32_t* group, const int3
               "features_segment_distinct: n_rows=%lld n_groups=%lld out of range", (long long)n_rows, (long long)n_groups);
   CQL_REQUIRE(out && (n_rows == 0 || (group && perm && offsets && key)), "features_segment_distinct: NULL pointer");
   hipStream_t s = (hipStream_t)stream;
-  FEAT_MEMSET(out, 0, (size_t)n_groups * 4, "features_segment_distinct");
+  CQL_MEMSET(out, 0, (size_t)n_groups * 4, s, "features_segment_distinct");
   if (n_rows == 0) return CQLREC_OK;
   hipLaunchKernelGGL(features_heads_kernel, dim3(cql_ceil_div(n_rows, 256)), dim3(256), 0, s, group, perm, offsets, key,
                      n_rows, out);
@@ -436,13 +361,13 @@ __global__ void features_pair_pop_kernel(const int64_t* __restrict__ keys, const
   if (i > m) return;
   const int64_t cur = (i < m) ? keys[i] / (n_cat + 1) : n_entity;
   const int64_t prev = (i > 0) ? keys[i - 1] / (n_cat + 1) : -1;
-  for (int64_t e = prev + 1; e <= cur; ++e) entity_off[e] = i;
+  cql_fill_gap(prev, cur, i, entity_off);
   if (i < m) pop[i] = (double)runs[i] / (double)entity_count[cur];
 }
 
 extern "C" int64_t cqlrec_features_pair_counts_ws_bytes(int64_t n_rows) {
   if (n_rows < 0) return 0;
-  return 2 * a256(n_rows * 8) + a256(n_rows * 4) + sort_temp_cap(n_rows) + 256;
+  return 2 * cql_align256(n_rows * 8) + cql_align256(n_rows * 4) + cql_sort_temp_cap(n_rows) + 256;
 }
 
 extern "C" int cqlrec_features_pair_counts(const int32_t* entity, const int32_t* other, const int32_t* code,
@@ -456,31 +381,25 @@ extern "C" int cqlrec_features_pair_counts(const int32_t* entity, const int32_t*
   CQL_REQUIRE(n_out && entity_off, "features_pair_counts: NULL pointer");
   hipStream_t s = (hipStream_t)stream;
   if (n_rows == 0) {
-    FEAT_MEMSET(n_out, 0, 8, "features_pair_counts");
-    FEAT_MEMSET(entity_off, 0, (size_t)(n_entity + 1) * 8, "features_pair_counts");
+    CQL_MEMSET(n_out, 0, 8, s, "features_pair_counts");
+    CQL_MEMSET(entity_off, 0, (size_t)(n_entity + 1) * 8, s, "features_pair_counts");
     return CQLREC_OK;
   }
   CQL_REQUIRE(entity && other && code && entity_count && ws && keys && pop, "features_pair_counts: NULL pointer");
   CQL_REQUIRE(ws_bytes >= cqlrec_features_pair_counts_ws_bytes(n_rows), "features_pair_counts: workspace too small");
   char* p = (char*)ws;
-  int64_t* raw = (int64_t*)p;     p += a256(n_rows * 8);
-  int64_t* sorted = (int64_t*)p;  p += a256(n_rows * 8);
-  uint32_t* runs = (uint32_t*)p;  p += a256(n_rows * 4);
+  int64_t* raw = (int64_t*)p;     p += cql_align256(n_rows * 8);
+  int64_t* sorted = (int64_t*)p;  p += cql_align256(n_rows * 8);
+  uint32_t* runs = (uint32_t*)p;  p += cql_align256(n_rows * 4);
   void* temp = p;
-  const size_t cap = (size_t)sort_temp_cap(n_rows);
-  const unsigned bits = bits_for(n_entity * (n_cat + 1));        // the keys are non-negative and below that product
-  static_assert(sizeof(size_t) == sizeof(int64_t), "the count is written as size_t");
+  const size_t cap = (size_t)cql_sort_temp_cap(n_rows);
+  const unsigned bits = cql_bits_for(n_entity * (n_cat + 1));        // the keys are non-negative and below that product
   hipLaunchKernelGGL(features_pair_key_kernel, dim3(cql_ceil_div(n_rows, 256)), dim3(256), 0, s, entity, other, code, n_rows,
                      n_cat, raw);
-  size_t need = 0;
-  FEAT_ROCPRIM(rocprim::radix_sort_keys(nullptr, need, raw, sorted, (size_t)n_rows, 0u, bits, s), "features_pair_counts");
-  FEAT_TEMP_FITS(need, cap, "features_pair_counts");
-  FEAT_ROCPRIM(rocprim::radix_sort_keys(temp, need, raw, sorted, (size_t)n_rows, 0u, bits, s), "features_pair_counts");
-  FEAT_ROCPRIM(rocprim::run_length_encode(nullptr, need, sorted, (unsigned int)n_rows, keys, runs, (size_t*)n_out, s),
-               "features_pair_counts");
-  FEAT_TEMP_FITS(need, cap, "features_pair_counts");
-  FEAT_ROCPRIM(rocprim::run_length_encode(temp, need, sorted, (unsigned int)n_rows, keys, runs, (size_t*)n_out, s),
-               "features_pair_counts");
+  int rc = cql_sort_keys("features_pair_counts", temp, cap, raw, sorted, n_rows, bits, s);
+  if (rc == CQLREC_OK)
+    rc = cql_run_length_encode("features_pair_counts", temp, cap, sorted, n_rows, keys, runs, (size_t*)n_out, s);
+  if (rc != CQLREC_OK) return rc;
   hipLaunchKernelGGL(features_pair_pop_kernel, dim3(cql_ceil_div(n_rows + 1, 256)), dim3(256), 0, s, keys, runs, n_out,
                      entity_count, n_cat, n_entity, pop, entity_off);
   CQL_LAUNCH_CHECK("features_pair_counts");

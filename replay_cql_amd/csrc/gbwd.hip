@@ -9,9 +9,8 @@
 //      sum in registers and stores once per run; pieces of runs that cross a chunk edge are combined by a second
 //      small pass in chunk order (hot items: one add per 64 contributions, then one wave sums the pieces).
 #include <cstring>
-#include <rocprim/device/device_radix_sort.hpp>
 
-#include "common.h"
+#include "segment_common.h"
 
 __global__ __launch_bounds__(256) void gbwd_pairs_kernel(const int64_t* __restrict__ offsets,
                                                          const int32_t* __restrict__ items,
@@ -182,13 +181,9 @@ static void segsum_launch(const void* src, const float* w, const uint32_t* keys,
 #define GB_CH 64   // pairs per wave, window gather
 #define OH_CH 8    // pairs per wave, one-hot scatter
 
-static inline int64_t a256(int64_t x) { return (x + 255) / 256 * 256; }
-static inline unsigned key_bits(int64_t n_items) {
-  unsigned b = 1;
-  while ((1ll << b) <= n_items) ++b;   // pad key = n_items must be representable
-  return b;
-}
-static int64_t sort_temp_bound(int64_t n) { return a256(2 * n * 4 * 2) + (8ll << 20); }
+static inline unsigned key_bits(int64_t n_items) { return cql_bits_for(n_items + 1); }   // pad key = n_items is representable
+// 32-bit keys and values: half of cql_sort_temp_cap (the step's workspace is sized from this)
+static int64_t sort_temp_bound(int64_t n) { return cql_align256(2 * n * 4 * 2) + (8ll << 20); }
 
 namespace {
 struct GbWs {
@@ -204,13 +199,13 @@ GbWs gb_carve(void* ws, int64_t n_states, int32_t L, int32_t d) {
   const int64_t n = n_states * L;
   char* p = (char*)ws;
   GbWs w;
-  w.g = (float*)p;              p += a256(n_states * d * 4);
-  w.edge = (float*)p;           p += a256(((n + GB_CH - 1) / GB_CH) * 2 * d * 4);
-  w.lens = (int32_t*)p;         p += a256(n_states * 4);
-  w.keys_in = (uint32_t*)p;     p += a256(n * 4);
-  w.vals_in = (uint32_t*)p;     p += a256(n * 4);
-  w.keys_out = (uint32_t*)p;    p += a256(n * 4);
-  w.vals_out = (uint32_t*)p;    p += a256(n * 4);
+  w.g = (float*)p;              p += cql_align256(n_states * d * 4);
+  w.edge = (float*)p;           p += cql_align256(((n + GB_CH - 1) / GB_CH) * 2 * d * 4);
+  w.lens = (int32_t*)p;         p += cql_align256(n_states * 4);
+  w.keys_in = (uint32_t*)p;     p += cql_align256(n * 4);
+  w.vals_in = (uint32_t*)p;     p += cql_align256(n * 4);
+  w.keys_out = (uint32_t*)p;    p += cql_align256(n * 4);
+  w.vals_out = (uint32_t*)p;    p += cql_align256(n * 4);
   w.temp = p;
   w.temp_cap = (size_t)sort_temp_bound(n);
   w.total = (int64_t)(p - (char*)ws) + (int64_t)w.temp_cap;
@@ -240,20 +235,9 @@ extern "C" int cqlrec_gather_pool_bwd_prepare(const int64_t* offsets, const int3
   CqlProfScope prof(CQLREC_PH_GATHER_BWD, s);
   hipLaunchKernelGGL(gbwd_pairs_kernel, dim3(cql_ceil_div(n_states, 4)), dim3(256), 0, s, offsets, items, users, ends,
                      end_delta, n_states, L, pad_key, w.keys_in, w.vals_in, w.lens);
-  size_t need = 0;
-  hipError_t e = rocprim::radix_sort_pairs(nullptr, need, w.keys_in, w.keys_out, w.vals_in, w.vals_out, (size_t)n, 0u,
-                                           key_bits(n_items), s);
-  if (e != hipSuccess || need > w.temp_cap) {
-    cql_set_error("gather_pool_bwd_prepare: radix sort needs %zu bytes of scratch (have %zu), err=%d", need, w.temp_cap,
-                  (int)e);
-    return CQLREC_ERR_HIP;
-  }
-  e = rocprim::radix_sort_pairs(w.temp, need, w.keys_in, w.keys_out, w.vals_in, w.vals_out, (size_t)n, 0u,
+  const int rc = cql_sort_pairs("gather_pool_bwd_prepare", w.temp, w.temp_cap, w.keys_in, w.keys_out, w.vals_in, w.vals_out, n,
                                 key_bits(n_items), s);
-  if (e != hipSuccess) {
-    cql_set_error("gather_pool_bwd_prepare: radix sort failed: %s", hipGetErrorString(e));
-    return CQLREC_ERR_HIP;
-  }
+  if (rc != CQLREC_OK) return rc;
   CQL_LAUNCH_CHECK("gather_pool_bwd_prepare");
   return CQLREC_OK;
 }
@@ -272,10 +256,7 @@ int cql_gather_pool_bwd_mark_rows(const void* ws, int64_t n_states, int32_t L, i
                                   hipStream_t s) {
   CQL_REQUIRE(ws && row_map, "gather_pool_bwd_mark_rows: NULL pointer");
   CQL_REQUIRE(n_items > 0 && n_items < (1ll << 31), "gather_pool_bwd_mark_rows: n_items=%lld", (long long)n_items);
-  if (hipMemsetAsync(row_map, 0, (size_t)n_items, s) != hipSuccess) {
-    cql_set_error("gather_pool_bwd_mark_rows: clearing the map failed");
-    return CQLREC_ERR_HIP;
-  }
+  CQL_MEMSET(row_map, 0, (size_t)n_items, s, "gather_pool_bwd_mark_rows");
   if (n_states <= 0) return CQLREC_OK;
   const GbWs w = gb_carve(const_cast<void*>(ws), n_states, L, d);
   const int64_t n = n_states * L;
@@ -306,10 +287,7 @@ int cql_mark_read_rows(const int64_t* offsets, const int32_t* items, const int32
                        int64_t n_states, int32_t L, int64_t n_items, uint8_t* read_map, hipStream_t s) {
   CQL_REQUIRE(offsets && items && users && tpos && read_map, "mark_read_rows: NULL pointer");
   CQL_REQUIRE(n_items > 0 && n_items < (1ll << 31) && L > 0, "mark_read_rows: n_items=%lld L=%d", (long long)n_items, L);
-  if (hipMemsetAsync(read_map, 0, (size_t)n_items, s) != hipSuccess) {
-    cql_set_error("mark_read_rows: clearing the map failed");
-    return CQLREC_ERR_HIP;
-  }
+  CQL_MEMSET(read_map, 0, (size_t)n_items, s, "mark_read_rows");
   if (n_states <= 0) return CQLREC_OK;
   CqlProfScope prof(CQLREC_PH_GATHER_BWD, s);
   hipLaunchKernelGGL(mark_read_rows_kernel, dim3(cql_ceil_div(n_states * (L + 1), 256)), dim3(256), 0, s, offsets, items,
@@ -366,12 +344,12 @@ OhWs oh_carve(void* ws, int64_t batch, int32_t d) {
   char* p = (char*)ws;
   OhWs w;
   const int64_t n_chunks = (batch + OH_CH - 1) / OH_CH;
-  w.keys_in = (uint32_t*)p;     p += a256(batch * 4);
-  w.vals_in = (uint32_t*)p;     p += a256(batch * 4);
-  w.keys_out = (uint32_t*)p;    p += a256(batch * 4);
-  w.vals_out = (uint32_t*)p;    p += a256(batch * 4);
-  w.edge = (float*)p;           p += a256(n_chunks * 2 * d * 4);
-  w.edge_w = (float*)p;         p += a256(n_chunks * 2 * 4);
+  w.keys_in = (uint32_t*)p;     p += cql_align256(batch * 4);
+  w.vals_in = (uint32_t*)p;     p += cql_align256(batch * 4);
+  w.keys_out = (uint32_t*)p;    p += cql_align256(batch * 4);
+  w.vals_out = (uint32_t*)p;    p += cql_align256(batch * 4);
+  w.edge = (float*)p;           p += cql_align256(n_chunks * 2 * d * 4);
+  w.edge_w = (float*)p;         p += cql_align256(n_chunks * 2 * 4);
   w.temp = p;
   w.temp_cap = (size_t)sort_temp_bound(batch);
   w.total = (int64_t)(p - (char*)ws) + (int64_t)w.temp_cap;
@@ -395,19 +373,9 @@ int cql_onehot_prepare(const int32_t* act, int64_t batch, int64_t n_items, int32
   const OhWs w = oh_carve(ws, batch, d);
   CqlProfScope prof(CQLREC_PH_GATHER_BWD, s);
   hipLaunchKernelGGL(onehot_pairs_kernel, dim3(cql_ceil_div(batch, 256)), dim3(256), 0, s, act, batch, w.keys_in, w.vals_in);
-  size_t need = 0;
-  hipError_t e = rocprim::radix_sort_pairs(nullptr, need, w.keys_in, w.keys_out, w.vals_in, w.vals_out, (size_t)batch, 0u,
-                                           key_bits(n_items), s);
-  if (e != hipSuccess || need > w.temp_cap) {
-    cql_set_error("onehot_prepare: radix sort needs %zu bytes of scratch (have %zu), err=%d", need, w.temp_cap, (int)e);
-    return CQLREC_ERR_HIP;
-  }
-  e = rocprim::radix_sort_pairs(w.temp, need, w.keys_in, w.keys_out, w.vals_in, w.vals_out, (size_t)batch, 0u,
+  const int rc = cql_sort_pairs("onehot_prepare", w.temp, w.temp_cap, w.keys_in, w.keys_out, w.vals_in, w.vals_out, batch,
                                 key_bits(n_items), s);
-  if (e != hipSuccess) {
-    cql_set_error("onehot_prepare: radix sort failed: %s", hipGetErrorString(e));
-    return CQLREC_ERR_HIP;
-  }
+  if (rc != CQLREC_OK) return rc;
   CQL_LAUNCH_CHECK("onehot_prepare");
   return CQLREC_OK;
 }

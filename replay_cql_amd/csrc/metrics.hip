@@ -10,11 +10,8 @@
 // All arithmetic in fp64; sums are per-block partials + one final pass (as eval_topk_kernel); the only atomics are
 // integer atomicMin / atomicAdd, whose results do not depend on the order of arrival.
 #include <climits>
-#include <rocprim/device/device_radix_sort.hpp>
 
-#include "common.h"
-
-static inline int64_t mx_a256(int64_t x) { return (x + 255) / 256 * 256; }
+#include "segment_common.h"
 
 #define MX_MAX_KS 8
 struct MxKs {
@@ -39,10 +36,6 @@ static int mx_take_ks(const int32_t* ks, int32_t n_ks, int32_t kmax, const char*
 // =============================================================================================================
 // (a) frame -> block
 // =============================================================================================================
-__global__ void mx_iota_kernel(uint32_t* p, int64_t n) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) p[i] = (uint32_t)i;
-}
 __global__ void mx_key_item_kernel(const int32_t* __restrict__ item, const uint32_t* __restrict__ perm, int64_t n,
                                    uint64_t* __restrict__ key) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -65,14 +58,6 @@ __global__ void mx_key_row_kernel(const int32_t* __restrict__ row, const uint32_
   if (i >= n) return;
   const int64_t r = row[perm[i]];
   key[i] = (uint64_t)((r < 0 || r >= n_users) ? n_users : r);
-}
-// off[u] = first sorted position whose bucket >= u, u = 0..n_users+1
-__global__ void mx_offsets_kernel(const uint64_t* __restrict__ key, int64_t n, int64_t n_users, int64_t* __restrict__ off) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i > n) return;
-  const int64_t cur = (i < n) ? (int64_t)key[i] : n_users + 1;
-  const int64_t prev = (i > 0) ? (int64_t)key[i - 1] : -1;
-  for (int64_t u = prev + 1; u <= cur; ++u) off[u] = i;
 }
 __global__ __launch_bounds__(256) void mx_block_kernel(const int64_t* __restrict__ off, const uint32_t* __restrict__ perm,
                                                        const int32_t* __restrict__ item, const double* __restrict__ rel,
@@ -111,11 +96,9 @@ __global__ __launch_bounds__(256) void mx_block_kernel(const int64_t* __restrict
   }
 }
 
-static int64_t mx_sort_temp_bytes(int64_t n_rows) { return mx_a256(4 * n_rows * 8) + (16ll << 20); }
-
 extern "C" int64_t cqlrec_recs_frame_to_block_ws_bytes(int64_t n_rows, int64_t n_users) {
   if (n_rows < 0 || n_users < 0) return -1;
-  return 2 * mx_a256(n_rows * 4) + 2 * mx_a256(n_rows * 8) + mx_a256((n_users + 2) * 8) + mx_sort_temp_bytes(n_rows) + 256;
+  return CqlPermSort::bytes(n_rows) + cql_align256((n_users + 2) * 8) + cql_sort_temp_cap(n_rows) + 256;
 }
 
 extern "C" int cqlrec_recs_frame_to_block(const int32_t* row, const int32_t* item_idx, const double* relevance,
@@ -137,44 +120,22 @@ extern "C" int cqlrec_recs_frame_to_block(const int32_t* row, const int32_t* ite
     return CQLREC_OK;
   }
   char* p = (char*)ws;
-  uint32_t* perm_a = (uint32_t*)p;  p += mx_a256(n_rows * 4);
-  uint32_t* perm_b = (uint32_t*)p;  p += mx_a256(n_rows * 4);
-  uint64_t* key_a = (uint64_t*)p;   p += mx_a256(n_rows * 8);
-  uint64_t* key_b = (uint64_t*)p;   p += mx_a256(n_rows * 8);
-  int64_t* off = (int64_t*)p;       p += mx_a256((n_users + 2) * 8);
-  void* temp = p;
-  const size_t temp_cap = (size_t)mx_sort_temp_bytes(n_rows);
+  CqlPermSort ps(p, n_rows, s);
+  int64_t* off = (int64_t*)p;       p += cql_align256((n_users + 2) * 8);
+  ps.temp = p;
   const dim3 grid(cql_ceil_div(n_rows, 256));
-  hipLaunchKernelGGL(mx_iota_kernel, grid, block, 0, s, perm_a, n_rows);
+  cql_iota(ps.perm, n_rows, false, s);
   // LSD over (user, relevance desc, item asc): the least significant key first, every pass a STABLE sort
-  for (int which = 0; which < 3; ++which) {
-    unsigned bits = 64;
-    if (which == 0) {
-      hipLaunchKernelGGL(mx_key_item_kernel, grid, block, 0, s, item_idx, perm_a, n_rows, key_a);
-      bits = 32;
-    } else if (which == 1) {
-      hipLaunchKernelGGL(mx_key_rel_kernel, grid, block, 0, s, relevance, perm_a, n_rows, key_a);
-    } else {
-      hipLaunchKernelGGL(mx_key_row_kernel, grid, block, 0, s, row, perm_a, n_rows, n_users, key_a);
-      bits = (unsigned)(64 - __builtin_clzll((unsigned long long)n_users));
-    }
-    size_t need = 0;
-    hipError_t e = rocprim::radix_sort_pairs(nullptr, need, key_a, key_b, perm_a, perm_b, (size_t)n_rows, 0u, bits, s);
-    if (e != hipSuccess || need > temp_cap) {
-      cql_set_error("recs_frame_to_block: radix sort needs %zu bytes of scratch (have %zu), err=%d", need, temp_cap, (int)e);
-      return CQLREC_ERR_HIP;
-    }
-    e = rocprim::radix_sort_pairs(temp, need, key_a, key_b, perm_a, perm_b, (size_t)n_rows, 0u, bits, s);
-    if (e != hipSuccess) {
-      cql_set_error("recs_frame_to_block: radix sort failed: %s", hipGetErrorString(e));
-      return CQLREC_ERR_HIP;
-    }
-    uint32_t* t = perm_a;
-    perm_a = perm_b;
-    perm_b = t;
-  }
-  hipLaunchKernelGGL(mx_offsets_kernel, dim3(cql_ceil_div(n_rows + 1, 256)), block, 0, s, key_b, n_rows, n_users, off);
-  hipLaunchKernelGGL(mx_block_kernel, ugrid, block, 0, s, off, perm_a, item_idx, relevance, payload, n_users, (int)kmax,
+  int rc;
+  hipLaunchKernelGGL(mx_key_item_kernel, grid, block, 0, s, item_idx, ps.perm, n_rows, ps.keys<uint64_t>());
+  if ((rc = ps.pass<uint64_t>("recs_frame_to_block", 32)) != CQLREC_OK) return rc;
+  hipLaunchKernelGGL(mx_key_rel_kernel, grid, block, 0, s, relevance, ps.perm, n_rows, ps.keys<uint64_t>());
+  if ((rc = ps.pass<uint64_t>("recs_frame_to_block", 64)) != CQLREC_OK) return rc;
+  hipLaunchKernelGGL(mx_key_row_kernel, grid, block, 0, s, row, ps.perm, n_rows, n_users, ps.keys<uint64_t>());
+  if ((rc = ps.pass<uint64_t>("recs_frame_to_block", cql_bits_for(n_users + 1))) != CQLREC_OK) return rc;   // bucket n_users
+  // off[u] = first sorted position whose bucket >= u, u = 0..n_users+1
+  cql_segment_bounds(CqlGroupOfKey<uint64_t>{ps.sorted<uint64_t>()}, n_rows, n_users + 1, off, nullptr, s);
+  hipLaunchKernelGGL(mx_block_kernel, ugrid, block, 0, s, off, ps.perm, item_idx, relevance, payload, n_users, (int)kmax,
                      (int)dedup, rec_idx, rec_val, rec_pos, rec_w);
   CQL_LAUNCH_CHECK("recs_frame_to_block");
   return CQLREC_OK;
@@ -381,7 +342,7 @@ __global__ void mx_final_kernel(const double* __restrict__ block_sums, int nbloc
 
 extern "C" int64_t cqlrec_eval_extras_ws_bytes(int64_t n_users, int32_t n_ks) {
   if (n_users < 0 || n_ks < 0) return -1;
-  return mx_a256((int64_t)cql_ceil_div(n_users, 256) * CQLREC_EVAL_EXTRAS * n_ks * 8) + 256;
+  return cql_align256((int64_t)cql_ceil_div(n_users, 256) * CQLREC_EVAL_EXTRAS * n_ks * 8) + 256;
 }
 
 extern "C" int cqlrec_eval_extras(const int32_t* rec_idx, int64_t n_users, int32_t kmax, const int32_t* rec_rows,
@@ -431,7 +392,7 @@ __global__ void mx_pair_heads_kernel(const uint64_t* __restrict__ key, int64_t n
 
 extern "C" int64_t cqlrec_eval_item_user_counts_ws_bytes(int64_t n_rows) {
   if (n_rows < 0) return -1;
-  return 2 * mx_a256(n_rows * 8) + mx_sort_temp_bytes(n_rows) + 256;
+  return 2 * cql_align256(n_rows * 8) + cql_sort_temp_cap(n_rows) + 256;
 }
 
 extern "C" int cqlrec_eval_item_user_counts(const int32_t* item_idx, const int32_t* user_idx, int64_t n_rows,
@@ -443,27 +404,16 @@ extern "C" int cqlrec_eval_item_user_counts(const int32_t* item_idx, const int32
   CQL_REQUIRE(ws_bytes >= cqlrec_eval_item_user_counts_ws_bytes(n_rows), "eval_item_user_counts: workspace too small");
   hipStream_t s = (hipStream_t)stream;
   char* p = (char*)ws;
-  uint64_t* key_a = (uint64_t*)p;   p += mx_a256(n_rows * 8);
-  uint64_t* key_b = (uint64_t*)p;   p += mx_a256(n_rows * 8);
+  uint64_t* key_a = (uint64_t*)p;   p += cql_align256(n_rows * 8);
+  uint64_t* key_b = (uint64_t*)p;   p += cql_align256(n_rows * 8);
   void* temp = p;
-  const size_t temp_cap = (size_t)mx_sort_temp_bytes(n_rows);
+  const size_t temp_cap = (size_t)cql_sort_temp_cap(n_rows);
   const dim3 grid(cql_ceil_div(n_rows, 256)), block(256);
   hipLaunchKernelGGL(mx_pair_key_kernel, grid, block, 0, s, item_idx, user_idx, n_rows, key_a);
-  size_t need = 0;
-  hipError_t e = rocprim::radix_sort_keys(nullptr, need, key_a, key_b, (size_t)n_rows, 0u, 64u, s);
-  if (e != hipSuccess || need > temp_cap) {
-    cql_set_error("eval_item_user_counts: radix sort needs %zu bytes of scratch (have %zu), err=%d", need, temp_cap, (int)e);
-    return CQLREC_ERR_HIP;
-  }
-  e = rocprim::radix_sort_keys(temp, need, key_a, key_b, (size_t)n_rows, 0u, 64u, s);
-  if (e != hipSuccess) {
-    cql_set_error("eval_item_user_counts: radix sort failed: %s", hipGetErrorString(e));
-    return CQLREC_ERR_HIP;
-  }
-  if (hipMemsetAsync(cnt, 0, (size_t)n_items * 4, s) != hipSuccess || hipMemsetAsync(n_distinct_users, 0, 8, s) != hipSuccess) {
-    cql_set_error("eval_item_user_counts: memset failed");
-    return CQLREC_ERR_HIP;
-  }
+  const int rc = cql_sort_keys("eval_item_user_counts", temp, temp_cap, key_a, key_b, n_rows, 64, s);
+  if (rc != CQLREC_OK) return rc;
+  CQL_MEMSET(cnt, 0, (size_t)n_items * 4, s, "eval_item_user_counts");
+  CQL_MEMSET(n_distinct_users, 0, 8, s, "eval_item_user_counts");
   hipLaunchKernelGGL(mx_pair_heads_kernel, grid, block, 0, s, key_b, n_rows, n_items, cnt,
                      (unsigned long long*)n_distinct_users);
   CQL_LAUNCH_CHECK("eval_item_user_counts");
@@ -555,10 +505,7 @@ extern "C" int cqlrec_eval_item_hist(const int32_t* rec_idx, int64_t n_users, in
   CQL_REQUIRE(n_users > 0 && kmax > 0 && n_items > 0, "eval_item_hist: n_users=%lld kmax=%d n_items=%lld", (long long)n_users,
               kmax, (long long)n_items);
   hipStream_t s = (hipStream_t)stream;
-  if (hipMemsetAsync(cnt, 0, (size_t)n_items * 4, s) != hipSuccess) {
-    cql_set_error("eval_item_hist: memset failed");
-    return CQLREC_ERR_HIP;
-  }
+  CQL_MEMSET(cnt, 0, (size_t)n_items * 4, s, "eval_item_hist");
   hipLaunchKernelGGL(mx_item_hist_kernel, dim3(cql_ceil_div(n_users * kmax, 256)), dim3(256), 0, s, rec_idx,
                      n_users * (int64_t)kmax, n_items, cnt);
   CQL_LAUNCH_CHECK("eval_item_hist");

@@ -9,47 +9,11 @@
 // order, which the expansion produces and the stable sort keeps: up to NB_SHORT terms left to right by one thread, more
 // by one wave (lane l takes the terms l, l + 64, ... in that order, then a butterfly over the lanes).  How the query
 // rows are cut into chunks therefore never shows in the result.
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_run_length_encode.hpp>
-#include <rocprim/device/device_scan.hpp>
+#include "segment_common.h"
 
-#include "common.h"
-
-static inline int64_t a256(int64_t x) { return (x + 255) / 256 * 256; }
 static const int64_t NB_MAX = 1ll << 31;
 static const int NB_SHORT = 32;
 static const uint32_t NB_PAD = 0xFFFFFFFFu;
-static inline int64_t sort_temp_cap(int64_t n) { return a256(4 * n * 8) + (16ll << 20); }
-static inline int64_t scan_temp_cap(int64_t n) { return a256(n * 8) + (1ll << 20); }
-
-#define NB_ROCPRIM(call, what)                                                           \
-  do {                                                                                   \
-    hipError_t e__ = (call);                                                             \
-    if (e__ != hipSuccess) {                                                             \
-      cql_set_error("%s: rocPRIM failed: %s", what, hipGetErrorString(e__));             \
-      return CQLREC_ERR_HIP;                                                             \
-    }                                                                                    \
-  } while (0)
-#define NB_TEMP_FITS(need, cap, what)                                                    \
-  do {                                                                                   \
-    if ((need) > (size_t)(cap)) {                                                        \
-      cql_set_error("%s: rocPRIM needs %zu bytes of scratch (have %zu)", what, (size_t)(need), (size_t)(cap)); \
-      return CQLREC_ERR_HIP;                                                             \
-    }                                                                                    \
-  } while (0)
-#define NB_MEMSET(ptr, val, bytes, what)                                                 \
-  do {                                                                                   \
-    if (hipMemsetAsync(ptr, val, bytes, s) != hipSuccess) {                              \
-      cql_set_error("%s: memset failed", what);                                          \
-      return CQLREC_ERR_HIP;                                                             \
-    }                                                                                    \
-  } while (0)
-
-static inline unsigned bits_for(int64_t n) {
-  unsigned bits = 1;
-  while (bits < 62 && (1ll << bits) < n) ++bits;
-  return bits;
-}
 
 __device__ __forceinline__ double nb_wave_sum(double acc) {
 #pragma unroll
@@ -134,7 +98,7 @@ extern "C" int cqlrec_neighbour_norms(const int32_t* perm, const int64_t* offset
   CQL_REQUIRE(norm, "neighbour_norms: NULL pointer");
   hipStream_t s = (hipStream_t)stream;
   if (n_rows == 0) {
-    NB_MEMSET(norm, 0, (size_t)n_groups * 8, "neighbour_norms");
+    CQL_MEMSET(norm, 0, (size_t)n_groups * 8, s, "neighbour_norms");
     return CQLREC_OK;
   }
   CQL_REQUIRE(perm && offsets && w, "neighbour_norms: NULL pointer");
@@ -175,7 +139,7 @@ __global__ void neighbour_row_prefix_kernel(const int64_t* __restrict__ l_off, c
 
 extern "C" int64_t cqlrec_neighbour_count_ws_bytes(int64_t nnz_l) {
   if (nnz_l < 0 || nnz_l >= NB_MAX) return 0;
-  return a256((nnz_l + 1) * 8) + scan_temp_cap(nnz_l + 1) + 256;
+  return cql_align256((nnz_l + 1) * 8) + cql_scan_temp_cap(nnz_l + 1) + 256;
 }
 
 extern "C" int cqlrec_neighbour_count(const int64_t* l_off, const int32_t* l_col, int64_t n_q, int64_t nnz_l,
@@ -190,19 +154,15 @@ extern "C" int cqlrec_neighbour_count(const int64_t* l_off, const int32_t* l_col
     CQL_REQUIRE(l_off && entry_prefix && row_prefix && ws && (nnz_l == 0 || (l_col && r_off)), "neighbour_count: NULL pointer");
     CQL_REQUIRE(ws_bytes >= cqlrec_neighbour_count_ws_bytes(nnz_l), "neighbour_count: workspace too small");
   }
-  NB_MEMSET(stats, 0, 16, "neighbour_count");
+  CQL_MEMSET(stats, 0, 16, s, "neighbour_count");
   if (n_q == 0) return CQLREC_OK;
   char* p = (char*)ws;
-  int64_t* len = (int64_t*)p;  p += a256((nnz_l + 1) * 8);
+  int64_t* len = (int64_t*)p;  p += cql_align256((nnz_l + 1) * 8);
   void* temp = p;
-  const size_t cap = (size_t)scan_temp_cap(nnz_l + 1);
+  const size_t cap = (size_t)cql_scan_temp_cap(nnz_l + 1);
   hipLaunchKernelGGL(neighbour_len_kernel, dim3(cql_ceil_div(nnz_l + 1, 256)), dim3(256), 0, s, l_col, r_off, nnz_l, len);
-  size_t need = 0;
-  NB_ROCPRIM(rocprim::exclusive_scan(nullptr, need, len, entry_prefix, (int64_t)0, (size_t)(nnz_l + 1),
-                                     rocprim::plus<int64_t>(), s), "neighbour_count");
-  NB_TEMP_FITS(need, cap, "neighbour_count");
-  NB_ROCPRIM(rocprim::exclusive_scan(temp, need, len, entry_prefix, (int64_t)0, (size_t)(nnz_l + 1),
-                                     rocprim::plus<int64_t>(), s), "neighbour_count");
+  const int rc = cql_exclusive_scan("neighbour_count", temp, cap, len, entry_prefix, (int64_t)0, nnz_l + 1, s);
+  if (rc != CQLREC_OK) return rc;
   hipLaunchKernelGGL(neighbour_row_prefix_kernel, dim3(cql_ceil_div(n_q + 1, 256)), dim3(256), 0, s, l_off, entry_prefix, n_q,
                      nnz_l, row_prefix, stats);
   CQL_LAUNCH_CHECK("neighbour_count");
@@ -355,15 +315,6 @@ __global__ void neighbour_row_key_kernel(NbChunk C, const uint64_t* __restrict__
   const uint32_t p = payload[i];
   row_key[i] = p == NB_PAD ? (uint32_t)C.rows : (uint32_t)(ukey[p] >> C.jbits);
 }
-// row_start[g] = the first sorted position whose row is >= g, for g in [0, rows + 1]
-__global__ void neighbour_bounds_kernel(const uint32_t* __restrict__ row_key, int64_t T, int64_t rows,
-                                        int64_t* __restrict__ row_start) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i > T) return;
-  const int64_t cur = (i < T) ? (int64_t)row_key[i] : rows + 1;
-  const int64_t prev = (i > 0) ? (int64_t)row_key[i - 1] : -1;
-  for (int64_t g = prev + 1; g <= cur; ++g) row_start[g] = i;
-}
 __global__ void neighbour_write_kernel(NbChunk C, const uint64_t* __restrict__ ukey, const double* __restrict__ csum,
                                        const uint32_t* __restrict__ row_key, const uint32_t* __restrict__ payload,
                                        const int64_t* __restrict__ row_start, int32_t k, int32_t* __restrict__ ids,
@@ -403,7 +354,8 @@ extern "C" int64_t cqlrec_neighbour_topk_ws_bytes(int64_t n_q, int64_t n_cols, i
     return 0;
   const int64_t cap = nb_cap(max_tuples, largest_row);
   if (cap >= NB_MAX) return 0;
-  return 4 * a256(cap * 8) + 6 * a256(cap * 4) + a256((n_q + 2) * 8) + 256 + sort_temp_cap(cap) + 256;
+  return 4 * cql_align256(cap * 8) + 6 * cql_align256(cap * 4) + cql_align256((n_q + 2) * 8) + 256 + cql_sort_temp_cap(cap) +
+         256;
 }
 
 extern "C" int cqlrec_neighbour_topk(int32_t mode, const int64_t* l_off, const int32_t* l_col, const double* l_val,
@@ -443,30 +395,29 @@ extern "C" int cqlrec_neighbour_topk(int32_t mode, const int64_t* l_off, const i
   hipStream_t s = (hipStream_t)stream;
   const dim3 block(256);
   hipLaunchKernelGGL(neighbour_fill_kernel, dim3(cql_ceil_div(n_q * (int64_t)k, 256)), block, 0, s, n_q * (int64_t)k, ids, vals);
-  NB_MEMSET(count, 0, (size_t)n_q * 4, "neighbour_topk");
+  CQL_MEMSET(count, 0, (size_t)n_q * 4, s, "neighbour_topk");
   if (total == 0) {
     CQL_LAUNCH_CHECK("neighbour_topk");
     return CQLREC_OK;
   }
   const int64_t cap = nb_cap(max_tuples, largest_row);
   char* p = (char*)ws;
-  uint64_t* A8 = (uint64_t*)p;      p += a256(cap * 8);
-  uint64_t* B8 = (uint64_t*)p;      p += a256(cap * 8);
-  double* C8 = (double*)p;          p += a256(cap * 8);
-  double* D8 = (double*)p;          p += a256(cap * 8);
-  uint32_t* seg_off = (uint32_t*)p; p += a256(cap * 4);
-  uint32_t* runs = (uint32_t*)p;    p += a256(cap * 4);
-  uint32_t* F4 = (uint32_t*)p;      p += a256(cap * 4);
-  uint32_t* G4 = (uint32_t*)p;      p += a256(cap * 4);
-  uint32_t* H4 = (uint32_t*)p;      p += a256(cap * 4);
-  uint32_t* I4 = (uint32_t*)p;      p += a256(cap * 4);
-  int64_t* row_start = (int64_t*)p; p += a256((n_q + 2) * 8);
+  uint64_t* A8 = (uint64_t*)p;      p += cql_align256(cap * 8);
+  uint64_t* B8 = (uint64_t*)p;      p += cql_align256(cap * 8);
+  double* C8 = (double*)p;          p += cql_align256(cap * 8);
+  double* D8 = (double*)p;          p += cql_align256(cap * 8);
+  uint32_t* seg_off = (uint32_t*)p; p += cql_align256(cap * 4);
+  uint32_t* runs = (uint32_t*)p;    p += cql_align256(cap * 4);
+  uint32_t* F4 = (uint32_t*)p;      p += cql_align256(cap * 4);
+  uint32_t* G4 = (uint32_t*)p;      p += cql_align256(cap * 4);
+  uint32_t* H4 = (uint32_t*)p;      p += cql_align256(cap * 4);
+  uint32_t* I4 = (uint32_t*)p;      p += cql_align256(cap * 4);
+  int64_t* row_start = (int64_t*)p; p += cql_align256((n_q + 2) * 8);
   size_t* n_runs = (size_t*)p;
   uint32_t* n_long = (uint32_t*)(p + 8);
   p += 256;
   void* temp = p;
-  const size_t temp_cap = (size_t)sort_temp_cap(cap);
-  static_assert(sizeof(size_t) == sizeof(int64_t), "the count is written as size_t");
+  const size_t temp_cap = (size_t)cql_sort_temp_cap(cap);
 
   NbEpilogue E = {};
   E.mode = mode;
@@ -476,7 +427,7 @@ extern "C" int cqlrec_neighbour_topk(int32_t mode, const int64_t* l_off, const i
   E.mask = mask;
   E.seen_off = seen_off;
   E.seen_col = seen_col;
-  const unsigned jbits = bits_for(n_cols);
+  const unsigned jbits = cql_bits_for(n_cols);
   const char* what = "neighbour_topk";
   int64_t q0 = 0;
   while (q0 < n_q) {
@@ -492,35 +443,26 @@ extern "C" int cqlrec_neighbour_topk(int32_t mode, const int64_t* l_off, const i
     if (C.T == 0) continue;
     const int64_t T = C.T;
     const dim3 grid(cql_ceil_div(T, 256));
-    const unsigned qbits = bits_for(C.rows + 1);         // the row past the chunk is representable
-    size_t need = 0;
+    const unsigned qbits = cql_bits_for(C.rows + 1);         // the row past the chunk is representable
+    int rc;
     // expand: (A8, C8); sort: (B8, D8)
     hipLaunchKernelGGL(neighbour_expand_kernel, grid, block, 0, s, C, l_off, l_col, l_val, r_off, r_col, r_val, entry_prefix,
                        n_cols, A8, C8);
-    NB_ROCPRIM(rocprim::radix_sort_pairs(nullptr, need, A8, B8, C8, D8, (size_t)T, 0u, jbits + qbits, s), what);
-    NB_TEMP_FITS(need, temp_cap, what);
-    NB_ROCPRIM(rocprim::radix_sort_pairs(temp, need, A8, B8, C8, D8, (size_t)T, 0u, jbits + qbits, s), what);
+    if ((rc = cql_sort_pairs(what, temp, temp_cap, A8, B8, C8, D8, T, jbits + qbits, s)) != CQLREC_OK) return rc;
     // reduce: the distinct keys (A8), their run lengths and first positions, their sums (C8)
-    NB_ROCPRIM(rocprim::run_length_encode(nullptr, need, B8, (unsigned int)T, A8, runs, n_runs, s), what);
-    NB_TEMP_FITS(need, temp_cap, what);
-    NB_ROCPRIM(rocprim::run_length_encode(temp, need, B8, (unsigned int)T, A8, runs, n_runs, s), what);
-    NB_ROCPRIM(rocprim::exclusive_scan(nullptr, need, runs, seg_off, 0u, (size_t)T, rocprim::plus<uint32_t>(), s), what);
-    NB_TEMP_FITS(need, temp_cap, what);
-    NB_ROCPRIM(rocprim::exclusive_scan(temp, need, runs, seg_off, 0u, (size_t)T, rocprim::plus<uint32_t>(), s), what);
-    NB_MEMSET(n_long, 0, 4, what);
+    if ((rc = cql_run_length_encode(what, temp, temp_cap, B8, T, A8, runs, n_runs, s)) != CQLREC_OK) return rc;
+    if ((rc = cql_exclusive_scan(what, temp, temp_cap, runs, seg_off, 0u, T, s)) != CQLREC_OK) return rc;
+    CQL_MEMSET(n_long, 0, 4, s, what);
     hipLaunchKernelGGL(neighbour_sum_short_kernel, grid, block, 0, s, D8, seg_off, runs, n_runs, C8, H4, n_long);
     const int long_blocks = cql_ceil_div(T / NB_SHORT + 1, 4) < 2048 ? cql_ceil_div(T / NB_SHORT + 1, 4) : 2048;
     hipLaunchKernelGGL(neighbour_sum_long_kernel, dim3(long_blocks), block, 0, s, D8, seg_off, runs, H4, n_long, C8);
     // select: by value (B8, F4) -> (D8 as keys, G4), then by row (H4, G4) -> (I4, F4)
     hipLaunchKernelGGL(neighbour_epilogue_kernel, grid, block, 0, s, C, E, A8, n_runs, C8, B8, F4);
-    NB_ROCPRIM(rocprim::radix_sort_pairs(nullptr, need, B8, (uint64_t*)D8, F4, G4, (size_t)T, 0u, 64u, s), what);
-    NB_TEMP_FITS(need, temp_cap, what);
-    NB_ROCPRIM(rocprim::radix_sort_pairs(temp, need, B8, (uint64_t*)D8, F4, G4, (size_t)T, 0u, 64u, s), what);
+    if ((rc = cql_sort_pairs(what, temp, temp_cap, B8, (uint64_t*)D8, F4, G4, T, 64, s)) != CQLREC_OK) return rc;
     hipLaunchKernelGGL(neighbour_row_key_kernel, grid, block, 0, s, C, A8, G4, H4);
-    NB_ROCPRIM(rocprim::radix_sort_pairs(nullptr, need, H4, I4, G4, F4, (size_t)T, 0u, qbits, s), what);
-    NB_TEMP_FITS(need, temp_cap, what);
-    NB_ROCPRIM(rocprim::radix_sort_pairs(temp, need, H4, I4, G4, F4, (size_t)T, 0u, qbits, s), what);
-    hipLaunchKernelGGL(neighbour_bounds_kernel, dim3(cql_ceil_div(T + 1, 256)), block, 0, s, I4, T, C.rows, row_start);
+    if ((rc = cql_sort_pairs(what, temp, temp_cap, H4, I4, G4, F4, T, qbits, s)) != CQLREC_OK) return rc;
+    // row_start[g] = the first sorted position whose row is >= g, for g in [0, rows + 1]
+    cql_segment_bounds(CqlGroupOfKey<uint32_t>{I4}, T, C.rows + 1, row_start, nullptr, s);
     hipLaunchKernelGGL(neighbour_write_kernel, grid, block, 0, s, C, A8, C8, I4, F4, row_start, k, ids, vals, count);
     CQL_LAUNCH_CHECK(what);
   }

@@ -4,19 +4,12 @@
 //   f4  quality metrics of a [users x k] recommendation block against a ground-truth CSR, the per-user formulas of
 //       replay/metrics/{ndcg,hitrate,precision,recall,map,mrr}.py::_get_metric_value_by_user.
 #include <cstring>
-#include <rocprim/device/device_radix_sort.hpp>
 
-#include "common.h"
-
-static inline int64_t a256(int64_t x) { return (x + 255) / 256 * 256; }
+#include "segment_common.h"
 
 // =============================================================================================================
 // f2  CSR builder
 // =============================================================================================================
-__global__ void iota_kernel(uint32_t* p, int64_t n) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) p[i] = (uint32_t)i;
-}
 template <typename K, typename S>
 __global__ void gather_key_kernel(const S* __restrict__ src, const uint32_t* __restrict__ perm, int64_t n, K* dst,
                                   K bias) {
@@ -32,7 +25,7 @@ __global__ void csr_finish_kernel(const int32_t* __restrict__ user_idx, const in
   // offsets[u] = first sorted position whose user >= u: fill the gap between consecutive users
   const int64_t cur = (i < n) ? (int64_t)user_idx[perm[i]] : n_users;
   const int64_t prev = (i > 0) ? (int64_t)user_idx[perm[i - 1]] : -1;
-  for (int64_t u = prev + 1; u <= cur; ++u) offsets[u] = i;
+  cql_fill_gap(prev, cur, i, offsets);
   if (i < n) {
     items[i] = item_idx[perm[i]];
     if (rewards) rewards[i] = (float)relevance[perm[i]];
@@ -40,7 +33,7 @@ __global__ void csr_finish_kernel(const int32_t* __restrict__ user_idx, const in
 }
 
 extern "C" int64_t cqlrec_build_csr_ws_bytes(int64_t n_rows) {
-  return 2 * a256(n_rows * 4) + 2 * a256(n_rows * 8) + a256(4 * n_rows * 8) + (16ll << 20) + 256;
+  return CqlPermSort::bytes(n_rows) + cql_sort_temp_cap(n_rows) + 256;
 }
 
 extern "C" int cqlrec_build_csr(const int32_t* user_idx, const int32_t* item_idx, const int64_t* timestamp,
@@ -55,53 +48,25 @@ extern "C" int cqlrec_build_csr(const int32_t* user_idx, const int32_t* item_idx
   CQL_REQUIRE(ws_bytes >= cqlrec_build_csr_ws_bytes(n_rows), "build_csr: workspace too small");
   hipStream_t s = (hipStream_t)stream;
   char* p = (char*)ws;
-  uint32_t* perm_a = (uint32_t*)p;  p += a256(n_rows * 4);
-  uint32_t* perm_b = (uint32_t*)p;  p += a256(n_rows * 4);
-  uint64_t* key_a = (uint64_t*)p;   p += a256(n_rows * 8);
-  uint64_t* key_b = (uint64_t*)p;   p += a256(n_rows * 8);
-  void* temp = p;
-  size_t temp_cap = (size_t)(a256(4 * n_rows * 8) + (16ll << 20));
+  CqlPermSort ps(p, n_rows, s);
+  ps.temp = p;
   const dim3 grid(cql_ceil_div(n_rows, 256)), block(256);
-  hipLaunchKernelGGL(iota_kernel, grid, block, 0, s, perm_a, n_rows);
+  cql_iota(ps.perm, n_rows, false, s);
   // LSD over the composite key: item (least significant), then timestamp, then user; every pass is a STABLE sort
-  auto pass = [&](int which) -> int {
-    int bits = 64;
-    if (which == 0) {
-      hipLaunchKernelGGL((gather_key_kernel<uint64_t, int32_t>), grid, block, 0, s, item_idx, perm_a, n_rows, key_a,
-                         (uint64_t)0);
-      bits = 32;
-    } else if (which == 1) {   // signed timestamps -> order-preserving unsigned
-      hipLaunchKernelGGL((gather_key_kernel<uint64_t, int64_t>), grid, block, 0, s, timestamp, perm_a, n_rows, key_a,
-                         (uint64_t)1 << 63);
-    } else {
-      hipLaunchKernelGGL((gather_key_kernel<uint64_t, int32_t>), grid, block, 0, s, user_idx, perm_a, n_rows, key_a,
-                         (uint64_t)0);
-      bits = 32;
-    }
-    size_t need = 0;
-    hipError_t e = rocprim::radix_sort_pairs(nullptr, need, key_a, key_b, perm_a, perm_b, (size_t)n_rows, 0u,
-                                             (unsigned)bits, s);
-    if (e != hipSuccess || need > temp_cap) {
-      cql_set_error("build_csr: radix sort needs %zu bytes of scratch (have %zu), err=%d", need, temp_cap, (int)e);
-      return CQLREC_ERR_HIP;
-    }
-    e = rocprim::radix_sort_pairs(temp, need, key_a, key_b, perm_a, perm_b, (size_t)n_rows, 0u, (unsigned)bits, s);
-    if (e != hipSuccess) {
-      cql_set_error("build_csr: radix sort failed: %s", hipGetErrorString(e));
-      return CQLREC_ERR_HIP;
-    }
-    uint32_t* t = perm_a;
-    perm_a = perm_b;
-    perm_b = t;
-    return CQLREC_OK;
-  };
-  for (int w = 0; w < 3; ++w) {
-    if (w == 1 && !timestamp) continue;
-    const int rc = pass(w);
-    if (rc != CQLREC_OK) return rc;
+  int rc;
+  hipLaunchKernelGGL((gather_key_kernel<uint64_t, int32_t>), grid, block, 0, s, item_idx, ps.perm, n_rows,
+                     ps.keys<uint64_t>(), (uint64_t)0);
+  if ((rc = ps.pass<uint64_t>("build_csr", 32)) != CQLREC_OK) return rc;
+  if (timestamp) {   // signed timestamps -> order-preserving unsigned
+    hipLaunchKernelGGL((gather_key_kernel<uint64_t, int64_t>), grid, block, 0, s, timestamp, ps.perm, n_rows,
+                       ps.keys<uint64_t>(), (uint64_t)1 << 63);
+    if ((rc = ps.pass<uint64_t>("build_csr", 64)) != CQLREC_OK) return rc;
   }
+  hipLaunchKernelGGL((gather_key_kernel<uint64_t, int32_t>), grid, block, 0, s, user_idx, ps.perm, n_rows,
+                     ps.keys<uint64_t>(), (uint64_t)0);
+  if ((rc = ps.pass<uint64_t>("build_csr", 32)) != CQLREC_OK) return rc;
   hipLaunchKernelGGL(csr_finish_kernel, dim3(cql_ceil_div(n_rows + 1, 256)), block, 0, s, user_idx, item_idx, relevance,
-                     perm_a, n_rows, n_users, offsets, items, rewards);
+                     ps.perm, n_rows, n_users, offsets, items, rewards);
   CQL_LAUNCH_CHECK("build_csr");
   return CQLREC_OK;
 }
@@ -194,7 +159,7 @@ __global__ void eval_final_kernel(const double* __restrict__ block_sums, int nbl
 }
 
 extern "C" int64_t cqlrec_eval_topk_ws_bytes(int64_t n_users, int32_t n_ks) {
-  return a256((int64_t)cql_ceil_div(n_users, 256) * CQLREC_EVAL_METRICS * n_ks * 8) + 256;
+  return cql_align256((int64_t)cql_ceil_div(n_users, 256) * CQLREC_EVAL_METRICS * n_ks * 8) + 256;
 }
 
 extern "C" int cqlrec_eval_topk(const int32_t* rec_idx, int64_t n_users, int32_t kmax, const int32_t* rec_rows,

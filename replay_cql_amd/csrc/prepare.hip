@@ -7,54 +7,14 @@
 // Order inside a user: (key, key2, input row index), ranked DESCENDING as cqlrec_split_rank does -- stable LSD radix
 // passes over a row permutation that starts REVERSED (stability then keeps later rows first): key2, then key, then
 // user.  The ascending row number is count[u] + 1 - rank.
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_select.hpp>
-#include <rocprim/iterator/counting_iterator.hpp>
+#include "segment_common.h"
 
-#include "common.h"
-
-static inline int64_t a256(int64_t x) { return (x + 255) / 256 * 256; }
 static const int64_t PREPARE_MAX_ROWS = 1ll << 31;
-// scratch left for rocPRIM behind the explicit buffers (the bound split.hip and prep.hip use)
-static inline int64_t sort_temp_cap(int64_t n) { return a256(4 * n * 8) + (16ll << 20); }
-
-#define PREPARE_ROCPRIM(call, what)                                                      \
-  do {                                                                                   \
-    hipError_t e__ = (call);                                                             \
-    if (e__ != hipSuccess) {                                                             \
-      cql_set_error("%s: rocPRIM failed: %s", what, hipGetErrorString(e__));             \
-      return CQLREC_ERR_HIP;                                                             \
-    }                                                                                    \
-  } while (0)
-#define PREPARE_TEMP_FITS(need, cap, what)                                               \
-  do {                                                                                   \
-    if ((need) > (size_t)(cap)) {                                                        \
-      cql_set_error("%s: rocPRIM needs %zu bytes of scratch (have %zu)", what, (size_t)(need), (size_t)(cap)); \
-      return CQLREC_ERR_HIP;                                                             \
-    }                                                                                    \
-  } while (0)
-#define PREPARE_MEMSET(ptr, val, bytes, what)                                            \
-  do {                                                                                   \
-    if (hipMemsetAsync(ptr, val, bytes, s) != hipSuccess) {                              \
-      cql_set_error("%s: memset failed", what);                                          \
-      return CQLREC_ERR_HIP;                                                             \
-    }                                                                                    \
-  } while (0)
-
-static inline unsigned bits_for(int64_t n) {
-  unsigned bits = 1;
-  while (bits < 32 && (1ll << bits) < n) ++bits;
-  return bits;
-}
 
 // =============================================================================================================
 // rank inside the user under (key desc, key2 desc, row index desc)
 // =============================================================================================================
-__global__ void prepare_perm_init_kernel(int64_t n, uint32_t* __restrict__ perm) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) perm[i] = (uint32_t)(n - 1 - i);
-}
-// sort keys of the rows in their current order, for an ASCENDING sort: key2 and key reversed, the user as it is
+// sort keys of the rows in their current order, for an ASCENDING sort: key2 and key reversed
 __global__ void prepare_key2_kernel(const int32_t* __restrict__ key2, const uint32_t* __restrict__ perm, int64_t n,
                                     uint32_t top, uint32_t* __restrict__ out) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -65,36 +25,9 @@ __global__ void prepare_key_kernel(const int64_t* __restrict__ key, const uint32
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) out[i] = ~((uint64_t)key[perm[i]] ^ (1ull << 63));
 }
-__global__ void prepare_user_key_kernel(const int32_t* __restrict__ user_idx, const uint32_t* __restrict__ perm,
-                                        int64_t n, uint32_t* __restrict__ out) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) out[i] = (uint32_t)user_idx[perm[i]];
-}
-// offsets[u] = first sorted position whose user >= u
-__global__ void prepare_bounds_kernel(const int32_t* __restrict__ user_idx, const uint32_t* __restrict__ perm, int64_t n,
-                                      int64_t n_users, int64_t* __restrict__ offsets) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i > n) return;
-  const int64_t cur = (i < n) ? (int64_t)user_idx[perm[i]] : n_users;
-  const int64_t prev = (i > 0) ? (int64_t)user_idx[perm[i - 1]] : -1;
-  for (int64_t u = prev + 1; u <= cur; ++u) offsets[u] = i;
-}
-__global__ void prepare_rank_finish_kernel(const int32_t* __restrict__ user_idx, const uint32_t* __restrict__ perm,
-                                           int64_t n, const int64_t* __restrict__ offsets, int32_t* __restrict__ rank) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const uint32_t r = perm[i];
-  rank[r] = (int32_t)(i - offsets[user_idx[r]] + 1);
-}
-__global__ void prepare_rank_count_kernel(const int64_t* __restrict__ offsets, int64_t n_users,
-                                          int32_t* __restrict__ count) {
-  const int64_t u = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (u < n_users) count[u] = (int32_t)(offsets[u + 1] - offsets[u]);
-}
 
 extern "C" int64_t cqlrec_prepare_rank_ws_bytes(int64_t n_rows, int64_t n_users) {
-  if (n_rows < 0 || n_users < 0) return 0;
-  return 2 * a256(n_rows * 4) + 2 * a256(n_rows * 8) + a256((n_users + 1) * 8) + sort_temp_cap(n_rows) + 256;
+  return cql_rank_ws_bytes(n_rows, n_users);
 }
 
 extern "C" int cqlrec_prepare_rank(const int32_t* user_idx, const int64_t* key, const int32_t* key2, int64_t n_rows,
@@ -107,57 +40,26 @@ extern "C" int cqlrec_prepare_rank(const int32_t* user_idx, const int64_t* key, 
   CQL_REQUIRE(count, "prepare_rank: NULL pointer");
   hipStream_t s = (hipStream_t)stream;
   if (n_rows == 0) {
-    PREPARE_MEMSET(count, 0, (size_t)n_users * 4, "prepare_rank");
+    CQL_MEMSET(count, 0, (size_t)n_users * 4, s, "prepare_rank");
     return CQLREC_OK;
   }
   CQL_REQUIRE(user_idx && key && ws && rank, "prepare_rank: NULL pointer");
   CQL_REQUIRE(ws_bytes >= cqlrec_prepare_rank_ws_bytes(n_rows, n_users), "prepare_rank: workspace too small");
   char* p = (char*)ws;
-  uint32_t* cur = (uint32_t*)p;    p += a256(n_rows * 4);
-  uint32_t* other = (uint32_t*)p;  p += a256(n_rows * 4);
-  uint64_t* key_a = (uint64_t*)p;  p += a256(n_rows * 8);
-  uint64_t* key_b = (uint64_t*)p;  p += a256(n_rows * 8);
-  int64_t* offsets = (int64_t*)p;  p += a256((n_users + 1) * 8);
-  void* temp = p;
-  const size_t temp_cap = (size_t)sort_temp_cap(n_rows);
+  CqlPermSort ps(p, n_rows, s);
+  int64_t* offsets = (int64_t*)p;  p += cql_align256((n_users + 1) * 8);
+  ps.temp = p;
   const dim3 grid(cql_ceil_div(n_rows, 256)), block(256);
-  uint32_t* k32_a = (uint32_t*)key_a;
-  uint32_t* k32_b = (uint32_t*)key_b;
-  size_t need = 0;
-  hipLaunchKernelGGL(prepare_perm_init_kernel, grid, block, 0, s, n_rows, cur);
+  int rc;
+  cql_iota(ps.perm, n_rows, true, s);
   if (key2) {  // least significant: key2 descending, over the bits a value below n_key2 can have
-    const unsigned bits = bits_for(n_key2);
-    hipLaunchKernelGGL(prepare_key2_kernel, grid, block, 0, s, key2, cur, n_rows, (uint32_t)(n_key2 - 1), k32_a);
-    PREPARE_ROCPRIM(rocprim::radix_sort_pairs(nullptr, need, k32_a, k32_b, cur, other, (size_t)n_rows, 0u, bits, s),
-                    "prepare_rank");
-    PREPARE_TEMP_FITS(need, temp_cap, "prepare_rank");
-    PREPARE_ROCPRIM(rocprim::radix_sort_pairs(temp, need, k32_a, k32_b, cur, other, (size_t)n_rows, 0u, bits, s),
-                    "prepare_rank");
-    uint32_t* t = cur;  cur = other;  other = t;
+    hipLaunchKernelGGL(prepare_key2_kernel, grid, block, 0, s, key2, ps.perm, n_rows, (uint32_t)(n_key2 - 1),
+                       ps.keys<uint32_t>());
+    if ((rc = ps.pass<uint32_t>("prepare_rank", cql_bits_for(n_key2))) != CQLREC_OK) return rc;
   }
-  hipLaunchKernelGGL(prepare_key_kernel, grid, block, 0, s, key, cur, n_rows, key_a);
-  PREPARE_ROCPRIM(rocprim::radix_sort_pairs(nullptr, need, key_a, key_b, cur, other, (size_t)n_rows, 0u, 64u, s),
-                  "prepare_rank");
-  PREPARE_TEMP_FITS(need, temp_cap, "prepare_rank");
-  PREPARE_ROCPRIM(rocprim::radix_sort_pairs(temp, need, key_a, key_b, cur, other, (size_t)n_rows, 0u, 64u, s),
-                  "prepare_rank");
-  {
-    uint32_t* t = cur;  cur = other;  other = t;
-  }
-  const unsigned ubits = bits_for(n_users);
-  hipLaunchKernelGGL(prepare_user_key_kernel, grid, block, 0, s, user_idx, cur, n_rows, k32_a);
-  PREPARE_ROCPRIM(rocprim::radix_sort_pairs(nullptr, need, k32_a, k32_b, cur, other, (size_t)n_rows, 0u, ubits, s),
-                  "prepare_rank");
-  PREPARE_TEMP_FITS(need, temp_cap, "prepare_rank");
-  PREPARE_ROCPRIM(rocprim::radix_sort_pairs(temp, need, k32_a, k32_b, cur, other, (size_t)n_rows, 0u, ubits, s),
-                  "prepare_rank");
-  cur = other;
-  hipLaunchKernelGGL(prepare_bounds_kernel, dim3(cql_ceil_div(n_rows + 1, 256)), block, 0, s, user_idx, cur, n_rows,
-                     n_users, offsets);
-  hipLaunchKernelGGL(prepare_rank_finish_kernel, grid, block, 0, s, user_idx, cur, n_rows, offsets, rank);
-  hipLaunchKernelGGL(prepare_rank_count_kernel, dim3(cql_ceil_div(n_users, 256)), block, 0, s, offsets, n_users, count);
-  CQL_LAUNCH_CHECK("prepare_rank");
-  return CQLREC_OK;
+  hipLaunchKernelGGL(prepare_key_kernel, grid, block, 0, s, key, ps.perm, n_rows, ps.keys<uint64_t>());
+  if ((rc = ps.pass<uint64_t>("prepare_rank", 64)) != CQLREC_OK) return rc;
+  return cql_rank_tail(ps, user_idx, n_users, offsets, rank, count, nullptr, "prepare_rank");
 }
 
 // =============================================================================================================
@@ -174,7 +76,7 @@ extern "C" int cqlrec_prepare_count(const int32_t* ids, int64_t n_rows, int64_t 
               "prepare_count: n_rows=%lld n_groups=%lld out of range", (long long)n_rows, (long long)n_groups);
   CQL_REQUIRE(count && (ids || n_rows == 0), "prepare_count: NULL pointer");
   hipStream_t s = (hipStream_t)stream;
-  PREPARE_MEMSET(count, 0, (size_t)n_groups * 4, "prepare_count");
+  CQL_MEMSET(count, 0, (size_t)n_groups * 4, s, "prepare_count");
   if (n_rows == 0) return CQLREC_OK;
   hipLaunchKernelGGL(prepare_count_kernel, dim3(cql_ceil_div(n_rows, 256)), dim3(256), 0, s, ids, n_rows, count);
   CQL_LAUNCH_CHECK("prepare_count");
@@ -343,7 +245,7 @@ extern "C" int cqlrec_prepare_keep(int32_t rule, const int32_t* group, const int
 // =============================================================================================================
 extern "C" int64_t cqlrec_prepare_compact_ws_bytes(int64_t n_rows) {
   if (n_rows < 0) return 0;
-  return a256(n_rows * 8) + (16ll << 20) + 256;
+  return cql_align256(n_rows * 8) + (16ll << 20) + 256;
 }
 
 extern "C" int cqlrec_prepare_compact(const uint8_t* keep, int64_t n_rows, void* ws, int64_t ws_bytes, int64_t* rows,
@@ -352,19 +254,14 @@ extern "C" int cqlrec_prepare_compact(const uint8_t* keep, int64_t n_rows, void*
   CQL_REQUIRE(n_kept, "prepare_compact: NULL pointer");
   hipStream_t s = (hipStream_t)stream;
   if (n_rows == 0) {
-    PREPARE_MEMSET(n_kept, 0, 8, "prepare_compact");
+    CQL_MEMSET(n_kept, 0, 8, s, "prepare_compact");
     return CQLREC_OK;
   }
   CQL_REQUIRE(keep && ws && rows, "prepare_compact: NULL pointer");
   CQL_REQUIRE(ws_bytes >= cqlrec_prepare_compact_ws_bytes(n_rows), "prepare_compact: workspace too small");
   const size_t cap = (size_t)(cqlrec_prepare_compact_ws_bytes(n_rows) - 256);
-  static_assert(sizeof(size_t) == sizeof(int64_t), "the count is written as size_t");
-  rocprim::counting_iterator<int64_t> all_rows(0);
-  size_t need = 0;
-  PREPARE_ROCPRIM(rocprim::select(nullptr, need, all_rows, keep, rows, (size_t*)n_kept, (size_t)n_rows, s),
-                  "prepare_compact");
-  PREPARE_TEMP_FITS(need, cap, "prepare_compact");
-  PREPARE_ROCPRIM(rocprim::select(ws, need, all_rows, keep, rows, (size_t*)n_kept, (size_t)n_rows, s), "prepare_compact");
+  const int rc = cql_select_rows("prepare_compact", ws, cap, keep, rows, n_kept, n_rows, s);
+  if (rc != CQLREC_OK) return rc;
   CQL_LAUNCH_CHECK("prepare_compact");
   return CQLREC_OK;
 }
@@ -374,7 +271,7 @@ extern "C" int cqlrec_prepare_compact(const uint8_t* keep, int64_t n_rows, void*
 // =============================================================================================================
 extern "C" int64_t cqlrec_prepare_distinct_ws_bytes(int64_t n) {
   if (n < 0) return 0;
-  return a256(n * 8) + sort_temp_cap(n) + 256;
+  return cql_align256(n * 8) + cql_sort_temp_cap(n) + 256;
 }
 
 extern "C" int cqlrec_prepare_distinct(const int64_t* ids, int64_t n, void* ws, int64_t ws_bytes, int64_t* out,
@@ -383,36 +280,24 @@ extern "C" int cqlrec_prepare_distinct(const int64_t* ids, int64_t n, void* ws, 
   CQL_REQUIRE(n_out, "prepare_distinct: NULL pointer");
   hipStream_t s = (hipStream_t)stream;
   if (n == 0) {
-    PREPARE_MEMSET(n_out, 0, 8, "prepare_distinct");
+    CQL_MEMSET(n_out, 0, 8, s, "prepare_distinct");
     return CQLREC_OK;
   }
   CQL_REQUIRE(ids && ws && out, "prepare_distinct: NULL pointer");
   CQL_REQUIRE(ws_bytes >= cqlrec_prepare_distinct_ws_bytes(n), "prepare_distinct: workspace too small");
   int64_t* sorted = (int64_t*)ws;
-  void* temp = (char*)ws + a256(n * 8);
-  const size_t cap = (size_t)sort_temp_cap(n);
-  static_assert(sizeof(size_t) == sizeof(int64_t), "the count is written as size_t");
-  size_t need = 0;
-  PREPARE_ROCPRIM(rocprim::radix_sort_keys(nullptr, need, ids, sorted, (size_t)n, 0u, 64u, s), "prepare_distinct");
-  PREPARE_TEMP_FITS(need, cap, "prepare_distinct");
-  PREPARE_ROCPRIM(rocprim::radix_sort_keys(temp, need, ids, sorted, (size_t)n, 0u, 64u, s), "prepare_distinct");
-  PREPARE_ROCPRIM(rocprim::unique(nullptr, need, sorted, out, (size_t*)n_out, (size_t)n, rocprim::equal_to<int64_t>(), s),
-                  "prepare_distinct");
-  PREPARE_TEMP_FITS(need, cap, "prepare_distinct");
-  PREPARE_ROCPRIM(rocprim::unique(temp, need, sorted, out, (size_t*)n_out, (size_t)n, rocprim::equal_to<int64_t>(), s),
-                  "prepare_distinct");
+  void* temp = (char*)ws + cql_align256(n * 8);
+  const size_t cap = (size_t)cql_sort_temp_cap(n);
+  int rc = cql_sort_keys("prepare_distinct", temp, cap, ids, sorted, n, 64, s);
+  if (rc == CQLREC_OK) rc = cql_unique("prepare_distinct", temp, cap, sorted, out, n_out, n, s);
+  if (rc != CQLREC_OK) return rc;
   CQL_LAUNCH_CHECK("prepare_distinct");
   return CQLREC_OK;
 }
 
-__global__ void prepare_iota_kernel(int64_t m, int32_t* __restrict__ out) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < m) out[i] = (int32_t)i;
-}
-
 extern "C" int64_t cqlrec_prepare_sort_labels_ws_bytes(int64_t m) {
   if (m < 0) return 0;
-  return a256(m * 4) + sort_temp_cap(m) + 256;
+  return cql_align256(m * 4) + cql_sort_temp_cap(m) + 256;
 }
 
 extern "C" int cqlrec_prepare_sort_labels(const int64_t* labels, int64_t m, void* ws, int64_t ws_bytes, int64_t* sorted,
@@ -423,14 +308,11 @@ extern "C" int cqlrec_prepare_sort_labels(const int64_t* labels, int64_t m, void
   CQL_REQUIRE(ws_bytes >= cqlrec_prepare_sort_labels_ws_bytes(m), "prepare_sort_labels: workspace too small");
   hipStream_t s = (hipStream_t)stream;
   int32_t* iota = (int32_t*)ws;
-  void* temp = (char*)ws + a256(m * 4);
-  hipLaunchKernelGGL(prepare_iota_kernel, dim3(cql_ceil_div(m, 256)), dim3(256), 0, s, m, iota);
-  size_t need = 0;
-  PREPARE_ROCPRIM(rocprim::radix_sort_pairs(nullptr, need, labels, sorted, iota, sorted_idx, (size_t)m, 0u, 64u, s),
-                  "prepare_sort_labels");
-  PREPARE_TEMP_FITS(need, sort_temp_cap(m), "prepare_sort_labels");
-  PREPARE_ROCPRIM(rocprim::radix_sort_pairs(temp, need, labels, sorted, iota, sorted_idx, (size_t)m, 0u, 64u, s),
-                  "prepare_sort_labels");
+  void* temp = (char*)ws + cql_align256(m * 4);
+  cql_iota((uint32_t*)iota, m, false, s);                 // m < 2^31: the same bits as int32
+  const int rc = cql_sort_pairs("prepare_sort_labels", temp, (size_t)cql_sort_temp_cap(m), labels, sorted, iota, sorted_idx, m,
+                                64, s);
+  if (rc != CQLREC_OK) return rc;
   CQL_LAUNCH_CHECK("prepare_sort_labels");
   return CQLREC_OK;
 }
@@ -461,7 +343,7 @@ extern "C" int cqlrec_prepare_lookup(const int64_t* ids, int64_t n_rows, const i
               "prepare_lookup: n_rows=%lld m=%lld out of range", (long long)n_rows, (long long)m);
   CQL_REQUIRE(miss && (n_rows == 0 || (ids && out && (m == 0 || (sorted && sorted_idx)))), "prepare_lookup: NULL pointer");
   hipStream_t s = (hipStream_t)stream;
-  PREPARE_MEMSET(miss, 0, 4, "prepare_lookup");
+  CQL_MEMSET(miss, 0, 4, s, "prepare_lookup");
   if (n_rows == 0) return CQLREC_OK;
   hipLaunchKernelGGL(prepare_lookup_kernel, dim3(cql_ceil_div(n_rows, 256)), dim3(256), 0, s, ids, n_rows, sorted,
                      sorted_idx, m, out, miss);
@@ -489,7 +371,7 @@ extern "C" int cqlrec_prepare_gather(const int64_t* idx, int64_t n_rows, const i
               "prepare_gather: n_rows=%lld m=%lld out of range", (long long)n_rows, (long long)m);
   CQL_REQUIRE(bad && (n_rows == 0 || (idx && out && (m == 0 || labels))), "prepare_gather: NULL pointer");
   hipStream_t s = (hipStream_t)stream;
-  PREPARE_MEMSET(bad, 0, 4, "prepare_gather");
+  CQL_MEMSET(bad, 0, 4, s, "prepare_gather");
   if (n_rows == 0) return CQLREC_OK;
   hipLaunchKernelGGL(prepare_gather_kernel, dim3(cql_ceil_div(n_rows, 256)), dim3(256), 0, s, idx, n_rows, labels, m, out,
                      bad);

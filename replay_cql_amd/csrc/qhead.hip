@@ -778,12 +778,11 @@ __global__ __launch_bounds__(256) void qhead_bwd_sparse_kernel(const float* __re
 // =============================================================================================================
 // C ABI
 // =============================================================================================================
-static inline int64_t align256(int64_t x) { return (x + 255) / 256 * 256; }
 
 extern "C" int64_t cqlrec_qhead_ws_bytes(int64_t rows, int64_t n_items, int32_t d) {
   (void)d;
   const QSplit sp = qs_choose_split(n_items, rows, QS_SPW_FWD, QS_TI, QS_TARGET_BLOCKS);
-  return 3 * align256((int64_t)sp.nsplit * rows * 4) + 256;
+  return 3 * cql_align256((int64_t)sp.nsplit * rows * 4) + 256;
 }
 
 static int qhead_fwd_impl(const uint16_t* H_b, int64_t rows, const uint16_t* E_out_b, const float* b_out, int64_t n_items,
@@ -815,7 +814,7 @@ static int qhead_fwd_impl(const uint16_t* H_b, int64_t rows, const uint16_t* E_o
   CQL_REQUIRE(mode == CQLREC_QHEAD_LSE || mode == CQLREC_QHEAD_ARGMAX, "qhead_fwd: bad mode %d", mode);
   CQL_REQUIRE(ws_bytes >= cqlrec_qhead_ws_bytes(rows, n_items, d), "qhead_fwd: workspace too small");
   const QSplit sp = qs_choose_split(n_items, rows, QS_SPW_FWD, QS_TI, QS_TARGET_BLOCKS);
-  const int64_t seg = align256((int64_t)sp.nsplit * rows * 4);
+  const int64_t seg = cql_align256((int64_t)sp.nsplit * rows * 4);
   QArgs a = {};
   a.res = H_b;
   a.n_res = rows;
@@ -867,9 +866,9 @@ static int qhead_fwd_impl(const uint16_t* H_b, int64_t rows, const uint16_t* E_o
 extern "C" int64_t cqlrec_qhead_bwd_ws_bytes(int64_t batch, int64_t n_items, int32_t d) {
   const QSplit s1 = qs_choose_split(n_items, batch, QS_SPW_BWD, QS_TI, QS_TARGET_BLOCKS_BWD);
   const QSplit s2 = qs_choose_split(batch, n_items, QS_SPW_BWD, QS_TI, QS_TARGET_BLOCKS_BWD);
-  const int64_t a1 = align256((int64_t)s1.nsplit * batch * d * 4);
+  const int64_t a1 = cql_align256((int64_t)s1.nsplit * batch * d * 4);
   // a2: the slabs of the retired skeleton form of the item-side backward, still counted so that the size stays as it was
-  const int64_t a2 = align256((int64_t)s2.nsplit * n_items * d * 4) + align256((int64_t)s2.nsplit * n_items * 4);
+  const int64_t a2 = cql_align256((int64_t)s2.nsplit * n_items * d * 4) + cql_align256((int64_t)s2.nsplit * n_items * 4);
   const int64_t a3 = cql_qde_ws_bytes(batch, n_items, d);
   const int64_t m = (a1 > a2 ? a1 : a2);
   return (m > a3 ? m : a3) + 256;
@@ -958,7 +957,7 @@ static FusedWs fused_ws(void* ws, int64_t rows, int64_t n_items, int32_t d) {
   // the row-blocks: one block per CU); qfwd3_kernel (d = 256, 128 states per block, one block per CU resident) gets half as
   // many, twice as long slices -- one round of blocks, half the slab traffic
   f.sp = qs_choose_split(n_items, rows, QS_SPW_BWD, QS_TI, cql_qfwd3_supported(d, n_items) ? QS_TARGET_BLOCKS_BWD / 2 : QS_TARGET_BLOCKS_BWD);
-  const int64_t slab_b = align256((int64_t)f.sp.nsplit * rows * d * 4), seg = align256((int64_t)f.sp.nsplit * rows * 4);
+  const int64_t slab_b = cql_align256((int64_t)f.sp.nsplit * rows * d * 4), seg = cql_align256((int64_t)f.sp.nsplit * rows * 4);
   f.slab = (float*)ws;
   f.part_a = (float*)((char*)ws + slab_b);
   f.part_b = (float*)((char*)ws + slab_b + seg);

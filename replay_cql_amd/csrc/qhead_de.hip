@@ -333,7 +333,6 @@ __global__ void qde_nlse_natural_kernel(const float* __restrict__ nlse2, int64_t
 // =============================================================================================================
 // host side
 // =============================================================================================================
-static inline int64_t de_align256(int64_t x) { return (x + 255) / 256 * 256; }
 static int de_env_int(const char* name, int dflt) {
   const char* v = getenv(name);
   return (v && *v) ? atoi(v) : dflt;
@@ -363,7 +362,7 @@ static int de_grid(int64_t n_items, int64_t batch, int d) {
 
 int64_t cql_qde_ws_bytes(int64_t batch, int64_t n_items, int32_t d) {
   const int64_t grid = 512;      // upper bound of de_grid() for every block shape
-  return de_align256(grid * QDE_MAX_ITEMS * d * 4) + de_align256(grid * QDE_MAX_ITEMS * 4) + de_align256(batch * 4) + de_align256(grid * 16) + 256;
+  return cql_align256(grid * QDE_MAX_ITEMS * d * 4) + cql_align256(grid * QDE_MAX_ITEMS * 4) + cql_align256(batch * 4) + cql_align256(grid * 16) + 256;
 }
 
 template <int D, int NBUF, int WAVES>
@@ -406,17 +405,17 @@ int cql_qde_launch(const uint16_t* H_b, const float* nlse2, int64_t batch, const
   a.T = (int32_t)((batch + ti - 1) / ti);
   const int grid = de_grid(n_items, batch, d);
   a.slab = (float*)ws;
-  a.slab_cs = (float*)((char*)ws + de_align256((int64_t)grid * items * d * 4));
+  a.slab_cs = (float*)((char*)ws + cql_align256((int64_t)grid * items * d * 4));
   static const int want_stamps = de_env_int("CQL_QDE_STAMPS", 0);     // diagnostic: in-kernel clock, synchronises
-  unsigned long long* stamps_dev = (unsigned long long*)((char*)a.slab_cs + de_align256((int64_t)grid * items * 4) +
-                                                         de_align256(batch * 4));
+  unsigned long long* stamps_dev = (unsigned long long*)((char*)a.slab_cs + cql_align256((int64_t)grid * items * 4) +
+                                                         cql_align256(batch * 4));
   a.stamps = want_stamps ? stamps_dev : nullptr;
   const bool form3 = !form2 && cql_qde3_supported(d, batch);      // d = 256: same groups, stages and grid as qde_kernel<256>
   if (form2 || form3) {
     if (nlse_nat) {        // the caller's forward already wrote -lse in natural units
       a.nlse2 = nlse_nat;
     } else {
-      float* nat = (float*)((char*)a.slab_cs + de_align256((int64_t)grid * items * 4));
+      float* nat = (float*)((char*)a.slab_cs + cql_align256((int64_t)grid * items * 4));
       {
         CqlProfScope prof(CQLREC_PH_QHEAD_SMALL, s);
         hipLaunchKernelGGL(qde_nlse_natural_kernel, dim3(cql_ceil_div(batch, 256)), dim3(256), 0, s, nlse2, batch, nat);

@@ -10,13 +10,8 @@
 //
 // Random draws: h(x) = mix64(mix64(seed) ^ x), u(x) = ((h >> 11) + 0.5) * 2^-53 -- data._mix64 / data._u01 bit for bit
 // (the double add rounds to nearest even in both; the multiply by a power of two is exact).
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_select.hpp>
-#include <rocprim/iterator/counting_iterator.hpp>
+#include "segment_common.h"
 
-#include "common.h"
-
-static inline int64_t a256(int64_t x) { return (x + 255) / 256 * 256; }
 static const int64_t SPLIT_MAX_ROWS = 1ll << 31;
 
 __host__ __device__ __forceinline__ uint64_t split_mix64(uint64_t z) {
@@ -26,26 +21,6 @@ __host__ __device__ __forceinline__ uint64_t split_mix64(uint64_t z) {
   return z ^ (z >> 31);
 }
 __device__ __forceinline__ double split_u01(uint64_t h) { return ((double)(h >> 11) + 0.5) * 0x1p-53; }
-
-// scratch left for rocPRIM behind the explicit buffers: a sort without double buffers keeps one more copy of keys and
-// values there (the bound prep.hip uses)
-static inline int64_t sort_temp_cap(int64_t n) { return a256(4 * n * 8) + (16ll << 20); }
-
-#define SPLIT_ROCPRIM(call, what)                                                        \
-  do {                                                                                   \
-    hipError_t e__ = (call);                                                             \
-    if (e__ != hipSuccess) {                                                             \
-      cql_set_error("%s: rocPRIM failed: %s", what, hipGetErrorString(e__));             \
-      return CQLREC_ERR_HIP;                                                             \
-    }                                                                                    \
-  } while (0)
-#define SPLIT_TEMP_FITS(need, cap, what)                                                 \
-  do {                                                                                   \
-    if ((need) > (size_t)(cap)) {                                                        \
-      cql_set_error("%s: rocPRIM needs %zu bytes of scratch (have %zu)", what, (size_t)(need), (size_t)(cap)); \
-      return CQLREC_ERR_HIP;                                                             \
-    }                                                                                    \
-  } while (0)
 
 // =============================================================================================================
 // rank inside the user
@@ -61,37 +36,9 @@ __global__ void rank_init_kernel(const int64_t* __restrict__ key, int64_t n, int
   perm[i] = (uint32_t)r;
   skey[i] = ~k;
 }
-__global__ void rank_user_key_kernel(const int32_t* __restrict__ user_idx, const uint32_t* __restrict__ perm, int64_t n,
-                                     uint32_t* __restrict__ ukey) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) ukey[i] = (uint32_t)user_idx[perm[i]];
-}
-// offsets[u] = first sorted position whose user >= u (as csr_finish_kernel); every first row of a user counts it present
-__global__ void rank_bounds_kernel(const int32_t* __restrict__ user_idx, const uint32_t* __restrict__ perm, int64_t n,
-                                   int64_t n_users, int64_t* __restrict__ offsets,
-                                   unsigned long long* __restrict__ n_present) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i > n) return;
-  const int64_t cur = (i < n) ? (int64_t)user_idx[perm[i]] : n_users;
-  const int64_t prev = (i > 0) ? (int64_t)user_idx[perm[i - 1]] : -1;
-  for (int64_t u = prev + 1; u <= cur; ++u) offsets[u] = i;
-  if (n_present && i < n && cur != prev) atomicAdd(n_present, 1ull);
-}
-__global__ void rank_finish_kernel(const int32_t* __restrict__ user_idx, const uint32_t* __restrict__ perm, int64_t n,
-                                   const int64_t* __restrict__ offsets, int32_t* __restrict__ rank) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const uint32_t r = perm[i];
-  rank[r] = (int32_t)(i - offsets[user_idx[r]] + 1);
-}
-__global__ void rank_count_kernel(const int64_t* __restrict__ offsets, int64_t n_users, int32_t* __restrict__ count) {
-  const int64_t u = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (u < n_users) count[u] = (int32_t)(offsets[u + 1] - offsets[u]);
-}
 
 extern "C" int64_t cqlrec_split_rank_ws_bytes(int64_t n_rows, int64_t n_users) {
-  if (n_rows < 0 || n_users < 0) return 0;
-  return 2 * a256(n_rows * 4) + 2 * a256(n_rows * 8) + a256((n_users + 1) * 8) + sort_temp_cap(n_rows) + 256;
+  return cql_rank_ws_bytes(n_rows, n_users);
 }
 
 extern "C" int cqlrec_split_rank(const int32_t* user_idx, const int64_t* key, int64_t n_rows, int64_t n_users,
@@ -102,53 +49,22 @@ extern "C" int cqlrec_split_rank(const int32_t* user_idx, const int64_t* key, in
   CQL_REQUIRE(count, "split_rank: NULL pointer");
   hipStream_t s = (hipStream_t)stream;
   if (n_rows == 0) {
-    if (hipMemsetAsync(count, 0, (size_t)n_users * 4, s) != hipSuccess ||
-        (n_present && hipMemsetAsync(n_present, 0, 8, s) != hipSuccess)) {
-      cql_set_error("split_rank: memset failed");
-      return CQLREC_ERR_HIP;
-    }
+    CQL_MEMSET(count, 0, (size_t)n_users * 4, s, "split_rank");
+    if (n_present) CQL_MEMSET(n_present, 0, 8, s, "split_rank");
     return CQLREC_OK;
   }
   CQL_REQUIRE(user_idx && ws && rank && (key || shuffle), "split_rank: NULL pointer");
   CQL_REQUIRE(ws_bytes >= cqlrec_split_rank_ws_bytes(n_rows, n_users), "split_rank: workspace too small");
   char* p = (char*)ws;
-  uint32_t* perm_a = (uint32_t*)p;  p += a256(n_rows * 4);
-  uint32_t* perm_b = (uint32_t*)p;  p += a256(n_rows * 4);
-  uint64_t* key_a = (uint64_t*)p;   p += a256(n_rows * 8);
-  uint64_t* key_b = (uint64_t*)p;   p += a256(n_rows * 8);
-  int64_t* offsets = (int64_t*)p;   p += a256((n_users + 1) * 8);
-  void* temp = p;
-  const size_t temp_cap = (size_t)sort_temp_cap(n_rows);
-  const dim3 grid(cql_ceil_div(n_rows, 256)), block(256);
-  hipLaunchKernelGGL(rank_init_kernel, grid, block, 0, s, key, n_rows, shuffle ? 1 : 0, split_mix64(seed), perm_a, key_a);
-  // pass 1: by key descending (ascending over the complemented key); stable, so equal keys keep later rows first
-  size_t need = 0;
-  SPLIT_ROCPRIM(rocprim::radix_sort_pairs(nullptr, need, key_a, key_b, perm_a, perm_b, (size_t)n_rows, 0u, 64u, s),
-                "split_rank");
-  SPLIT_TEMP_FITS(need, temp_cap, "split_rank");
-  SPLIT_ROCPRIM(rocprim::radix_sort_pairs(temp, need, key_a, key_b, perm_a, perm_b, (size_t)n_rows, 0u, 64u, s),
-                "split_rank");
-  // pass 2: by user, over the bits a user id below n_users can have
-  unsigned bits = 1;
-  while (bits < 32 && (1ll << bits) < n_users) ++bits;
-  uint32_t* ukey_a = (uint32_t*)key_a;
-  uint32_t* ukey_b = (uint32_t*)key_b;
-  hipLaunchKernelGGL(rank_user_key_kernel, grid, block, 0, s, user_idx, perm_b, n_rows, ukey_a);
-  SPLIT_ROCPRIM(rocprim::radix_sort_pairs(nullptr, need, ukey_a, ukey_b, perm_b, perm_a, (size_t)n_rows, 0u, bits, s),
-                "split_rank");
-  SPLIT_TEMP_FITS(need, temp_cap, "split_rank");
-  SPLIT_ROCPRIM(rocprim::radix_sort_pairs(temp, need, ukey_a, ukey_b, perm_b, perm_a, (size_t)n_rows, 0u, bits, s),
-                "split_rank");
-  if (n_present && hipMemsetAsync(n_present, 0, 8, s) != hipSuccess) {
-    cql_set_error("split_rank: memset failed");
-    return CQLREC_ERR_HIP;
-  }
-  hipLaunchKernelGGL(rank_bounds_kernel, dim3(cql_ceil_div(n_rows + 1, 256)), block, 0, s, user_idx, perm_a, n_rows,
-                     n_users, offsets, (unsigned long long*)n_present);
-  hipLaunchKernelGGL(rank_finish_kernel, grid, block, 0, s, user_idx, perm_a, n_rows, offsets, rank);
-  hipLaunchKernelGGL(rank_count_kernel, dim3(cql_ceil_div(n_users, 256)), block, 0, s, offsets, n_users, count);
-  CQL_LAUNCH_CHECK("split_rank");
-  return CQLREC_OK;
+  CqlPermSort ps(p, n_rows, s);
+  int64_t* offsets = (int64_t*)p;   p += cql_align256((n_users + 1) * 8);
+  ps.temp = p;
+  hipLaunchKernelGGL(rank_init_kernel, dim3(cql_ceil_div(n_rows, 256)), dim3(256), 0, s, key, n_rows, shuffle ? 1 : 0,
+                     split_mix64(seed), ps.perm, ps.keys<uint64_t>());
+  // by key descending (ascending over the complemented key); stable, so equal keys keep later rows first
+  const int rc = ps.pass<uint64_t>("split_rank", 64);
+  if (rc != CQLREC_OK) return rc;
+  return cql_rank_tail(ps, user_idx, n_users, offsets, rank, count, n_present, "split_rank");
 }
 
 // =============================================================================================================
@@ -160,7 +76,7 @@ __global__ void pick_kth_kernel(const int64_t* __restrict__ sorted, int64_t m, i
 
 extern "C" int64_t cqlrec_split_kth_key_ws_bytes(int64_t n) {
   if (n < 0) return 0;
-  return a256(n * 8) + sort_temp_cap(n) + 256;
+  return cql_align256(n * 8) + cql_sort_temp_cap(n) + 256;
 }
 
 extern "C" int cqlrec_split_kth_key(const int64_t* key, int64_t n, int64_t m, void* ws, int64_t ws_bytes, int64_t* out,
@@ -171,11 +87,9 @@ extern "C" int cqlrec_split_kth_key(const int64_t* key, int64_t n, int64_t m, vo
   CQL_REQUIRE(ws_bytes >= cqlrec_split_kth_key_ws_bytes(n), "split_kth_key: workspace too small");
   hipStream_t s = (hipStream_t)stream;
   int64_t* sorted = (int64_t*)ws;
-  void* temp = (char*)ws + a256(n * 8);
-  size_t need = 0;
-  SPLIT_ROCPRIM(rocprim::radix_sort_keys(nullptr, need, key, sorted, (size_t)n, 0u, 64u, s), "split_kth_key");
-  SPLIT_TEMP_FITS(need, sort_temp_cap(n), "split_kth_key");
-  SPLIT_ROCPRIM(rocprim::radix_sort_keys(temp, need, key, sorted, (size_t)n, 0u, 64u, s), "split_kth_key");
+  void* temp = (char*)ws + cql_align256(n * 8);
+  const int rc = cql_sort_keys("split_kth_key", temp, (size_t)cql_sort_temp_cap(n), key, sorted, n, 64, s);
+  if (rc != CQLREC_OK) return rc;
   hipLaunchKernelGGL(pick_kth_kernel, dim3(1), dim3(64), 0, s, sorted, m, out);
   CQL_LAUNCH_CHECK("split_kth_key");
   return CQLREC_OK;
@@ -222,7 +136,7 @@ __global__ __launch_bounds__(1024) void new_users_threshold_kernel(const int64_t
 
 extern "C" int64_t cqlrec_split_new_users_ws_bytes(int64_t n_users) {
   if (n_users < 0) return 0;
-  return a256(n_users * 8) + a256(n_users * 4) + sort_temp_cap(n_users) + 256;
+  return cql_align256(n_users * 8) + cql_align256(n_users * 4) + cql_sort_temp_cap(n_users) + 256;
 }
 
 extern "C" int cqlrec_split_new_users(const int32_t* user_idx, const int64_t* key, int64_t n_rows, int64_t n_users,
@@ -235,19 +149,15 @@ extern "C" int cqlrec_split_new_users(const int32_t* user_idx, const int64_t* ke
   CQL_REQUIRE(ws_bytes >= cqlrec_split_new_users_ws_bytes(n_users), "split_new_users: workspace too small");
   hipStream_t s = (hipStream_t)stream;
   char* p = (char*)ws;
-  int64_t* sorted = (int64_t*)p;  p += a256(n_users * 8);
-  int32_t* cnt = (int32_t*)p;     p += a256(n_users * 4);
+  int64_t* sorted = (int64_t*)p;  p += cql_align256(n_users * 8);
+  int32_t* cnt = (int32_t*)p;     p += cql_align256(n_users * 4);
   void* temp = p;
   const dim3 block(256);
   hipLaunchKernelGGL(user_start_init_kernel, dim3(cql_ceil_div(n_users, 256)), block, 0, s, user_start, cnt, n_users);
   hipLaunchKernelGGL(user_start_kernel, dim3(cql_ceil_div(n_rows, 256)), block, 0, s, user_idx, key, n_rows, user_start,
                      cnt);
-  size_t need = 0;
-  SPLIT_ROCPRIM(rocprim::radix_sort_keys(nullptr, need, user_start, sorted, (size_t)n_users, 0u, 64u, s),
-                "split_new_users");
-  SPLIT_TEMP_FITS(need, sort_temp_cap(n_users), "split_new_users");
-  SPLIT_ROCPRIM(rocprim::radix_sort_keys(temp, need, user_start, sorted, (size_t)n_users, 0u, 64u, s),
-                "split_new_users");
+  const int rc = cql_sort_keys("split_new_users", temp, (size_t)cql_sort_temp_cap(n_users), user_start, sorted, n_users, 64, s);
+  if (rc != CQLREC_OK) return rc;
   hipLaunchKernelGGL(new_users_threshold_kernel, dim3(1), dim3(1024), 0, s, sorted, cnt, n_users, test_size, threshold);
   CQL_LAUNCH_CHECK("split_new_users");
   return CQLREC_OK;
@@ -278,7 +188,7 @@ __global__ void pick_mark_kernel(const int32_t* __restrict__ count, const uint32
 
 extern "C" int64_t cqlrec_split_pick_users_ws_bytes(int64_t n_users) {
   if (n_users < 0) return 0;
-  return 2 * a256(n_users * 4) + 2 * a256(n_users * 8) + sort_temp_cap(n_users) + 256;
+  return CqlPermSort::bytes(n_users) + cql_sort_temp_cap(n_users) + 256;
 }
 
 extern "C" int cqlrec_split_pick_users(const int32_t* count, int64_t n_users, uint64_t seed, int64_t n_pick, void* ws,
@@ -289,30 +199,17 @@ extern "C" int cqlrec_split_pick_users(const int32_t* count, int64_t n_users, ui
   CQL_REQUIRE(ws_bytes >= cqlrec_split_pick_users_ws_bytes(n_users), "split_pick_users: workspace too small");
   hipStream_t s = (hipStream_t)stream;
   char* p = (char*)ws;
-  uint32_t* perm_a = (uint32_t*)p;  p += a256(n_users * 4);
-  uint32_t* perm_b = (uint32_t*)p;  p += a256(n_users * 4);
-  uint64_t* key_a = (uint64_t*)p;   p += a256(n_users * 8);
-  uint64_t* key_b = (uint64_t*)p;   p += a256(n_users * 8);
-  void* temp = p;
-  const size_t temp_cap = (size_t)sort_temp_cap(n_users);
+  CqlPermSort ps(p, n_users, s);
+  ps.temp = p;
   const dim3 grid(cql_ceil_div(n_users, 256)), block(256);
-  hipLaunchKernelGGL(pick_init_kernel, grid, block, 0, s, n_users, split_mix64(seed), perm_a, key_a);
-  size_t need = 0;
-  SPLIT_ROCPRIM(rocprim::radix_sort_pairs(nullptr, need, key_a, key_b, perm_a, perm_b, (size_t)n_users, 0u, 64u, s),
-                "split_pick_users");
-  SPLIT_TEMP_FITS(need, temp_cap, "split_pick_users");
-  SPLIT_ROCPRIM(rocprim::radix_sort_pairs(temp, need, key_a, key_b, perm_a, perm_b, (size_t)n_users, 0u, 64u, s),
-                "split_pick_users");
+  hipLaunchKernelGGL(pick_init_kernel, grid, block, 0, s, n_users, split_mix64(seed), ps.perm, ps.keys<uint64_t>());
+  int rc = ps.pass<uint64_t>("split_pick_users", 64);
+  if (rc != CQLREC_OK) return rc;
   // users without rows go behind the others (one stable pass over one bit)
-  uint32_t* akey_a = (uint32_t*)key_a;
-  uint32_t* akey_b = (uint32_t*)key_b;
-  hipLaunchKernelGGL(pick_absent_key_kernel, grid, block, 0, s, count, perm_b, n_users, akey_a);
-  SPLIT_ROCPRIM(rocprim::radix_sort_pairs(nullptr, need, akey_a, akey_b, perm_b, perm_a, (size_t)n_users, 0u, 1u, s),
-                "split_pick_users");
-  SPLIT_TEMP_FITS(need, temp_cap, "split_pick_users");
-  SPLIT_ROCPRIM(rocprim::radix_sort_pairs(temp, need, akey_a, akey_b, perm_b, perm_a, (size_t)n_users, 0u, 1u, s),
-                "split_pick_users");
-  hipLaunchKernelGGL(pick_mark_kernel, grid, block, 0, s, count, perm_a, n_users, n_pick, test_user);
+  hipLaunchKernelGGL(pick_absent_key_kernel, grid, block, 0, s, count, ps.perm, n_users, ps.keys<uint32_t>());
+  rc = ps.pass<uint32_t>("split_pick_users", 1);
+  if (rc != CQLREC_OK) return rc;
+  hipLaunchKernelGGL(pick_mark_kernel, grid, block, 0, s, count, ps.perm, n_users, n_pick, test_user);
   CQL_LAUNCH_CHECK("split_pick_users");
   return CQLREC_OK;
 }
@@ -441,7 +338,7 @@ __global__ void filter_test_kernel(const int32_t* __restrict__ user_idx, const i
   if (!keep) is_test[i] = 0;
 }
 
-static inline int64_t bitmap_bytes(int64_t n) { return a256((n + 31) / 32 * 4); }
+static inline int64_t bitmap_bytes(int64_t n) { return cql_align256((n + 31) / 32 * 4); }
 
 extern "C" int64_t cqlrec_split_filter_test_ws_bytes(int64_t n_users, int64_t n_items) {
   if (n_users < 0 || n_items < 0) return 0;
@@ -466,10 +363,7 @@ extern "C" int cqlrec_split_filter_test(const int32_t* user_idx, const int32_t* 
   uint32_t* item_bits = drop_cold_items ? (uint32_t*)((char*)ws + bitmap_bytes(n_users)) : nullptr;
   const dim3 grid(cql_ceil_div(n_rows, 256)), block(256);
   if (user_bits || item_bits) {
-    if (hipMemsetAsync(ws, 0, (size_t)(bitmap_bytes(n_users) + bitmap_bytes(n_items)), s) != hipSuccess) {
-      cql_set_error("split_filter_test: memset failed");
-      return CQLREC_ERR_HIP;
-    }
+    CQL_MEMSET(ws, 0, (size_t)(bitmap_bytes(n_users) + bitmap_bytes(n_items)), s, "split_filter_test");
     hipLaunchKernelGGL(presence_kernel, grid, block, 0, s, user_idx, item_idx, is_train, n_rows, user_bits, item_bits);
   }
   hipLaunchKernelGGL(filter_test_kernel, grid, block, 0, s, user_idx, item_idx, drop_zero_rel ? relevance : nullptr,
@@ -483,7 +377,7 @@ extern "C" int cqlrec_split_filter_test(const int32_t* user_idx, const int32_t* 
 // =============================================================================================================
 extern "C" int64_t cqlrec_split_compact_ws_bytes(int64_t n_rows) {
   if (n_rows < 0) return 0;
-  return a256(n_rows * 8) + (16ll << 20) + 256;
+  return cql_align256(n_rows * 8) + (16ll << 20) + 256;
 }
 
 extern "C" int cqlrec_split_compact(const uint8_t* is_train, const uint8_t* is_test, int64_t n_rows, void* ws,
@@ -493,26 +387,17 @@ extern "C" int cqlrec_split_compact(const uint8_t* is_train, const uint8_t* is_t
   CQL_REQUIRE(counts, "split_compact: NULL pointer");
   hipStream_t s = (hipStream_t)stream;
   if (n_rows == 0) {
-    if (hipMemsetAsync(counts, 0, 16, s) != hipSuccess) {
-      cql_set_error("split_compact: memset failed");
-      return CQLREC_ERR_HIP;
-    }
+    CQL_MEMSET(counts, 0, 16, s, "split_compact");
     return CQLREC_OK;
   }
   CQL_REQUIRE(is_train && is_test && ws && train_rows && test_rows, "split_compact: NULL pointer");
   CQL_REQUIRE(ws_bytes >= cqlrec_split_compact_ws_bytes(n_rows), "split_compact: workspace too small");
   const size_t cap = (size_t)(cqlrec_split_compact_ws_bytes(n_rows) - 256);
-  static_assert(sizeof(size_t) == sizeof(int64_t), "counts are written as size_t");
   const uint8_t* flags[2] = {is_train, is_test};
   int64_t* outs[2] = {train_rows, test_rows};
   for (int w = 0; w < 2; ++w) {
-    rocprim::counting_iterator<int64_t> rows(0);
-    size_t need = 0;
-    SPLIT_ROCPRIM(rocprim::select(nullptr, need, rows, flags[w], outs[w], (size_t*)(counts + w), (size_t)n_rows, s),
-                  "split_compact");
-    SPLIT_TEMP_FITS(need, cap, "split_compact");
-    SPLIT_ROCPRIM(rocprim::select(ws, need, rows, flags[w], outs[w], (size_t*)(counts + w), (size_t)n_rows, s),
-                  "split_compact");
+    const int rc = cql_select_rows("split_compact", ws, cap, flags[w], outs[w], counts + w, n_rows, s);
+    if (rc != CQLREC_OK) return rc;
   }
   CQL_LAUNCH_CHECK("split_compact");
   return CQLREC_OK;
