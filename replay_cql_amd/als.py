@@ -13,16 +13,17 @@ Nothing here has a CPU path: without a GPU every call that computes raises Cqlre
 from __future__ import annotations
 
 import math
-from typing import Any, Dict, Optional
+from typing import Optional
 
 import numpy as np
 import pandas as pd
 import torch
 
+from . import _log as L
 from . import _prepare as P
 from . import data as D
-from .neighbour import _id_tensor
-from .recommender_api import REC_COLUMNS, PandasRecommender
+from ._device import Ws
+from .device_recommender import DeviceRecommender
 
 __all__ = ["ALSWrap"]
 
@@ -45,9 +46,7 @@ class Als(P.Feat):
     def gram(self, F):
         n, r = F.shape
         G = torch.empty((r, r), dtype=torch.float64, device=self.dev)
-        nb = int(self.lib.cqlrec_als_gram_ws_bytes(n, r))
-        ws = self._ws(nb)
-        self.N.check(self.lib.cqlrec_als_gram(self._p(F), n, r, ws.data_ptr(), nb, G.data_ptr(), self.stream), "als_gram")
+        self.call("als_gram", F, n, r, Ws(n, r), G)
         return G
 
     def _mode(self, implicit: bool) -> int:
@@ -62,12 +61,8 @@ class Als(P.Feat):
         A = torch.empty((n_list, r, r), dtype=torch.float64, device=self.dev)
         b = torch.empty((n_list, r), dtype=torch.float64, device=self.dev)
         ne = self._empty(n_list, torch.int32)
-        nb = int(self.lib.cqlrec_als_normal_equations_ws_bytes(n_list, n_pieces, r))
-        ws = self._ws(nb)
-        self.N.check(self.lib.cqlrec_als_normal_equations(
-            off.data_ptr(), self._p(src), self._p(rating), n_dst, self._p(F), n_src, r, self._p(G), self._mode(implicit),
-            float(alpha), self._p(rows), n_list, n_pieces, ws.data_ptr(), nb, A.data_ptr(), b.data_ptr(), ne.data_ptr(),
-            self.stream), "als_normal_equations")
+        self.call("als_normal_equations", off, src, rating, n_dst, F, n_src, r, G, self._mode(implicit), float(alpha), rows,
+                  n_list, n_pieces, Ws(n_list, n_pieces, r), A, b, ne)
         return A, b, ne
 
     def half_step(self, side, F, G, implicit: bool, alpha: float, reg: float, X, has, failed, rows=None,
@@ -79,12 +74,8 @@ class Als(P.Feat):
             raise ValueError("X / has_factor do not have one row per destination row")
         n_list = n_dst if rows is None else rows.numel()
         n_pieces = count_pieces(off, rows) if n_pieces is None else int(n_pieces)
-        nb = int(self.lib.cqlrec_als_half_step_ws_bytes(n_list, n_pieces, r))
-        ws = self._ws(nb)
-        self.N.check(self.lib.cqlrec_als_half_step(
-            off.data_ptr(), self._p(src), self._p(rating), n_dst, self._p(F), n_src, r, self._p(G), self._mode(implicit),
-            float(alpha), float(reg), self._p(rows), n_list, n_pieces, ws.data_ptr(), nb, X.data_ptr(), has.data_ptr(),
-            failed.data_ptr(), self.stream), "als_half_step")
+        self.call("als_half_step", off, src, rating, n_dst, F, n_src, r, G, self._mode(implicit), float(alpha), float(reg),
+                  rows, n_list, n_pieces, Ws(n_list, n_pieces, r), X, has, failed)
 
     def topk(self, users, U, u_has, V, v_has, k: int, mask=None, seen=None):
         """(ids int32 [n_q, k] padded with -1, values float32 [n_q, k] padded with -inf, count int32 [n_q]); seen =
@@ -96,28 +87,26 @@ class Als(P.Feat):
         s_off, s_col = seen if seen is not None else (None, None)
         if s_off is not None and s_off.numel() < n_users + 1:
             raise ValueError("the seen lists need an offset per user")
-        self.N.check(self.lib.cqlrec_als_topk(self._p(users), n_q, self._p(U), self._p(u_has), n_users, self._p(V),
-                                              self._p(v_has), n_items, r, self._p(mask), self._p(s_off), self._p(s_col), int(k),
-                                              ids.data_ptr(), vals.data_ptr(), count.data_ptr(), self.stream), "als_topk")
+        self.call("als_topk", users, n_q, U, u_has, n_users, V, v_has, n_items, r, mask, s_off, s_col, int(k), ids, vals, count)
         return ids, vals, count
 
     def pair_scores(self, pair_user, pair_item, U, u_has, V, v_has):
         """(score float32 [n_pairs], valid uint8 [n_pairs])"""
         n = pair_user.numel()
         score, valid = self._empty(n, torch.float32), self._empty(n, torch.uint8)
-        self.N.check(self.lib.cqlrec_als_pair_scores(self._p(pair_user), self._p(pair_item), n, self._p(U), self._p(u_has),
-                                                     U.shape[0], self._p(V), self._p(v_has), V.shape[0], U.shape[1],
-                                                     score.data_ptr(), valid.data_ptr(), self.stream), "als_pair_scores")
+        self.call("als_pair_scores", pair_user, pair_item, n, U, u_has, U.shape[0], V, v_has, V.shape[0], U.shape[1], score,
+                  valid)
         return score, valid
 
 
-class ALSWrap(PandasRecommender):
+class ALSWrap(DeviceRecommender):
     """Alternating least squares for implicit (default) or explicit feedback.
 
     `_predict` returns at most k rows per user, already without the seen items and without ids that have no factor; the
     template's `_filter_seen` and `get_top_k_recs` then change nothing, as with `NeighbourRec`."""
 
     _seed: Optional[int] = None
+    _state_attr = "_factors"
     _search_space = {"rank": {"type": "loguniform_int", "args": [8, 256]}}
 
     def __init__(self, rank: int = 10, implicit_prefs: bool = True, seed: Optional[int] = None, *, max_iter: int = 10,
@@ -150,30 +139,12 @@ class ALSWrap(PandasRecommender):
         norm = torch.sqrt((z * z).sum(dim=1, keepdim=True))
         return (z / norm).to(torch.float32).contiguous()
 
-    def _fit_wrap(self, log, user_features=None, item_features=None) -> None:
-        """pandas and Spark logs go through the template; a pyarrow log or a dict of device tensors stays on the device"""
-        src = P.normalise(log)
-        if isinstance(src, pd.DataFrame) or type(src).__module__.startswith("pyspark"):
-            super()._fit_wrap(src, user_features, item_features)
-            return
-        lg = P.open_log(src, str(self))
-        if lg.n == 0:
-            raise ValueError("cannot fit an empty log")
-        users, items = torch.unique(lg.ids("user_idx")).cpu().numpy(), torch.unique(lg.ids("item_idx")).cpu().numpy()
-        self.fit_users, self.fit_items = pd.DataFrame({"user_idx": users}), pd.DataFrame({"item_idx": items})
-        self._num_users, self._num_items = len(users), len(items)
-        self._user_dim_size, self._item_dim_size = int(users.max()) + 1, int(items.max()) + 1
-        self._fit_device(lg)
-
-    def _fit(self, log: pd.DataFrame, user_features=None, item_features=None) -> None:
-        self._fit_device(P.open_log(log, str(self)))
-
     def _fit_device(self, lg) -> None:
         if lg.n == 0:
             raise ValueError("cannot fit an empty log")
         eng = Als(lg.device)
-        (user, n_users), (item, n_items) = P.dense_ids(lg, ["user_idx", "item_idx"])
-        rel = P.float_column(lg, "relevance")
+        (user, n_users), (item, n_items) = L.dense_ids(lg, ["user_idx", "item_idx"])
+        rel = L.float_column(lg, "relevance")
         if bool(torch.isnan(rel).any()):
             raise ValueError("relevance contains NaN")
         perm_i, off_i = eng.segments(item, n_items, user.to(torch.int64))
@@ -202,11 +173,6 @@ class ALSWrap(PandasRecommender):
         self._factors = {"user": (U, has_u), "item": (V, has_v)}
 
     # -------------------------------------------------------------------------------- the tables
-    def _fitted(self):
-        if "_factors" not in self.__dict__:
-            raise RuntimeError(f"{self} model is not fitted")
-        return self._factors
-
     def factors_device(self, entity: str):
         """(factors float32 [n, rank], has_factor uint8 [n]) of 'user' or 'item' on the device, indexed by the id"""
         if entity not in ("user", "item"):
@@ -223,13 +189,13 @@ class ALSWrap(PandasRecommender):
         eng = Als(dev)
         lg = None
         if log is not None:
-            lg = P.open_log(P.normalise(log), str(self))
+            lg = L.open_log(L.normalise(log), str(self))
             if lg.device != dev:
                 raise ValueError(f"the log is on {lg.device}, the model on {dev}")
-        users, items = _id_tensor(users, dev), _id_tensor(items, dev)
+        users, items = self._id_tensor(users, dev), self._id_tensor(items, dev)
         seen = None
         if lg is not None and lg.n:
-            (user, n_log_users), (item, _) = P.dense_ids(lg, ["user_idx", "item_idx"])
+            (user, n_log_users), (item, _) = L.dense_ids(lg, ["user_idx", "item_idx"])
             if users is None:
                 users = torch.unique(user.to(torch.int64))
             if filter_seen_items:
@@ -239,27 +205,9 @@ class ALSWrap(PandasRecommender):
         if users is None:
             users = torch.nonzero(has_u).flatten()
         users = users[users < (1 << 31) - 1]
-        mask = None
-        if items is not None:
-            mask = torch.zeros(V.shape[0], dtype=torch.uint8, device=dev)
-            mask[items[items < V.shape[0]]] = 1
+        mask = self._item_mask(items, V.shape[0], dev)
         ids, vals, count = eng.topk(users.to(torch.int32).contiguous(), U, has_u, V, has_v, int(k), mask=mask, seen=seen)
         return users, ids, vals, count
-
-    def recommend(self, log, k: int, users=None, items=None, filter_seen_items: bool = True) -> Dict[str, torch.Tensor]:
-        """The k best items of every user as device columns {user_idx int32, item_idx int32, relevance float64}, in the
-        order of `users` (None: the users of the log ascending, or without a log every user that has a factor), then
-        rank.  `log`: pandas, pyarrow, a dict of device tensors or None (nothing is seen); `users` / `items`: tensors,
-        iterables or None (every item).  Ids without a factor are absent."""
-        users, ids, vals, count = self._recommend(log, int(k), users, items, filter_seen_items)
-        keep = torch.arange(ids.shape[1], device=ids.device)[None, :] < count[:, None]
-        return {"user_idx": users.to(torch.int32)[:, None].expand_as(ids)[keep], "item_idx": ids[keep],
-                "relevance": vals[keep].to(torch.float64)}
-
-    def _predict(self, log, k: int, users: pd.DataFrame, items: pd.DataFrame, user_features=None, item_features=None,
-                 filter_seen_items: bool = True) -> pd.DataFrame:
-        out = self.recommend(log, int(k), users["user_idx"], items["item_idx"], filter_seen_items)
-        return pd.DataFrame({c: out[c].cpu().numpy() for c in REC_COLUMNS})
 
     def _predict_pairs(self, pairs: pd.DataFrame, log=None, user_features=None, item_features=None) -> pd.DataFrame:
         (U, has_u), (V, has_v) = self._fitted()["user"], self._fitted()["item"]

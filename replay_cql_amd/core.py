@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from . import _native as N
+from ._device import _ptr
 
 
 @dataclass
@@ -34,10 +35,6 @@ class CQLHyper:
     eps: float = 1e-8
     tau: float = 0.005
     seed: int = 0
-
-
-def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
-    return None if t is None else t.data_ptr()
 
 
 def _stream() -> int:

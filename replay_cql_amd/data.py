@@ -133,8 +133,7 @@ def build_csr_device(user_idx, item_idx, timestamp, relevance, n_users: int, dev
 
     timestamp=None: rows ordered by (user, item asc) -- the `seen` lists of cqlrec_score_topk (sorted_seen() on the
     device).  relevance=None: no reward column (returns rewards=None)."""
-    from . import _native as N
-    lib = N.load()
+    from ._device import Engine, Ws
     dev = torch.device(device)
     u, i = _dev_col(user_idx, torch.int32, dev), _dev_col(item_idx, torch.int32, dev)
     t = None if timestamp is None else _dev_col(timestamp_key(timestamp), torch.int64, dev)
@@ -151,10 +150,5 @@ def build_csr_device(user_idx, item_idx, timestamp, relevance, n_users: int, dev
         lo = torch.minimum(u.min(), i.min())
         if int(lo) < 0 or int(u.max()) >= n_users:
             raise ValueError("user_idx / item_idx must be non-negative dense indices below n_users")
-    ws_bytes = int(lib.cqlrec_build_csr_ws_bytes(n))
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    N.check(lib.cqlrec_build_csr(u.data_ptr(), i.data_ptr(), None if t is None else t.data_ptr(),
-                                 None if r is None else r.data_ptr(), n, n_users, ws.data_ptr(), ws_bytes,
-                                 offsets.data_ptr(), items.data_ptr(), None if rewards is None else rewards.data_ptr(),
-                                 torch.cuda.current_stream().cuda_stream), "build_csr")
+    Engine(dev).call("build_csr", u, i, t, r, n, n_users, Ws(n), offsets, items, rewards)
     return offsets, items, rewards

@@ -46,6 +46,7 @@ from typing import Optional, Union
 
 import torch
 
+from . import _log as L
 from . import _prepare as P
 from .splitters import _instant_ns, _threshold_key
 
@@ -61,7 +62,7 @@ def _logger():
 
 
 def _need(log, name, kinds: str, what: str) -> None:
-    kind, _ = P.column_kind(log, name)
+    kind, _ = L.column_kind(log, name)
     if kind not in kinds:
         raise ValueError(f"column {name} must be {what}")
 
@@ -94,21 +95,21 @@ def _spans(days: int, ts_kind: str):
         x = 86400.0 * float(days)
     except OverflowError:
         x = math.copysign(math.inf, days)
-    return P.clip64(days * DAY_S * (10 ** 9 if ts_kind == "datetime" else 1)), x
+    return L.clip64(days * DAY_S * (10 ** 9 if ts_kind == "datetime" else 1)), x
 
 
 def filter_by_min_count(data_frame, num_entries: int, group_by: str = "user_idx", *, return_rows: bool = False):
     """Remove the rows whose `group_by` value occurs fewer than `num_entries` times in `data_frame`."""
-    src = P.normalise(data_frame)
+    src = L.normalise(data_frame)
     _id_column(src, group_by)
-    lg = P.open_log(src, "filter_by_min_count")
+    lg = L.open_log(src, "filter_by_min_count")
     if lg.n == 0:
         return _result(lg, _no_rows(lg), return_rows)
-    (group, n_groups), = P.dense_ids(lg, [group_by])
+    (group, n_groups), = L.dense_ids(lg, [group_by])
     prep = P.Prep(lg.device)
     count = prep.count(group, n_groups)
     rows = prep.compact(prep.keep(_MIN_COUNT, lg.n, group=group, count=count,
-                                  n=P.clip64(math.ceil(num_entries))))
+                                  n=L.clip64(math.ceil(num_entries))))
     diff = (lg.n - rows.numel()) / lg.n
     (_logger().warning if diff > 0.5 else _logger().info)("current threshold removes %s%% of data", diff)
     return _result(lg, rows, return_rows)
@@ -116,14 +117,14 @@ def filter_by_min_count(data_frame, num_entries: int, group_by: str = "user_idx"
 
 def filter_out_low_ratings(data_frame, value: float, rating_column="relevance", *, return_rows: bool = False):
     """Remove the rows whose `rating_column` is less than `value` (or NaN)."""
-    src = P.normalise(data_frame)
+    src = L.normalise(data_frame)
     _need(src, rating_column, "iufb", "a numeric column")
     value = float(value)
-    lg = P.open_log(src, "filter_out_low_ratings")
+    lg = L.open_log(src, "filter_out_low_ratings")
     if lg.n == 0:
         return _result(lg, _no_rows(lg), return_rows)
     prep = P.Prep(lg.device)
-    rows = prep.compact(prep.keep(_MIN_VALUE, lg.n, value=P.float_column(lg, rating_column), x=value))
+    rows = prep.compact(prep.keep(_MIN_VALUE, lg.n, value=L.float_column(lg, rating_column), x=value))
     return _result(lg, rows, return_rows)
 
 
@@ -132,16 +133,16 @@ def take_num_user_interactions(log, num_interactions: int = 10, first: bool = Tr
                                user_col: str = "user_idx", item_col: Optional[str] = "item_idx", *,
                                return_rows: bool = False):
     """The first / last `num_interactions` rows of each user by (date_col, item_col, input row)."""
-    src = P.normalise(log)
+    src = L.normalise(log)
     _id_column(src, user_col)
     if item_col is not None:
         _id_column(src, item_col)
     _date_column(src, date_col)
-    n = P.clip64(math.floor(num_interactions))
-    lg = P.open_log(src, "take_num_user_interactions")
+    n = L.clip64(math.floor(num_interactions))
+    lg = L.open_log(src, "take_num_user_interactions")
     if lg.n == 0 or n <= 0:
         return _result(lg, _no_rows(lg), return_rows)
-    ids = P.dense_ids(lg, [user_col] + ([item_col] if item_col is not None else []))
+    ids = L.dense_ids(lg, [user_col] + ([item_col] if item_col is not None else []))
     (user, n_users), (item, n_items) = ids[0], (ids[1] if item_col is not None else (None, 0))
     prep = P.Prep(lg.device)
     rank, count = prep.rank(user, n_users, lg.key(date_col), item, n_items)
@@ -160,13 +161,13 @@ def take_num_days_of_user_hist(log, days: int = 10, first: bool = True, date_col
                                user_col: str = "user_idx", *, return_rows: bool = False):
     """The first / last `days` days of each user's history, counted from the user's own first / last timestamp."""
     days = _integral_days(days, "days")
-    src = P.normalise(log)
+    src = L.normalise(log)
     _id_column(src, user_col)
     _date_column(src, date_col)
-    lg = P.open_log(src, "take_num_days_of_user_hist")
+    lg = L.open_log(src, "take_num_days_of_user_hist")
     if lg.n == 0:
         return _result(lg, _no_rows(lg), return_rows)
-    (user, n_users), = P.dense_ids(lg, [user_col])
+    (user, n_users), = L.dense_ids(lg, [user_col])
     rows = _days(lg, P.Prep(lg.device), _DAYS_USER, lg.key(date_col), user, n_users, days, bool(first))
     return _result(lg, rows, return_rows)
 
@@ -178,14 +179,14 @@ def take_time_period(log, start_date: Optional[Union[str, datetime]] = None,
     for bound in (start_date, end_date):
         if bound is not None:
             _instant_ns(bound)                   # ValueError for a form or a string that is no date
-    src = P.normalise(log)
+    src = L.normalise(log)
     _date_column(src, date_column)
-    lg = P.open_log(src, "take_time_period")
+    lg = L.open_log(src, "take_time_period")
     if lg.n == 0:
         return _result(lg, _no_rows(lg), return_rows)
     key = lg.key(date_column)
-    lo = P.I64_MIN if start_date is None else P.clip64(_threshold_key(start_date, lg.ts_kind))
-    hi = 0 if end_date is None else P.clip64(_threshold_key(end_date, lg.ts_kind))
+    lo = L.I64_MIN if start_date is None else L.clip64(_threshold_key(start_date, lg.ts_kind))
+    hi = 0 if end_date is None else L.clip64(_threshold_key(end_date, lg.ts_kind))
     prep = P.Prep(lg.device)
     rows = prep.compact(prep.keep(_PERIOD, lg.n, key=key, lo=lo, hi=hi, open_end=end_date is None))
     return _result(lg, rows, return_rows)
@@ -195,9 +196,9 @@ def take_num_days_of_global_hist(log, duration_days: int, first: bool = True, da
                                  return_rows: bool = False):
     """The first / last `duration_days` days of the log, counted from its first / last timestamp."""
     days = _integral_days(duration_days, "duration_days")
-    src = P.normalise(log)
+    src = L.normalise(log)
     _date_column(src, date_column)
-    lg = P.open_log(src, "take_num_days_of_global_hist")
+    lg = L.open_log(src, "take_num_days_of_global_hist")
     if lg.n == 0:
         return _result(lg, _no_rows(lg), return_rows)
     rows = _days(lg, P.Prep(lg.device), _DAYS_GLOBAL, lg.key(date_column), None, 1, days, bool(first))

@@ -51,20 +51,21 @@ from typing import Dict, List, Optional
 import numpy as np
 import torch
 
+from . import _log as L
 from . import _prepare as P
 
 __all__ = ["EmptyFeatureProcessor", "LogStatFeaturesProcessor", "ConditionalPopularityProcessor",
            "HistoryBasedFeaturesProcessor"]
 
 DAY_S = 86400
-_NAT = P.I64_MIN                                   # numpy's NaT bit pattern
+_NAT = L.I64_MIN                                   # numpy's NaT bit pattern
 _STAT_COLS = ("std", "mean", "quantile_05", "quantile_5", "quantile_95")     # the reference's order; table: 2 1 3 4 5
 _STAT_AT = (2, 1, 3, 4, 5)
 _INT_COLS = ("history_length_days", "last_interaction_gap_days")
 
 
 def _id_column(log, name) -> None:
-    kind, _ = P.column_kind(log, name)
+    kind, _ = L.column_kind(log, name)
     if kind not in "iu":
         raise ValueError(f"column {name} must be an integer column")
 
@@ -128,14 +129,14 @@ class LogStatFeaturesProcessor(EmptyFeatureProcessor):
 
     # ---- fit ---------------------------------------------------------------------------------------------------
     def fit(self, log, features=None) -> None:
-        src = P.normalise(log)
+        src = L.normalise(log)
         for name in ("user_idx", "item_idx"):
             _id_column(src, name)
-        rel_kind, _ = P.column_kind(src, "relevance")
+        rel_kind, _ = L.column_kind(src, "relevance")
         if rel_kind not in "iufb":
             raise ValueError("column relevance must be a numeric column")
-        ts_kind = P.column_kind(src, "timestamp")[0] if P.has_column(src, "timestamp") else None
-        lg = P.open_log(src, "LogStatFeaturesProcessor.fit")
+        ts_kind = L.column_kind(src, "timestamp")[0] if L.has_column(src, "timestamp") else None
+        lg = L.open_log(src, "LogStatFeaturesProcessor.fit")
         self.calc_timestamp_based = self.calc_relevance_based = self._has_cr = False
         self._ts_kind, self._dev = None, lg.device
         self._n_users = self._n_items = 0
@@ -145,10 +146,10 @@ class LogStatFeaturesProcessor(EmptyFeatureProcessor):
             self._set_tables({"u_log_num_interact": None, "u_mean_i_log_num_interact": None},
                              {"i_log_num_interact": None, "i_mean_u_log_num_interact": None})
             return
-        (user, n_users), (item, n_items) = P.dense_ids(lg, ["user_idx", "item_idx"])
+        (user, n_users), (item, n_items) = L.dense_ids(lg, ["user_idx", "item_idx"])
         self._n_users, self._n_items = n_users, n_items
         feat = P.Feat(lg.device)
-        rel = P.float_column(lg, "relevance")
+        rel = L.float_column(lg, "relevance")
         lim = torch.stack([rel.min(), rel.max()]).cpu().tolist()          # torch's min / max propagate NaN
         if lim[0] != lim[0] or lim[1] != lim[1]:
             raise ValueError("relevance contains NaN")
@@ -360,16 +361,16 @@ class ConditionalPopularityProcessor(EmptyFeatureProcessor):
                              f"defined in `cat_features_list` are absent in features. "
                              f"features columns are: {columns}.")
         join_col, self.entity_name = (("item_idx", "user_idx") if "item_idx" in columns else ("user_idx", "item_idx"))
-        src = P.normalise(log)
+        src = L.normalise(log)
         for name in ("user_idx", "item_idx"):
             _id_column(src, name)
         fid = feats[join_col].to_numpy()
         if fid.dtype.kind not in "iu" or (len(fid) and (fid.min() < 0 or fid.max() >= (1 << 31) - 1)):
             raise ValueError(f"features column {join_col} must hold non-negative dense indices below 2^31 - 1")
-        lg = P.open_log(src, "ConditionalPopularityProcessor.fit")
+        lg = L.open_log(src, "ConditionalPopularityProcessor.fit")
         feat = P.Feat(lg.device) if lg.n else None
         if lg.n:
-            (entity, n_entity), (other, n_other) = P.dense_ids(lg, [self.entity_name, join_col])
+            (entity, n_entity), (other, n_other) = L.dense_ids(lg, [self.entity_name, join_col])
             count = feat.count(entity, n_entity)
         else:
             n_entity = n_other = 0
@@ -459,16 +460,16 @@ def _block(log_proc, pop_procs, user_idx, item_idx, dtype):
     if user_idx.dtype.is_floating_point or item_idx.dtype.is_floating_point or user_idx.shape != item_idx.shape or \
             user_idx.dim() != 1:
         raise ValueError("user_idx / item_idx must be integer vectors of one length")
-    if user_idx.numel() >= P.MAX_ROWS:
+    if user_idx.numel() >= L.MAX_ROWS:
         raise ValueError(f"a frame of {user_idx.numel()} pairs is beyond transform_block's 2^31 - 1")
     return _launch(log_proc, pop_procs, user_idx.to(torch.int64).contiguous(), item_idx.to(torch.int64).contiguous(), dtype)
 
 
 def _transform(frame, log_proc, pop_procs, what: str):
-    src = P.normalise(frame)
+    src = L.normalise(frame)
     for name in ("user_idx", "item_idx"):
         _id_column(src, name)
-    lg = P.open_log(src, what)
+    lg = L.open_log(src, what)
     user, item = _pair_ids(lg)
     block, names = _launch(log_proc, pop_procs, user, item, torch.float64, lg)
     cols: Dict[str, object] = {}
@@ -498,7 +499,7 @@ class HistoryBasedFeaturesProcessor:
         self.fitted: bool = False
 
     def fit(self, log, user_features=None, item_features=None) -> None:
-        log = P.normalise(log)
+        log = L.normalise(log)
         self.log_processor.fit(log=log, features=user_features)
         self.user_cond_pop_proc.fit(log=log, features=user_features)
         self.item_cond_pop_proc.fit(log=log, features=item_features)

@@ -25,6 +25,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
+from . import _log as L
 from . import _prepare as P
 
 __all__ = ["Indexer"]
@@ -35,7 +36,7 @@ def _np_dtype(dt) -> np.dtype:
 
 
 def _raw_id_dtype(frame, name: str) -> np.dtype:
-    kind, dt = P.column_kind(frame, name)
+    kind, dt = L.column_kind(frame, name)
     if kind not in "iu":
         raise ValueError(f"column {name} must hold integer ids (it is {'float' if kind == 'f' else 'no number'}): "
                          "factorize other ids on the host first, e.g. pandas.factorize")
@@ -98,14 +99,14 @@ class Indexer:
 
     @staticmethod
     def _distinct(src, col: str):
-        lg = P.open_log(src, "Indexer.fit")
+        lg = L.open_log(src, "Indexer.fit")
         if lg.n == 0:
             return torch.empty(0, dtype=torch.int64, device=lg.device)
         return P.Prep(lg.device).distinct(lg.ids(col))
 
     def fit(self, users, items) -> None:
         """Labels of the distinct ids of `users[user_col]` and `items[item_col]`, in ascending numeric order."""
-        users, items = P.normalise(users), P.normalise(items)
+        users, items = L.normalise(users), L.normalise(items)
         user_type, item_type = _raw_id_dtype(users, self.user_col), _raw_id_dtype(items, self.item_col)
         user_labels, item_labels = self._distinct(users, self.user_col), self._distinct(items, self.item_col)
         self.user_labels, self.user_type, self.item_labels, self.item_type = user_labels, user_type, item_labels, item_type
@@ -127,15 +128,15 @@ class Indexer:
     # ---- frames ---------------------------------------------------------------------------------------------
     def transform(self, df):
         """Raw `user_col` / `item_col` -> int32 `user_idx` / `item_idx`, in front of the other columns."""
-        src = P.normalise(df)
+        src = L.normalise(df)
         present = []
         for entity, col in (("item", self.item_col), ("user", self.user_col)):      # the reference's order
-            if not P.has_column(src, col):
+            if not L.has_column(src, col):
                 continue
             _raw_id_dtype(src, col)
             self._labels(entity)
             present.append((entity, col))
-        lg = P.open_log(src, "Indexer.transform")
+        lg = L.open_log(src, "Indexer.transform")
         prep = P.Prep(lg.device)
         done = {}
         for entity, col in present:
@@ -147,16 +148,16 @@ class Indexer:
 
     def inverse_transform(self, df):
         """`user_idx` / `item_idx` -> the raw ids under their original column names and dtype."""
-        src = P.normalise(df)
+        src = L.normalise(df)
         present = []
         for entity in ("item", "user"):
-            if not P.has_column(src, f"{entity}_idx"):
+            if not L.has_column(src, f"{entity}_idx"):
                 continue
-            if P.column_kind(src, f"{entity}_idx")[0] not in "iu":
+            if L.column_kind(src, f"{entity}_idx")[0] not in "iu":
                 raise ValueError(f"column {entity}_idx must be an integer column")
             self._labels(entity)
             present.append(entity)
-        lg = P.open_log(src, "Indexer.inverse_transform")
+        lg = L.open_log(src, "Indexer.inverse_transform")
         prep = P.Prep(lg.device)
         done = {}
         for entity in present:

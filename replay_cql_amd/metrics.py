@@ -21,6 +21,7 @@ import numpy as np
 import torch
 
 from . import _native as N
+from ._device import Engine, Ws
 
 METRICS = ("NDCG", "HitRate", "Precision", "Recall", "MAP", "MRR")
 
@@ -28,19 +29,13 @@ METRICS = ("NDCG", "HitRate", "Precision", "Recall", "MAP", "MRR")
 def _eval_topk_sums(rec_idx: torch.Tensor, gt_offsets: torch.Tensor, gt_items: torch.Tensor, ks: List[int],
                     rec_rows: Optional[torch.Tensor], return_per_user: bool):
     """cqlrec_eval_topk: (sums float64 [6 x n_ks] on the host, per_user [n x 6 x n_ks] on the device or None)."""
-    lib = N.load()
     n, kmax = int(rec_idx.shape[0]), int(rec_idx.shape[1])
     dev = rec_idx.device
     rec_idx = rec_idx.to(torch.int32).contiguous()
-    ks_arr = (C.c_int32 * len(ks))(*ks)
-    ws_bytes = int(lib.cqlrec_eval_topk_ws_bytes(n, len(ks)))
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
     sums = torch.zeros(len(METRICS) * len(ks), dtype=torch.float64, device=dev)
     per_user = torch.empty((n, len(METRICS), len(ks)), dtype=torch.float64, device=dev) if return_per_user else None
-    N.check(lib.cqlrec_eval_topk(rec_idx.data_ptr(), n, kmax, None if rec_rows is None else rec_rows.data_ptr(),
-                                 gt_offsets.data_ptr(), gt_items.data_ptr(), ks_arr, len(ks), ws.data_ptr(), ws_bytes,
-                                 None if per_user is None else per_user.data_ptr(), sums.data_ptr(),
-                                 torch.cuda.current_stream().cuda_stream), "eval_topk")
+    Engine(dev).call("eval_topk", rec_idx, n, kmax, rec_rows, gt_offsets, gt_items, (C.c_int32 * len(ks))(*ks), len(ks),
+                     Ws(n, len(ks)), per_user, sums)
     return sums.cpu().numpy().reshape(len(METRICS), len(ks)), per_user
 
 
@@ -72,14 +67,6 @@ def _device() -> torch.device:
     return torch.device("cuda", torch.cuda.current_device())
 
 
-def _stream() -> int:
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _ptr(t: Optional[torch.Tensor]):
-    return None if t is None else t.data_ptr()
-
-
 def _ks_list(k) -> List[int]:
     ks = sorted({int(x) for x in ([k] if isinstance(k, (int, np.integer)) else k)})
     if not ks or ks[0] <= 0 or len(ks) > 8:
@@ -93,7 +80,6 @@ def frame_to_block(row: torch.Tensor, item: torch.Tensor, rel: torch.Tensor, n_u
     """Frame columns on the device -> (rec_idx, rec_val, rec_pos, rec_w), each [n_users x kmax] or None
     (cqlrec_recs_frame_to_block).  `row` int32: the frame row's index into the evaluated users, anything outside
     0..n_users-1 for a user that is not evaluated."""
-    lib = N.load()
     dev = item.device
     n_rows = int(item.numel())
     if n_rows and bool(torch.isnan(rel).any()):
@@ -104,11 +90,8 @@ def frame_to_block(row: torch.Tensor, item: torch.Tensor, rel: torch.Tensor, n_u
     val = torch.empty((n_users, kmax), dtype=torch.float64, device=dev) if want_val else None
     pos = torch.empty((n_users, kmax), dtype=torch.int32, device=dev) if want_pos else None
     w = torch.empty((n_users, kmax), dtype=torch.float64, device=dev) if payload is not None else None
-    ws_bytes = int(lib.cqlrec_recs_frame_to_block_ws_bytes(n_rows, n_users))
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    N.check(lib.cqlrec_recs_frame_to_block(_ptr(row), _ptr(item), _ptr(rel), _ptr(payload), n_rows, n_users, kmax,
-                                           int(bool(dedup)), ws.data_ptr(), ws_bytes, rec.data_ptr(), _ptr(val), _ptr(pos),
-                                           _ptr(w), _stream()), "recs_frame_to_block")
+    Engine(dev).call("recs_frame_to_block", row, item, rel, payload, n_rows, n_users, kmax, int(bool(dedup)),
+                     Ws(n_rows, n_users), rec, val, pos, w)
     return rec, val, pos, w
 
 
@@ -118,41 +101,31 @@ def evaluate_extras(rec_idx: torch.Tensor, ks: Sequence[int], gt_offsets: Option
                     rec_w: Optional[torch.Tensor] = None):
     """(sums float64 [4 x n_ks] on the host, per_user float64 [n x 4 x n_ks] on the device) in the order of EXTRAS
     (cqlrec_eval_extras); a metric whose input is absent comes out 0."""
-    lib = N.load()
     ks = [int(k) for k in ks]
     n, kmax = int(rec_idx.shape[0]), int(rec_idx.shape[1])
     dev = rec_idx.device
-    ks_arr = (C.c_int32 * len(ks))(*ks)
-    ws_bytes = int(lib.cqlrec_eval_extras_ws_bytes(n, len(ks)))
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
     sums = torch.zeros(len(EXTRAS) * len(ks), dtype=torch.float64, device=dev)
     per_user = torch.empty((n, len(EXTRAS), len(ks)), dtype=torch.float64, device=dev)
-    N.check(lib.cqlrec_eval_extras(rec_idx.data_ptr(), n, kmax, _ptr(rec_rows), _ptr(gt_offsets), _ptr(gt_items),
-                                   _ptr(base_idx), 0 if base_idx is None else int(base_idx.shape[1]), _ptr(item_w),
-                                   0 if item_w is None else int(item_w.numel()), _ptr(rec_w), ks_arr, len(ks),
-                                   ws.data_ptr(), ws_bytes, per_user.data_ptr(), sums.data_ptr(), _stream()), "eval_extras")
+    Engine(dev).call("eval_extras", rec_idx, n, kmax, rec_rows, gt_offsets, gt_items, base_idx,
+                     0 if base_idx is None else int(base_idx.shape[1]), item_w, 0 if item_w is None else int(item_w.numel()),
+                     rec_w, (C.c_int32 * len(ks))(*ks), len(ks), Ws(n, len(ks)), per_user, sums)
     return sums.cpu().numpy().reshape(len(EXTRAS), len(ks)), per_user
 
 
 def item_user_counts(item: torch.Tensor, user: torch.Tensor, n_items: int):
     """(distinct users per item int32 [n_items], distinct users of the log) -- cqlrec_eval_item_user_counts."""
-    lib = N.load()
     dev = item.device
     n_rows = int(item.numel())
     cnt = torch.zeros(n_items, dtype=torch.int32, device=dev)
     if n_rows == 0:
         return cnt, 0
     nu = torch.zeros(1, dtype=torch.int64, device=dev)
-    ws_bytes = int(lib.cqlrec_eval_item_user_counts_ws_bytes(n_rows))
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    N.check(lib.cqlrec_eval_item_user_counts(item.data_ptr(), user.data_ptr(), n_rows, n_items, ws.data_ptr(), ws_bytes,
-                                             cnt.data_ptr(), nu.data_ptr(), _stream()), "eval_item_user_counts")
+    Engine(dev).call("eval_item_user_counts", item, user, n_rows, n_items, Ws(n_rows), cnt, nu)
     return cnt, int(nu.item())
 
 
 def surprisal_weights(item: torch.Tensor, user: torch.Tensor) -> torch.Tensor:
     """Per-item self-information of a log, normalised (replay/metrics/surprisal.py:57-63): float64 [max item + 1]."""
-    lib = N.load()
     if int(item.numel()) == 0:
         raise ValueError("Surprisal needs a log with at least two users")
     n_items = int(item.max()) + 1
@@ -160,14 +133,12 @@ def surprisal_weights(item: torch.Tensor, user: torch.Tensor) -> torch.Tensor:
     if n_users < 2:
         raise ValueError("Surprisal needs a log with at least two users: log2(1) = 0 leaves the weights undefined")
     w = torch.empty(n_items, dtype=torch.float64, device=item.device)
-    N.check(lib.cqlrec_eval_surprisal_weights(cnt.data_ptr(), n_items, n_users, w.data_ptr(), _stream()),
-            "eval_surprisal_weights")
+    Engine(item.device).call("eval_surprisal_weights", cnt, n_items, n_users, w)
     return w
 
 
 def coverage_counts(rec_idx: torch.Tensor, rec_pos: torch.Tensor, ks: Sequence[int]) -> List[int]:
     """For each k: how many items have a best position <= k (cqlrec_eval_coverage)."""
-    lib = N.load()
     ks = [int(k) for k in ks]
     n, kmax = int(rec_idx.shape[0]), int(rec_idx.shape[1])
     n_items = int(rec_idx.max()) + 1 if n else 0
@@ -176,8 +147,7 @@ def coverage_counts(rec_idx: torch.Tensor, rec_pos: torch.Tensor, ks: Sequence[i
     dev = rec_idx.device
     best = torch.empty(n_items, dtype=torch.int32, device=dev)
     counts = torch.zeros(len(ks), dtype=torch.int64, device=dev)
-    N.check(lib.cqlrec_eval_coverage(rec_idx.data_ptr(), rec_pos.data_ptr(), n, kmax, n_items, (C.c_int32 * len(ks))(*ks),
-                                     len(ks), best.data_ptr(), counts.data_ptr(), _stream()), "eval_coverage")
+    Engine(dev).call("eval_coverage", rec_idx, rec_pos, n, kmax, n_items, (C.c_int32 * len(ks))(*ks), len(ks), best, counts)
     return [int(c) for c in counts.cpu().tolist()]
 
 
@@ -425,21 +395,18 @@ class NCISPrecision(Metric):
         self._keys, self._vals = key[order].contiguous(), prev["relevance"][order].contiguous()
 
     def _values(self, rec, users, ks, g_off, g_items, dev):
-        lib = N.load()
+        eng = Engine(dev)
         n, kmax = int(users.numel()), ks[-1]
         n_rows = int(rec["item_idx"].numel())
         prev = torch.zeros(n_rows, dtype=torch.float64, device=dev)
         if n_rows:
             if self._by_user and int(rec["user_idx"].min()) < 0:
                 raise ValueError("user_idx must be non-negative")
-            N.check(lib.cqlrec_recs_join_prev(_ptr(self._keys), _ptr(self._vals), int(self._keys.numel()),
-                                              rec["user_idx"].data_ptr() if self._by_user else None,
-                                              rec["item_idx"].data_ptr(), n_rows, prev.data_ptr(), _stream()),
-                    "recs_join_prev")
+            eng.call("recs_join_prev", self._keys, self._vals, int(self._keys.numel()),
+                     rec["user_idx"] if self._by_user else None, rec["item_idx"], n_rows, prev)
         block, val, _, w = frame_to_block(_rows_of(users, rec["user_idx"]), rec["item_idx"], rec["relevance"], n, kmax,
                                           dedup=False, payload=prev, want_val=True)
-        N.check(lib.cqlrec_recs_ncis_weights(block.data_ptr(), val.data_ptr(), w.data_ptr(), n, kmax,
-                                             _ACTIVATIONS[self.activation], self.threshold, _stream()), "recs_ncis_weights")
+        eng.call("recs_ncis_weights", block, val, w, n, kmax, _ACTIVATIONS[self.activation], self.threshold)
         self._last_block = (block, val, w)       # the enriched lists, for inspection
         sums, pu = evaluate_extras(block, ks, g_off, g_items, rec_w=w)
         return pu[:, self._EXTRA_INDEX, :].contiguous(), sums[self._EXTRA_INDEX]
@@ -559,7 +526,6 @@ def item_distribution(log, recommendations, k: int):
     """Item popularity in `log` and in the top-k `recommendations` (replay/distributions.py:62-94): a pandas frame
     [item_idx, user_count, rec_count] ordered by (user_count, item_idx); both counts are numbers of distinct users."""
     import pandas as pd
-    lib = N.load()
     dev = _device()
     lg = _columns(log, dev)
     rec = _columns(recommendations, dev, need_rel=True)
@@ -576,8 +542,7 @@ def item_distribution(log, recommendations, k: int):
         # distinct users per item within the top k rows: a block cut at k with repeats dropped holds an item once per user
         block, _, _, _ = frame_to_block(_rows_of(users, rec["user_idx"]), rec["item_idx"], rec["relevance"],
                                         int(users.numel()), int(k))
-        N.check(lib.cqlrec_eval_item_hist(block.data_ptr(), int(users.numel()), int(k), n_items, rec_count.data_ptr(),
-                                          _stream()), "eval_item_hist")
+        Engine(dev).call("eval_item_hist", block, int(users.numel()), int(k), n_items, rec_count)
     present = torch.nonzero((user_count > 0) | (rec_count > 0)).flatten()
     uc, rc = user_count[present].to(torch.int64), rec_count[present].to(torch.int64)
     order = torch.argsort(uc * n_items + present, stable=True)

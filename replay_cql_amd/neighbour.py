@@ -20,7 +20,9 @@ import pandas as pd
 import torch
 
 from . import _prepare as P
-from .recommender_api import REC_COLUMNS, PandasRecommender, to_pandas
+from ._device import Ws
+from ._log import dense_ids, float_column, normalise, open_log
+from .device_recommender import DeviceRecommender
 
 __all__ = ["NeighbourRec", "ItemKNN"]
 
@@ -33,16 +35,13 @@ class Neigh(P.Feat):
     def weights(self, user, item, relevance, ucount, icount, n_items: int, weighting, k1: float, b: float):
         n = user.numel()
         out = self._empty(n, torch.float64)
-        self.N.check(self.lib.cqlrec_neighbour_weights(user.data_ptr(), item.data_ptr(), self._p(relevance),
-                                                       ucount.data_ptr(), icount.data_ptr(), n, int(n_items),
-                                                       self.N.NEIGHBOUR_WEIGHTINGS[weighting], float(k1), float(b),
-                                                       out.data_ptr(), self.stream), "neighbour_weights")
+        self.call("neighbour_weights", user, item, relevance, ucount, icount, n, int(n_items),
+                  self.N.NEIGHBOUR_WEIGHTINGS[weighting], float(k1), float(b), out)
         return out
 
     def norms(self, perm, offsets, w, n_groups: int):
         out = self._empty(n_groups, torch.float64)
-        self.N.check(self.lib.cqlrec_neighbour_norms(perm.data_ptr(), offsets.data_ptr(), w.data_ptr(), perm.numel(),
-                                                     n_groups, out.data_ptr(), self.stream), "neighbour_norms")
+        self.call("neighbour_norms", perm, offsets, w, perm.numel(), n_groups, out)
         return out
 
     def topk(self, mode: int, L, R, n_mid: int, n_cols: int, k: int, max_tuples: int, norm_q=None, norm_j=None,
@@ -60,30 +59,22 @@ class Neigh(P.Feat):
         if n_q == 0:
             return ids, vals, count
         eprefix, rprefix, stats = self._empty(nnz + 1, torch.int64), self._empty(n_q + 1, torch.int64), self._empty(2, torch.int64)
-        nb = int(self.lib.cqlrec_neighbour_count_ws_bytes(nnz))
-        ws = self._ws(nb)
-        self.N.check(self.lib.cqlrec_neighbour_count(l_off.data_ptr(), self._p(l_col), n_q, nnz, r_off.data_ptr(), n_mid,
-                                                     ws.data_ptr(), nb, eprefix.data_ptr(), rprefix.data_ptr(),
-                                                     stats.data_ptr(), self.stream), "neighbour_count")
+        # the count's workspace is gone when `call` returns, before the top-k's is allocated: that bounds peak memory
+        self.call("neighbour_count", l_off, l_col, n_q, nnz, r_off, n_mid, Ws(nnz), eprefix, rprefix, stats)
         total, largest = stats.cpu().tolist()
         host_prefix = rprefix.cpu()                      # the chunks are cut on the host: 8 (n_q + 1) bytes
         self.expansion = (int(total), int(largest))
         if int(max_tuples) < 1:
             raise ValueError(f"max_tuples must be positive, got {max_tuples}")
         max_tuples = max(1, min(int(max_tuples), int(total)))   # no workspace beyond the expansion; the result is the same
-        nb = int(self.lib.cqlrec_neighbour_topk_ws_bytes(n_q, n_cols, int(max_tuples), int(largest), int(k)))
+        nb = self.ws_bytes("neighbour_topk", n_q, n_cols, int(max_tuples), int(largest), int(k))
         if nb == 0:
             raise ValueError(f"neighbour top-k: k={k} (1..{self.N.NEIGHBOUR_MAX_K}), max_tuples={max_tuples} or a row of "
                              f"{largest} tuples (below 2^31) is out of range")
-        del ws
-        ws = self._ws(nb if total else 0)
         s_off, s_col = seen if seen is not None else (None, None)
-        self.N.check(self.lib.cqlrec_neighbour_topk(
-            int(mode), l_off.data_ptr(), self._p(l_col), self._p(l_val), n_q, nnz, r_off.data_ptr(), self._p(r_col),
-            self._p(r_val), n_mid, n_cols, eprefix.data_ptr(), host_prefix.data_ptr(), int(max_tuples), int(largest), int(k),
-            self._p(norm_q), self._p(norm_j), float(shrink), self._p(mask), self._p(s_off), self._p(s_col),
-            ws.data_ptr() if total else None, nb, ids.data_ptr(), vals.data_ptr(), count.data_ptr(), self.stream),
-            "neighbour_topk")
+        self.call("neighbour_topk", int(mode), l_off, l_col, l_val, n_q, nnz, r_off, r_col, r_val, n_mid, n_cols, eprefix,
+                  host_prefix, int(max_tuples), int(largest), int(k), norm_q, norm_j, float(shrink), mask, s_off, s_col,
+                  self._ws(nb) if total else None, nb, ids, vals, count)
         return ids, vals, count
 
     def pair_scores(self, pair_user, pair_item, h_off, h_item, n_users: int, S, n_s_rows: int):
@@ -91,27 +82,12 @@ class Neigh(P.Feat):
         s_off, s_col, s_val = S
         n = pair_user.numel()
         score, present = self._empty(n, torch.float64), self._empty(n, torch.uint8)
-        self.N.check(self.lib.cqlrec_neighbour_pair_scores(pair_user.data_ptr(), pair_item.data_ptr(), n, h_off.data_ptr(),
-                                                           self._p(h_item), n_users, s_off.data_ptr(), self._p(s_col),
-                                                           self._p(s_val), n_s_rows, score.data_ptr(), present.data_ptr(),
-                                                           self.stream), "neighbour_pair_scores")
+        self.call("neighbour_pair_scores", pair_user, pair_item, n, h_off, h_item, n_users, s_off, s_col, s_val, n_s_rows,
+                  score, present)
         return score, present
 
 
-def _id_tensor(ids, device) -> Optional[torch.Tensor]:
-    """distinct non-negative ids as an int64 device tensor, in the order given"""
-    if ids is None:
-        return None
-    if torch.is_tensor(ids):
-        t = ids.to(device=device, dtype=torch.int64).flatten()
-    else:
-        if isinstance(ids, pd.DataFrame):
-            ids = ids.iloc[:, 0]
-        t = torch.as_tensor(np.asarray(pd.unique(pd.Series(ids)), dtype=np.int64), device=device)
-    return t[t >= 0]
-
-
-class NeighbourRec(PandasRecommender):
+class NeighbourRec(DeviceRecommender):
     """Base of the models that hold an item-to-item similarity table and need the log at prediction time.
 
     The score of (u, j) is the sum over the LOG ROWS (u, i) of S[i -> j]: duplicated rows count, the log's relevance does
@@ -129,6 +105,7 @@ class NeighbourRec(PandasRecommender):
     item_to_item_metrics = ["similarity"]
     _similarity_metric = "similarity"
     max_tuples: int = DEFAULT_MAX_TUPLES
+    _state_attr = "_sim"
 
     # -------------------------------------------------------------------------------- bookkeeping
     @property
@@ -153,11 +130,6 @@ class NeighbourRec(PandasRecommender):
         self._similarity_metric = value
 
     # -------------------------------------------------------------------------------- the table
-    def _fitted(self):
-        if "_sim" not in self.__dict__:
-            raise RuntimeError(f"{self} model is not fitted")
-        return self._sim
-
     @property
     def similarity_device(self):
         """(ids int32 [n_items, K] padded with -1, values float64 [n_items, K], counts int32 [n_items]) on the device;
@@ -169,7 +141,7 @@ class NeighbourRec(PandasRecommender):
         """[item_idx_one, item_idx_two, similarity], by item_idx_one ascending, then rank"""
         if "_similarity_frame" not in self.__dict__:
             ids, vals, count = self._fitted()
-            keep = (torch.arange(ids.shape[1], device=ids.device)[None, :] < count[:, None]).cpu().numpy()
+            keep = self._first(ids, count).cpu().numpy()
             one = np.broadcast_to(np.arange(ids.shape[0], dtype=np.int32)[:, None], keep.shape)[keep]
             self._similarity_frame = pd.DataFrame({"item_idx_one": one, "item_idx_two": ids.cpu().numpy()[keep],
                                                    "similarity": vals.cpu().numpy()[keep]})
@@ -183,7 +155,7 @@ class NeighbourRec(PandasRecommender):
             off = torch.zeros(n_rows + 1, dtype=torch.int64, device=ids.device)
             off[1:ids.shape[0] + 1] = torch.cumsum(count.to(torch.int64), 0)
             off[ids.shape[0] + 1:] = off[ids.shape[0]]
-            keep = torch.arange(ids.shape[1], device=ids.device)[None, :] < count[:, None]
+            keep = self._first(ids, count)
             col, val = ids[keep].contiguous(), vals[keep].contiguous()
             row = torch.arange(ids.shape[0], device=ids.device, dtype=torch.int64)[:, None].expand_as(ids)[keep]
             by_col = torch.argsort(row * max(1, ids.shape[0]) + col.to(torch.int64))
@@ -194,7 +166,7 @@ class NeighbourRec(PandasRecommender):
     # -------------------------------------------------------------------------------- predict on the device
     def _history(self, lg):
         """(engine, users' CSR offsets, items of the rows ordered by (user, item, row), n_users, largest item + 1)"""
-        (user, n_users), (item, n_items) = P.dense_ids(lg, ["user_idx", "item_idx"])
+        (user, n_users), (item, n_items) = dense_ids(lg, ["user_idx", "item_idx"])
         eng = Neigh(lg.device)
         perm, off = eng.segments(user, n_users, item.to(torch.int64))
         return eng, off, item[perm.long()].contiguous(), n_users, n_items
@@ -204,9 +176,9 @@ class NeighbourRec(PandasRecommender):
         sim_ids = self._fitted()[0]
         if log is None:
             raise ValueError("log is not provided, but it is required for prediction")
-        lg = P.open_log(P.normalise(log), str(self))
+        lg = open_log(normalise(log), str(self))
         dev, n_cols = lg.device, int(sim_ids.shape[0])
-        users, items = _id_tensor(users, dev), _id_tensor(items, dev)
+        users, items = self._id_tensor(users, dev), self._id_tensor(items, dev)
         if lg.n == 0:
             users = users if users is not None else torch.empty(0, dtype=torch.int64, device=dev)
             m = users.numel()
@@ -226,34 +198,18 @@ class NeighbourRec(PandasRecommender):
         l_col = h_item[torch.repeat_interleave(off[uc], lens) + within].contiguous()
         l_val = torch.ones(nnz, dtype=torch.float64, device=dev)
         n_mid = max(n_cols, n_log_items)
-        mask = None
-        if items is not None:
-            mask = torch.zeros(n_cols, dtype=torch.uint8, device=dev)
-            mask[items[items < n_cols]] = 1
+        mask = self._item_mask(items, n_cols, dev)
         seen = (l_off, l_col) if filter_seen_items else None
         ids, vals, count = eng.topk(eng.N.NEIGHBOUR_PREDICT, (l_off, l_col, l_val), self._csr(n_mid)[0], n_mid, n_cols, int(k),
                                     self.max_tuples, mask=mask, seen=seen)
         self.expansion = eng.expansion
         return users, ids, vals, count
 
-    def recommend(self, log, k: int, users=None, items=None, filter_seen_items: bool = True) -> Dict[str, torch.Tensor]:
-        """The k best items of every user as device columns {user_idx int32, item_idx int32, relevance float64}, in the
-        order of `users` (None: the users of the log, ascending), then rank.  `log`: pandas, pyarrow or a dict of device
-        tensors; `users` / `items`: tensors, iterables or None (every item that has a similarity row)."""
-        users, ids, vals, count = self._recommend(log, int(k), users, items, filter_seen_items)
-        keep = torch.arange(ids.shape[1], device=ids.device)[None, :] < count[:, None]
-        return {"user_idx": users.to(torch.int32)[:, None].expand_as(ids)[keep], "item_idx": ids[keep], "relevance": vals[keep]}
-
-    def _predict(self, log, k: int, users: pd.DataFrame, items: pd.DataFrame, user_features=None, item_features=None,
-                 filter_seen_items: bool = True) -> pd.DataFrame:
-        out = self.recommend(log, k, users["user_idx"], items["item_idx"], filter_seen_items)
-        return pd.DataFrame({c: out[c].cpu().numpy() for c in REC_COLUMNS})
-
     def _predict_pairs(self, pairs: pd.DataFrame, log=None, user_features=None, item_features=None) -> pd.DataFrame:
         sim_ids = self._fitted()[0]
         if log is None:
             raise ValueError("log is not provided, but it is required for prediction")
-        lg = P.open_log(P.normalise(log), str(self))
+        lg = open_log(normalise(log), str(self))
         if lg.n == 0 or len(pairs) == 0:
             return pd.DataFrame({"user_idx": np.empty(0, np.int32), "item_idx": np.empty(0, np.int32),
                                  "relevance": np.empty(0, np.float64)})
@@ -314,24 +270,6 @@ class ItemKNN(NeighbourRec):
         return {"shrink": self.shrink, "use_relevance": self.use_relevance, "num_neighbours": self.num_neighbours,
                 "weighting": self.weighting}
 
-    def _fit_wrap(self, log, user_features=None, item_features=None) -> None:
-        """pandas and Spark logs go through the template; a pyarrow log or a dict of device tensors stays on the device"""
-        src = P.normalise(log)
-        if isinstance(src, pd.DataFrame) or type(src).__module__.startswith("pyspark"):
-            super()._fit_wrap(src, user_features, item_features)
-            return
-        lg = P.open_log(src, str(self))
-        if lg.n == 0:
-            raise ValueError("cannot fit an empty log")
-        users, items = torch.unique(lg.ids("user_idx")).cpu().numpy(), torch.unique(lg.ids("item_idx")).cpu().numpy()
-        self.fit_users, self.fit_items = pd.DataFrame({"user_idx": users}), pd.DataFrame({"item_idx": items})
-        self._num_users, self._num_items = len(users), len(items)
-        self._user_dim_size, self._item_dim_size = int(users.max()) + 1, int(items.max()) + 1
-        self._fit_device(lg)
-
-    def _fit(self, log: pd.DataFrame, user_features=None, item_features=None) -> None:
-        self._fit_device(P.open_log(log, str(self)))
-
     def _fit_device(self, lg) -> None:
         if self.weighting not in self._search_space["weighting"]["args"]:
             raise ValueError("weighting must be one of ['tf_idf', 'bm25']")
@@ -339,10 +277,10 @@ class ItemKNN(NeighbourRec):
         k = int(self.num_neighbours)
         if not 1 <= k <= N.N.NEIGHBOUR_MAX_K:
             raise ValueError(f"num_neighbours must be in 1..{N.N.NEIGHBOUR_MAX_K}, got {self.num_neighbours}")
-        (user, n_users), (item, n_items) = P.dense_ids(lg, ["user_idx", "item_idx"])
+        (user, n_users), (item, n_items) = dense_ids(lg, ["user_idx", "item_idx"])
         rel = None
         if self.use_relevance:
-            rel = P.float_column(lg, "relevance")
+            rel = float_column(lg, "relevance")
             if bool(torch.isnan(rel).any()):
                 raise ValueError("relevance contains NaN")
         ucount, icount = N.count(user, n_users), N.count(item, n_items)

@@ -38,6 +38,8 @@ import numpy as np
 import torch
 
 from . import data as D
+from ._device import Engine, Ws
+from ._log import _Log, dense_ids, float_column
 
 __all__ = ["Splitter", "UserSplitter", "DateSplitter", "RandomSplitter", "NewUsersSplitter", "ColdUserRandomSplitter",
            "k_folds"]
@@ -89,202 +91,62 @@ def _threshold_key(test_start, ts_kind: str) -> int:
     return int(D.timestamp_key(np.array([ns / 10 ** 9], dtype=np.float64))[0])
 
 
-# ----------------------------------------------------------------------------------------------------------
-# the log, whatever kind it came as
-# ----------------------------------------------------------------------------------------------------------
-class _Log:
-    """Columns of a log as device tensors (made on demand) + `take(rows)` that gives back the kind that came in."""
-
-    def __init__(self, log):
-        self.kind, self.src = None, log
-        try:
-            import pandas as pd
-            if isinstance(log, pd.DataFrame):
-                self.kind, self.n, self.names = "pandas", len(log), list(log.columns)
-        except ImportError:  # pragma: no cover
-            pass
-        if self.kind is None and isinstance(log, dict):
-            tens = [v for v in log.values() if torch.is_tensor(v)]
-            if not tens:
-                raise ValueError("a dict log must hold device tensors")
-            self.kind, self.n, self.names = "device", int(tens[0].shape[0]), list(log.keys())
-            self.device = tens[0].device
-            if any(t.shape[0] != self.n or t.device != self.device for t in tens):
-                raise ValueError("log columns differ in length or device")
-        if self.kind is None:
-            import pyarrow as pa
-            if isinstance(log, pa.RecordBatch):
-                self.kind, self.table = "batch", pa.Table.from_batches([log])
-            elif isinstance(log, pa.Table):
-                self.kind, self.table = "table", log
-            else:
-                batches = list(log)
-                if not batches or not all(isinstance(b, pa.RecordBatch) for b in batches):
-                    raise ValueError(f"cannot split a log of type {type(log)}: pandas, pyarrow or a dict of tensors")
-                self.kind, self.table = "table", pa.Table.from_batches(batches)
-            self.n, self.names = self.table.num_rows, list(self.table.schema.names)
-        if self.kind != "device":
-            if not torch.cuda.is_available():
-                from ._native import CqlrecError
-                raise CqlrecError("split() needs a GPU: the splitters have no CPU path")
-            self.device = torch.device("cuda", torch.cuda.current_device())
-        self.ts_kind = None
-
-    def _host(self, name: str) -> np.ndarray:
-        if name not in self.names:
-            raise ValueError(f"log has no column {name}")
-        if self.kind == "pandas":
-            return self.src[name].to_numpy()
-        col = self.table.column(name)
-        if col.null_count:
-            raise ValueError(f"column {name} contains nulls")
-        return col.combine_chunks().to_numpy(zero_copy_only=False)
-
-    def ids(self, name: str):
-        if self.kind == "device":
-            if name not in self.names:
-                raise ValueError(f"log has no column {name}")
-            t = self.src[name]
-            if t.dtype.is_floating_point:
-                raise ValueError(f"column {name} must be an integer column")
-            return t.to(torch.int64).contiguous()         # narrowed after the range check
-        a = self._host(name)
-        if a.dtype.kind not in "iu":
-            raise ValueError(f"column {name} must be an integer column, got {a.dtype}")
-        return D._dev_col(a.astype(np.int64, copy=False), torch.int64, self.device)
-
-    def key(self, name: str):
-        """timestamp_key of the column `name` as an int64 device tensor; sets ts_kind (datetime / int / float)."""
-        if self.kind == "device":
-            if name not in self.names:
-                raise ValueError(f"log has no column {name}")
-            t = self.src[name]
-            self.ts_kind = "float" if t.dtype.is_floating_point else "int"
-            return D.timestamp_key(t).contiguous()
-        a = self._host(name)
-        self.ts_kind = {"M": "datetime", "i": "int", "u": "int", "f": "float"}.get(a.dtype.kind)
-        if self.ts_kind is None:
-            raise ValueError(f"column {name} has unsupported dtype {a.dtype}")
-        return D._dev_col(D.timestamp_key(a), torch.int64, self.device)
-
-    def relevance(self):
-        if self.kind == "device":
-            if "relevance" not in self.names:
-                raise ValueError("log has no column relevance")
-            return self.src["relevance"].to(torch.float64).contiguous()
-        return D._dev_col(self._host("relevance").astype(np.float64, copy=False), torch.float64, self.device)
-
-    def take(self, rows):
-        if self.kind == "device":
-            return {k: (v[rows] if torch.is_tensor(v) else v) for k, v in self.src.items()}
-        idx = rows.cpu().numpy()
-        if self.kind == "pandas":
-            return self.src.iloc[idx].reset_index(drop=True)
-        import pyarrow as pa
-        out = self.table.take(pa.array(idx))
-        if self.kind == "batch":
-            out = out.combine_chunks()
-            return out.to_batches()[0] if out.num_rows else pa.RecordBatch.from_pylist([], schema=out.schema)
-        return out
-
-
-class _Run:
+class _Run(Engine):
     """One split on the device: the range-checked id columns and the calls into csrc/split.hip."""
 
     def __init__(self, log: _Log, user_col: str, item_col: Optional[str], need_items: bool):
-        from . import _native as N
-        self.N, self.lib, self.log, self.dev, self.n = N, N.load(), log, log.device, log.n
+        self.log, self.n = log, log.n
         if self.n >= 1 << 31:
             raise ValueError(f"a log of {self.n} rows is beyond the splitters' 2^31 - 1")
-        u = log.ids(user_col)
-        i = log.ids(item_col) if need_items and item_col is not None else None
-        if need_items and i is None:
+        if need_items and item_col is None:
+            log.ids(user_col)                            # a bad user column is reported first, as it always was
             raise ValueError("drop_cold_items needs an item column")
-        # the kernels index count arrays and bitmaps with the ids: range-check them first (one small sync)
-        lim = torch.stack([u.min(), u.max()] + ([i.min(), i.max()] if i is not None else [])).cpu().tolist()
-        if lim[0] < 0 or (i is not None and lim[2] < 0):
-            raise ValueError("user_idx / item_idx must be non-negative dense indices")
-        if max(lim) >= (1 << 31) - 1:
-            raise ValueError("user_idx / item_idx must be below 2^31 - 1")
-        self.n_users = int(lim[1]) + 1
-        self.n_items = int(lim[3]) + 1 if i is not None else 1
-        self.u = u.to(torch.int32)
-        self.i = None if i is None else i.to(torch.int32)
-        self.stream = torch.cuda.current_stream(self.dev).cuda_stream
-
-    def _ws(self, nbytes: int):
-        return torch.empty(int(nbytes), dtype=torch.uint8, device=self.dev)
-
-    def _empty(self, n, dt):
-        return torch.empty(int(n), dtype=dt, device=self.dev)
-
-    @staticmethod
-    def _p(t):
-        return None if t is None else t.data_ptr()
+        ids = dense_ids(log, [user_col] + ([item_col] if need_items else []), "user_idx / item_idx")
+        (self.u, self.n_users), (self.i, self.n_items) = ids[0], ids[1] if need_items else (None, 1)
+        super().__init__(log.device)
 
     def rank(self, key, shuffle: bool, seed: int):
         """(rank int32[n], count int32[n_users], n_present int64[1]) -- cqlrec_split_rank"""
         rank, count = self._empty(self.n, torch.int32), self._empty(self.n_users, torch.int32)
         present = self._empty(1, torch.int64)
-        nb = int(self.lib.cqlrec_split_rank_ws_bytes(self.n, self.n_users))
-        ws = self._ws(nb)
-        self.N.check(self.lib.cqlrec_split_rank(self.u.data_ptr(), self._p(key), self.n, self.n_users, int(shuffle), seed,
-                                                ws.data_ptr(), nb, rank.data_ptr(), count.data_ptr(), present.data_ptr(),
-                                                self.stream), "split_rank")
+        self.call("split_rank", self.u, key, self.n, self.n_users, int(shuffle), seed, Ws(self.n, self.n_users), rank, count,
+                  present)
         return rank, count, present
 
     def kth_key(self, key, m: int):
         out = self._empty(1, torch.int64)
-        nb = int(self.lib.cqlrec_split_kth_key_ws_bytes(self.n))
-        ws = self._ws(nb)
-        self.N.check(self.lib.cqlrec_split_kth_key(key.data_ptr(), self.n, int(m), ws.data_ptr(), nb, out.data_ptr(),
-                                                   self.stream), "split_kth_key")
+        self.call("split_kth_key", key, self.n, int(m), Ws(self.n), out)
         return out
 
     def new_users(self, key, test_size: float):
         start, thr = self._empty(self.n_users, torch.int64), self._empty(1, torch.int64)
-        nb = int(self.lib.cqlrec_split_new_users_ws_bytes(self.n_users))
-        ws = self._ws(nb)
-        self.N.check(self.lib.cqlrec_split_new_users(self.u.data_ptr(), key.data_ptr(), self.n, self.n_users,
-                                                     float(test_size), ws.data_ptr(), nb, start.data_ptr(), thr.data_ptr(),
-                                                     self.stream), "split_new_users")
+        self.call("split_new_users", self.u, key, self.n, self.n_users, float(test_size), Ws(self.n_users), start, thr)
         return start, thr
 
     def pick_users(self, count, seed: int, n_pick: int):
         out = self._empty(self.n_users, torch.uint8)
-        nb = int(self.lib.cqlrec_split_pick_users_ws_bytes(self.n_users))
-        ws = self._ws(nb)
-        self.N.check(self.lib.cqlrec_split_pick_users(count.data_ptr(), self.n_users, seed, int(n_pick), ws.data_ptr(), nb,
-                                                      out.data_ptr(), self.stream), "split_pick_users")
+        self.call("split_pick_users", count, self.n_users, seed, int(n_pick), Ws(self.n_users), out)
         return out
 
     def classify(self, rule: int, key=None, rank=None, count=None, test_user=None, user_start=None, threshold=None,
                  n: int = 0, fold: int = 0, frac: float = 0.0, seed: int = 0):
         is_train, is_test = self._empty(self.n, torch.uint8), self._empty(self.n, torch.uint8)
-        self.N.check(self.lib.cqlrec_split_classify(rule, self.u.data_ptr(), self._p(key), self._p(rank), self._p(count),
-                                                    self._p(test_user), self._p(user_start), self._p(threshold), self.n,
-                                                    int(n), int(fold), float(frac), seed, is_train.data_ptr(),
-                                                    is_test.data_ptr(), self.stream), "split_classify")
+        self.call("split_classify", rule, self.u, key, rank, count, test_user, user_start, threshold, self.n, int(n),
+                  int(fold), float(frac), seed, is_train, is_test)
         return is_train, is_test
 
     def filter_test(self, is_train, is_test, cold_users: bool, cold_items: bool, zero_rel: bool) -> None:
         if not (cold_users or cold_items or zero_rel):
             return
-        rel = self.log.relevance() if zero_rel else None
-        nb = int(self.lib.cqlrec_split_filter_test_ws_bytes(self.n_users, self.n_items))
-        ws = self._ws(nb)
-        self.N.check(self.lib.cqlrec_split_filter_test(self.u.data_ptr(), self._p(self.i), self._p(rel), is_train.data_ptr(),
-                                                       self.n, self.n_users, self.n_items, int(cold_users), int(cold_items),
-                                                       int(zero_rel), ws.data_ptr(), nb, is_test.data_ptr(), self.stream),
-                     "split_filter_test")
+        if zero_rel and "relevance" not in self.log.names:
+            raise ValueError("log has no column relevance")
+        rel = float_column(self.log, "relevance") if zero_rel else None
+        self.call("split_filter_test", self.u, self.i, rel, is_train, self.n, self.n_users, self.n_items, int(cold_users),
+                  int(cold_items), int(zero_rel), Ws(self.n_users, self.n_items), is_test)
 
     def compact(self, is_train, is_test):
         tr, te, counts = self._empty(self.n, torch.int64), self._empty(self.n, torch.int64), self._empty(2, torch.int64)
-        nb = int(self.lib.cqlrec_split_compact_ws_bytes(self.n))
-        ws = self._ws(nb)
-        self.N.check(self.lib.cqlrec_split_compact(is_train.data_ptr(), is_test.data_ptr(), self.n, ws.data_ptr(), nb,
-                                                   tr.data_ptr(), te.data_ptr(), counts.data_ptr(), self.stream),
-                     "split_compact")
+        self.call("split_compact", is_train, is_test, self.n, Ws(self.n), tr, te, counts)
         n_tr, n_te = counts.cpu().tolist()                   # the one device-to-host sync of the split proper
         return tr[:n_tr], te[:n_te]
 

@@ -57,7 +57,7 @@ def main():
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("als_bench needs a GPU: a CPU run gives no time")
-    from replay_cql_amd import _prepare as P
+    from replay_cql_amd import _log as L
     from replay_cql_amd import als as A
     dev = torch.device("cuda:0")
     log = make_log(args.users, args.items, dev)
@@ -87,9 +87,9 @@ def main():
 
     # the two CSR views, as ALSWrap._fit_device builds them
     eng = A.Als(dev)
-    lg = P.open_log(log, "als_bench")
-    (user, n_users), (item, n_items) = P.dense_ids(lg, ["user_idx", "item_idx"])
-    rel = P.float_column(lg, "relevance")
+    lg = L.open_log(log, "als_bench")
+    (user, n_users), (item, n_items) = L.dense_ids(lg, ["user_idx", "item_idx"])
+    rel = L.float_column(lg, "relevance")
     perm_i, off_i = eng.segments(item, n_items, user.to(torch.int64))
     perm_u, off_u = eng.segments(user, n_users, item.to(torch.int64))
     item_side = (off_i, user[perm_i.long()].contiguous(), rel[perm_i.long()].contiguous())
