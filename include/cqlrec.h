@@ -897,6 +897,41 @@ int cqlrec_als_pair_scores(const int32_t* pair_user, const int32_t* pair_item, i
                            int32_t rank, float* score, uint8_t* valid, cqlrec_stream stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * f10  Association rules on the device (AssociationRulesItemRec of replay/models/association_rules.py; DESIGN.md section
+ * 3.13 is the normative text): the engine of f8 with a third epilogue.  The rules of f5 - f9 carry over: integer atomics
+ * only, the same input gives the same bytes, arguments are validated on the host before any HIP call.  The count pass is
+ * cqlrec_neighbour_count, the chunk loop is the one of cqlrec_neighbour_topk.
+ * --------------------------------------------------------------------------------------------------------- */
+
+/* keep [n_rows] = 1 at ONE row of every distinct (session, item[, relevance]) triple, 0 at the others.  perm [n_rows]: a
+ * permutation of the rows that brings equal triples together (any order by (session, item, relevance value) does); one
+ * thread per position compares its row with the row in front, so a long run of equal rows costs its length.  relevance:
+ * NULL (every weight is 1) or fp64 without NaN; -0.0 and +0.0 are one value.  No scratch. */
+int cqlrec_rules_distinct(const int32_t* session, const int32_t* item, const double* relevance, const int32_t* perm,
+                          int64_t n_rows, uint8_t* keep, cqlrec_stream stream);
+
+/* L = items x sessions and R = sessions x items, both CSR (int64 offsets, int32 columns, fp64 weights) over the distinct
+ * rows that passed the item filter; entry_prefix / row_prefix_host / largest_row as cqlrec_neighbour_count gave them for
+ * (L, R).  For every ordered pair a != b that shares a session:
+ *   pair_count = the number of (row of a, row of b) combinations in one session; pair_relevance p = the sum of
+ *   min(w_a, w_b) over them, in the order of f8's sums (up to 32 terms left to right, more by one wave)
+ *   item_relevance [n_items] (output) = the sum of the weights of an item's rows, one wave per item; A = item_relevance[a],
+ *   C = item_relevance[b], n = (double)num_sessions
+ *   confidence = p / A;   lift = (n * confidence) / C;
+ *   confidence_gain = (C - p == 0) ? +inf : (confidence * (n - A)) / (C - p)        -- each evaluated as written, in fp64
+ * A pair with pair_count < min_pair_count, A == 0 or C == 0 is dropped.  Per a the k best by (lift descending, b
+ * DESCENDING; -0.0 = +0.0): ids [n_items][k] (padded with -1), confidence / lift / confidence_gain [n_items][k] (padded
+ * with 0), count [n_items].  The workspace is cqlrec_neighbour_topk's for n_q = n_cols = n_items; the result does not
+ * depend on max_tuples.  No synchronisation. */
+int64_t cqlrec_rules_topk_ws_bytes(int64_t n_items, int64_t max_tuples, int64_t largest_row, int32_t k);
+int cqlrec_rules_topk(const int64_t* l_off, const int32_t* l_col, const double* l_val, int64_t n_items, int64_t nnz_l,
+                      const int64_t* r_off, const int32_t* r_col, const double* r_val, int64_t n_sessions,
+                      const int64_t* entry_prefix, const int64_t* row_prefix_host, int64_t max_tuples, int64_t largest_row,
+                      int32_t k, int64_t num_sessions, int64_t min_pair_count, void* ws, int64_t ws_bytes, int32_t* ids,
+                      double* confidence, double* lift, double* confidence_gain, int32_t* count, double* item_relevance,
+                      cqlrec_stream stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * Measurement hooks (bench.py): when enabled, every launcher brackets its kernel with a pair of HIP events on
  * the stream it launches on; cqlrec_prof_read synchronises those events and returns, per phase, the summed
  * kernel time in ms and the number of launches, then resets the pool.  Not capturable in a hipGraph; off by

@@ -203,6 +203,10 @@ SIGNATURES = {
     "cqlrec_neighbour_topk": (i32, [i32, vp, vp, vp, i64, i64, vp, vp, vp, i64, i64, vp, vp, i64, i64, i32, vp, vp, f64, vp,
                                     vp, vp, vp, i64, vp, vp, vp, vp]),
     "cqlrec_neighbour_pair_scores": (i32, [vp, vp, i64, vp, vp, i64, vp, vp, vp, i64, vp, vp, vp]),
+    "cqlrec_rules_distinct": (i32, [vp, vp, vp, vp, i64, vp, vp]),
+    "cqlrec_rules_topk_ws_bytes": (i64, [i64, i64, i64, i32]),
+    "cqlrec_rules_topk": (i32, [vp, vp, vp, i64, i64, vp, vp, vp, i64, vp, vp, i64, i64, i32, i64, i64, vp, i64, vp, vp, vp,
+                                vp, vp, vp, vp]),
     "cqlrec_als_gram_ws_bytes": (i64, [i64, i32]),
     "cqlrec_als_gram": (i32, [vp, i64, i32, vp, i64, vp, vp]),
     "cqlrec_als_normal_equations_ws_bytes": (i64, [i64, i64, i32]),

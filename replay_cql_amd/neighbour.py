@@ -44,6 +44,22 @@ class Neigh(P.Feat):
         self.call("neighbour_norms", perm, offsets, w, perm.numel(), n_groups, out)
         return out
 
+    def _count(self, L, R, n_mid: int, max_tuples: int):
+        """The count pass of a product: (entry prefix, the row prefix on the host, total tuples, the largest row's, the
+        tuples a chunk holds).  Sets `self.expansion` and `self.row_prefix`."""
+        l_off, l_col, _ = L
+        n_q, nnz = l_off.numel() - 1, l_col.numel()
+        eprefix, rprefix, stats = self._empty(nnz + 1, torch.int64), self._empty(n_q + 1, torch.int64), self._empty(2, torch.int64)
+        # the count's workspace is gone when `call` returns, before the top-k's is allocated: that bounds peak memory
+        self.call("neighbour_count", l_off, l_col, n_q, nnz, R[0], n_mid, Ws(nnz), eprefix, rprefix, stats)
+        total, largest = stats.cpu().tolist()
+        host_prefix = rprefix.cpu()                      # the chunks are cut on the host: 8 (n_q + 1) bytes
+        self.expansion, self.row_prefix = (int(total), int(largest)), host_prefix
+        if int(max_tuples) < 1:
+            raise ValueError(f"max_tuples must be positive, got {max_tuples}")
+        max_tuples = max(1, min(int(max_tuples), int(total)))   # no workspace beyond the expansion; the result is the same
+        return eprefix, host_prefix, int(total), int(largest), max_tuples
+
     def topk(self, mode: int, L, R, n_mid: int, n_cols: int, k: int, max_tuples: int, norm_q=None, norm_j=None,
              shrink: float = 0.0, mask=None, seen=None):
         """(ids int32 [n_q, k] padded with -1, vals float64 [n_q, k], count int32 [n_q]) of the product of the CSR
@@ -58,15 +74,7 @@ class Neigh(P.Feat):
         self.expansion = (0, 0)
         if n_q == 0:
             return ids, vals, count
-        eprefix, rprefix, stats = self._empty(nnz + 1, torch.int64), self._empty(n_q + 1, torch.int64), self._empty(2, torch.int64)
-        # the count's workspace is gone when `call` returns, before the top-k's is allocated: that bounds peak memory
-        self.call("neighbour_count", l_off, l_col, n_q, nnz, r_off, n_mid, Ws(nnz), eprefix, rprefix, stats)
-        total, largest = stats.cpu().tolist()
-        host_prefix = rprefix.cpu()                      # the chunks are cut on the host: 8 (n_q + 1) bytes
-        self.expansion = (int(total), int(largest))
-        if int(max_tuples) < 1:
-            raise ValueError(f"max_tuples must be positive, got {max_tuples}")
-        max_tuples = max(1, min(int(max_tuples), int(total)))   # no workspace beyond the expansion; the result is the same
+        eprefix, host_prefix, total, largest, max_tuples = self._count(L, R, n_mid, max_tuples)
         nb = self.ws_bytes("neighbour_topk", n_q, n_cols, int(max_tuples), int(largest), int(k))
         if nb == 0:
             raise ValueError(f"neighbour top-k: k={k} (1..{self.N.NEIGHBOUR_MAX_K}), max_tuples={max_tuples} or a row of "
@@ -76,6 +84,34 @@ class Neigh(P.Feat):
                   host_prefix, int(max_tuples), int(largest), int(k), norm_q, norm_j, float(shrink), mask, s_off, s_col,
                   self._ws(nb) if total else None, nb, ids, vals, count)
         return ids, vals, count
+
+    def rules_distinct(self, session, item, relevance, perm):
+        """uint8 [n]: 1 at one row of every distinct (session, item[, relevance]); `perm` brings equal triples together"""
+        keep = self._empty(session.numel(), torch.uint8)
+        self.call("rules_distinct", session, item, relevance, perm, session.numel(), keep)
+        return keep
+
+    def rules_topk(self, L, R, n_sessions: int, k: int, max_tuples: int, num_sessions: int, min_pair_count: int):
+        """(ids int32 [n_items, k] padded with -1, confidence, lift, confidence_gain float64 [n_items, k], count int32
+        [n_items], item_relevance float64 [n_items]) of L = items x sessions and R = sessions x items (section f10)"""
+        l_off, l_col, l_val = L
+        r_off, r_col, r_val = R
+        n_items, nnz = l_off.numel() - 1, l_col.numel()
+        ids = torch.empty((n_items, k), dtype=torch.int32, device=self.dev)
+        planes = [torch.empty((n_items, k), dtype=torch.float64, device=self.dev) for _ in range(3)]
+        count, item_rel = self._empty(n_items, torch.int32), self._empty(n_items, torch.float64)
+        self.expansion = (0, 0)
+        if n_items == 0:
+            return (ids, *planes, count, item_rel)
+        eprefix, host_prefix, total, largest, max_tuples = self._count(L, R, n_sessions, max_tuples)
+        nb = self.ws_bytes("rules_topk", n_items, max_tuples, largest, int(k))
+        if nb == 0:
+            raise ValueError(f"rules top-k: k={k} (1..{self.N.NEIGHBOUR_MAX_K}), max_tuples={max_tuples} or a row of "
+                             f"{largest} tuples (below 2^31) is out of range")
+        self.call("rules_topk", l_off, l_col, l_val, n_items, nnz, r_off, r_col, r_val, n_sessions, eprefix, host_prefix,
+                  max_tuples, largest, int(k), int(num_sessions), int(min_pair_count), self._ws(nb) if total else None, nb,
+                  ids, *planes, count, item_rel)
+        return (ids, *planes, count, item_rel)
 
     def pair_scores(self, pair_user, pair_item, h_off, h_item, n_users: int, S, n_s_rows: int):
         """(score float64 [n_pairs], present uint8 [n_pairs]); S = a CSR whose rows are sorted by column"""
@@ -147,11 +183,18 @@ class NeighbourRec(DeviceRecommender):
                                                    "similarity": vals.cpu().numpy()[keep]})
         return self._similarity_frame
 
+    def _table(self):
+        """(ids, the value plane that `similarity_metric` names, count): what predict reads.  A model with one plane
+        holds exactly this; one with several (AssociationRulesItemRec) picks here."""
+        return self._fitted()
+
     def _csr(self, n_rows: int):
-        """the table as CSR with n_rows >= n_items rows: (offsets, columns, values) in rank order, and sorted by column"""
+        """the table as CSR with n_rows >= n_items rows: (offsets, columns, values) in rank order, and sorted by column;
+        the values are those of the current `similarity_metric`, and the cached copy follows a change of it"""
         cache = self.__dict__.setdefault("_csr_cache", {})
-        if n_rows not in cache:
-            ids, vals, count = self._fitted()
+        key = (n_rows, self._similarity_metric)
+        if key not in cache:
+            ids, vals, count = self._table()
             off = torch.zeros(n_rows + 1, dtype=torch.int64, device=ids.device)
             off[1:ids.shape[0] + 1] = torch.cumsum(count.to(torch.int64), 0)
             off[ids.shape[0] + 1:] = off[ids.shape[0]]
@@ -160,8 +203,8 @@ class NeighbourRec(DeviceRecommender):
             row = torch.arange(ids.shape[0], device=ids.device, dtype=torch.int64)[:, None].expand_as(ids)[keep]
             by_col = torch.argsort(row * max(1, ids.shape[0]) + col.to(torch.int64))
             cache.clear()
-            cache[n_rows] = ((off, col, val), (off, col[by_col].contiguous(), val[by_col].contiguous()))
-        return cache[n_rows]
+            cache[key] = ((off, col, val), (off, col[by_col].contiguous(), val[by_col].contiguous()))
+        return cache[key]
 
     # -------------------------------------------------------------------------------- predict on the device
     def _history(self, lg):
