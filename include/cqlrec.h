@@ -932,6 +932,59 @@ int cqlrec_rules_topk(const int64_t* l_off, const int32_t* l_col, const double* 
                       cqlrec_stream stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * f11  Dense fp64 linear algebra and ADMM SLIM on the device (ADMMSLIM of replay/models/admm_slim.py; DESIGN.md section
+ * 3.14 is the normative text).  Every matrix is row-major fp64.  The rules of f5 - f10 carry over: integer atomics only,
+ * no floating-point atomics, the same input gives the same bytes, arguments are validated on the host before any HIP
+ * call.  Element-wise expressions are evaluated as written (no contraction).
+ * --------------------------------------------------------------------------------------------------------- */
+#define CQLREC_DENSE_GRAM_PIECE 1024 /* entries of an item row that one workgroup of cqlrec_dense_gram sums */
+#define CQLREC_DENSE_BLOCK 64        /* the edge of a diagonal block that is factorised and inverted on chip */
+
+/* D = alpha op(A) op(B) + beta E on v_mfma_f64_16x16x4_f64; op(A) is m x k, op(B) is k x n, D and E are m x n; trans_x =
+ * 0: the matrix as stored, 1: its transpose (A is then stored k x m, B n x k).  Any m, n, k >= 1; edge tiles are
+ * predicated.  The sum over k of an element runs k ascending whatever the grid (no split over k); the element is
+ * alpha * sum, plus beta * E when beta != 0 (E is not read when beta == 0 and may be NULL).  D may be E; D must not
+ * overlap A or B.  No scratch. */
+int cqlrec_dense_gemm_f64(const double* A, int64_t lda, int32_t trans_a, const double* B, int64_t ldb, int32_t trans_b,
+                          const double* E, int64_t lde, double alpha, double beta, int64_t m, int64_t n, int64_t k, double* D,
+                          int64_t ldd, cqlrec_stream stream);
+
+/* G [n_items][n_items] = X^T X, X the users x items matrix of a log whose duplicated (user, item) rows are summed in row
+ * order.  The two views of the log as cqlrec_features_segments orders them: items -> (user, value) by (item, user, row)
+ * and users -> (item, value) by (user, item, row).  G_ij is summed users ascending; an item row of more than
+ * CQLREC_DENSE_GRAM_PIECE entries is cut into pieces of that many entries which are summed apart and combined in piece
+ * order.  n_pieces: the sum of ceil(len / CQLREC_DENSE_GRAM_PIECE) over the item rows longer than a piece, which the
+ * caller knows from the offsets; a long row beyond the announced pieces comes out as NaN. */
+int64_t cqlrec_dense_gram_ws_bytes(int64_t n_items, int64_t n_pieces);
+int cqlrec_dense_gram(const int64_t* i_off, const int32_t* i_user, const double* i_val, const int64_t* u_off,
+                      const int32_t* u_item, const double* u_val, int64_t n_items, int64_t n_users, int64_t n_pieces, void* ws,
+                      int64_t ws_bytes, double* G, cqlrec_stream stream);
+
+/* X [n][n] = (A + shift I)^-1 for a symmetric positive definite A + shift I, of which the lower triangle is read: a
+ * blocked Cholesky factorisation whose diagonal blocks (CQLREC_DENSE_BLOCK) are factorised and inverted by one workgroup
+ * on chip; panels, trailing updates and L^-T L^-1 go through the GEMM above.  *status (device int32): 0, or 1 + the index
+ * of the first pivot that was not positive -- X is then finite garbage; nothing faults or loops.  X must not overlap A. */
+int64_t cqlrec_dense_spd_inverse_ws_bytes(int64_t n);
+int cqlrec_dense_spd_inverse(const double* A, int64_t lda, int64_t n, double shift, void* ws, int64_t ws_bytes, double* X,
+                             int32_t* status, cqlrec_stream stream);
+
+/* One ADMM iteration on W, P, C, Gamma [n][n] (C and Gamma are updated in place), with c = lambda_1 / rho:
+ *   T = P + W (rho C - Gamma);  v_j = T_jj / W_jj;  B_ij = T_ij - W_ij v_j;  S = B + Gamma / rho;
+ *   C' = max(S - c, 0) - max(-S - c, 0);  Gamma' = Gamma + rho (B - C')
+ * sums [5] (device) = the sums of squares of B - C', C' - C, B, C', Gamma', per tile, then over the tiles in an order
+ * fixed by the tile index.  B is never stored; the workspace holds rho C - Gamma, v and the tile sums.  rho > 0,
+ * lambda_1 >= 0. */
+int64_t cqlrec_admm_iteration_ws_bytes(int64_t n);
+int cqlrec_admm_iteration(const double* W, const double* P, double* C, double* Gamma, int64_t n, double rho, double lambda_1,
+                          void* ws, int64_t ws_bytes, double* sums, cqlrec_stream stream);
+
+/* The non-zeros of C [n][n] as CSR, columns ascending.  Two calls: with col == val == NULL it counts and writes offsets
+ * [n_rows + 1] (int64; the rows n .. n_rows - 1 are empty); the caller reads offsets[n], allocates col (int32) and val
+ * (fp64) and calls again with them to have them written.  -0.0 is a zero. */
+int cqlrec_admm_compact(const double* C, int64_t n, int64_t n_rows, int64_t* offsets, int32_t* col, double* val,
+                        cqlrec_stream stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * Measurement hooks (bench.py): when enabled, every launcher brackets its kernel with a pair of HIP events on
  * the stream it launches on; cqlrec_prof_read synchronises those events and returns, per phase, the summed
  * kernel time in ms and the number of launches, then resets the pool.  Not capturable in a hipGraph; off by

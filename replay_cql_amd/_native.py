@@ -88,6 +88,8 @@ NEIGHBOUR_WEIGHTINGS = {None: 0, "tf_idf": 1, "bm25": 2}
 ALS_PIECE, ALS_GRAM_BLOCK, ALS_MAX_RANK, ALS_MAX_K = 1024, 4096, 128, 512
 ALS_EXPLICIT, ALS_IMPLICIT = 0, 1
 
+DENSE_GRAM_PIECE, DENSE_BLOCK = 1024, 64
+
 # name -> (restype, argtypes); every symbol include/cqlrec.h declares
 SIGNATURES = {
     "cqlrec_abi_version": (i32, []),
@@ -215,6 +217,14 @@ SIGNATURES = {
     "cqlrec_als_half_step": (i32, [vp, vp, vp, i64, vp, i64, i32, vp, i32, f64, f64, vp, i64, i64, vp, i64, vp, vp, vp, vp]),
     "cqlrec_als_topk": (i32, [vp, i64, vp, vp, i64, vp, vp, i64, i32, vp, vp, vp, i32, vp, vp, vp, vp]),
     "cqlrec_als_pair_scores": (i32, [vp, vp, i64, vp, vp, i64, vp, vp, i64, i32, vp, vp, vp]),
+    "cqlrec_dense_gemm_f64": (i32, [vp, i64, i32, vp, i64, i32, vp, i64, f64, f64, i64, i64, i64, vp, i64, vp]),
+    "cqlrec_dense_gram_ws_bytes": (i64, [i64, i64]),
+    "cqlrec_dense_gram": (i32, [vp, vp, vp, vp, vp, vp, i64, i64, i64, vp, i64, vp, vp]),
+    "cqlrec_dense_spd_inverse_ws_bytes": (i64, [i64]),
+    "cqlrec_dense_spd_inverse": (i32, [vp, i64, i64, f64, vp, i64, vp, vp, vp]),
+    "cqlrec_admm_iteration_ws_bytes": (i64, [i64]),
+    "cqlrec_admm_iteration": (i32, [vp, vp, vp, vp, i64, f64, f64, vp, i64, vp, vp]),
+    "cqlrec_admm_compact": (i32, [vp, i64, i64, vp, vp, vp, vp]),
     "cqlrec_prof_enable": (i32, [i32]),
     "cqlrec_prof_select": (i32, [C.c_uint32]),
     "cqlrec_debug_marks_enable": (i32, [i32]),

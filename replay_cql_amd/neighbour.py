@@ -183,6 +183,10 @@ class NeighbourRec(DeviceRecommender):
                                                    "similarity": vals.cpu().numpy()[keep]})
         return self._similarity_frame
 
+    def _n_rows(self) -> int:
+        """the number of rows of the fitted table: one per item id below the largest fitted one + 1"""
+        return int(self._fitted()[0].shape[0])
+
     def _table(self):
         """(ids, the value plane that `similarity_metric` names, count): what predict reads.  A model with one plane
         holds exactly this; one with several (AssociationRulesItemRec) picks here."""
@@ -216,11 +220,11 @@ class NeighbourRec(DeviceRecommender):
 
     def _recommend(self, log, k: int, users, items, filter_seen_items: bool):
         """(users int64 [m], ids int32 [m, k], vals float64 [m, k], count int32 [m]) on the device"""
-        sim_ids = self._fitted()[0]
+        n_cols = self._n_rows()
         if log is None:
             raise ValueError("log is not provided, but it is required for prediction")
         lg = open_log(normalise(log), str(self))
-        dev, n_cols = lg.device, int(sim_ids.shape[0])
+        dev = lg.device
         users, items = self._id_tensor(users, dev), self._id_tensor(items, dev)
         if lg.n == 0:
             users = users if users is not None else torch.empty(0, dtype=torch.int64, device=dev)
@@ -249,7 +253,7 @@ class NeighbourRec(DeviceRecommender):
         return users, ids, vals, count
 
     def _predict_pairs(self, pairs: pd.DataFrame, log=None, user_features=None, item_features=None) -> pd.DataFrame:
-        sim_ids = self._fitted()[0]
+        n_rows = self._n_rows()
         if log is None:
             raise ValueError("log is not provided, but it is required for prediction")
         lg = open_log(normalise(log), str(self))
@@ -259,7 +263,6 @@ class NeighbourRec(DeviceRecommender):
         eng, off, h_item, n_users, _ = self._history(lg)
         pu = torch.as_tensor(pairs["user_idx"].to_numpy().astype(np.int32), device=lg.device)
         pi = torch.as_tensor(pairs["item_idx"].to_numpy().astype(np.int32), device=lg.device)
-        n_rows = int(sim_ids.shape[0])
         score, present = eng.pair_scores(pu, pi, off, h_item, n_users, self._csr(n_rows)[1], n_rows)
         keep = present.bool().cpu().numpy()
         return pd.DataFrame({"user_idx": pairs["user_idx"].to_numpy()[keep].astype(np.int32),
