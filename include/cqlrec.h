@@ -333,6 +333,12 @@ int cqlrec_train_step_update(const cqlrec_train_ctx* ctx /* [host] */, uint64_t 
  *   backward_items  g_E_out, g_b_out                (elements [off_E_out, off_W1) of ctx->grads are final afterwards)
  *   backward_rest   dH, encoder gradients, g_E_in   (the remaining elements are final afterwards)
  *   update_range    Adam/Polyak/shadows/zero-grads over elements [lo, hi) (multiples of 4) */
+/* What is still in flight when cqlrec_train_step_forward (or _forward_after / _forward_early_items) has returned AND
+ * `stream` has drained: the sorts of the (item, state) and (action, transition) pairs that the backward needs run on a
+ * library stream that only the backward joins.  They read ctx->offsets / ctx->items and write ctx->ws until a
+ * cqlrec_train_step_backward_* call of that step has been issued and has completed, or until a device-wide
+ * synchronize.  A caller that runs forwards only (a validation loop) must synchronize the DEVICE, not `stream`, before it
+ * frees or rewrites the log or the workspace. */
 int cqlrec_train_step_forward(const cqlrec_train_ctx* ctx /* [host] */, uint64_t step, float* loss_out,
                               cqlrec_stream stream);
 /* The same with a dependency the caller still has in flight on ANOTHER stream: `items_ready` (a hipEvent_t, or NULL)
@@ -347,7 +353,25 @@ int cqlrec_train_step_forward_after(const cqlrec_train_ctx* ctx /* [host] */, ui
  * the arg-max pass, the TD target and the loss (what cqlrec_train_steps does for a single rank).  The
  * cqlrec_train_step_backward_items call of the same step, which must then be made on `items_stream`, adds only the
  * parts that need the loss (one-hot rows, then the cut pieces: the order in which a gradient row is summed does not
- * change).  items_ready may be NULL. */
+ * change).  items_ready may be NULL.
+ *
+ * The record of an early launch.  A successful call with items_stream != NULL, != stream and the library's concurrency
+ * on leaves a record (ctx->ws, ctx->grads, step, items_stream) with the current device; with items_stream NULL or equal
+ * to `stream`, or with cqlrec_set_concurrency(0), the call IS cqlrec_train_step_forward_after and leaves none.  The host
+ * address of the ctx struct is no part of it: a copy of the struct with the same ws / grads is the same context, another
+ * context never sees the record.  cqlrec_train_step_backward_items(ctx, step, s) then
+ *   - finds the record of (ws, grads, step) and s == items_stream: adds the one-hot rows and the cut pieces, and the
+ *     record is gone;
+ *   - finds it and s != items_stream: returns CQLREC_ERR_INVALID (the message names the item-side stream), launches
+ *     nothing and keeps the record, so the call can be repeated on the right stream;
+ *   - finds none: runs all of backward_items on s, the long kernel included.  That is the plain path and it is also
+ *     correct behind an early launch whose record is gone, because the long kernel stores every row of g_E_out / g_b_out
+ *     before anything is added to them.
+ * A record is dropped, without being used, by every call that overwrites the step vectors of the same workspace and step
+ * parity: cqlrec_train_step_forward, _forward_after, _fwd_bwd, cqlrec_train_steps and a newer _forward_early_items.
+ * The library keeps four records per device (two contexts at both parities); a fifth pushes the oldest out, whose step
+ * then takes the plain path.  An abandoned early launch (its backward_items never comes) still WRITES ctx->grads on
+ * items_stream: order it in front of whatever zeroes or fills ctx->grads next. */
 int cqlrec_train_step_forward_early_items(const cqlrec_train_ctx* ctx /* [host] */, uint64_t step, float* loss_out,
                                           cqlrec_stream stream, void* items_ready /* hipEvent_t */,
                                           cqlrec_stream items_stream);

@@ -580,36 +580,78 @@ int backward_rest_impl(const cqlrec_train_ctx* c, uint64_t step, cqlrec_stream s
   CQL_TRY(backward_states_impl(c, step, stream));
   return backward_chain_impl(c, step, stream);
 }
+
+// ---- early launches of the long item-side kernel (cqlrec_train_step_forward_early_items) that still wait for their
+// backward_items call.  A record is identified by what identifies the step's data -- workspace, gradient buffer, step and
+// the stream the kernel went to -- never by the host address of the ctx struct (callers copy that struct).  Per device slot
+// a small table: two contexts at both parities.  A record that is missing (dropped, or pushed out by a fifth one) only costs
+// the fast path: backward_items then runs all three parts, and the long kernel stores every row (accumulate = 0) before the
+// one-hot part, so whatever an earlier launch of it left is overwritten.
+struct EarlyItems {
+  bool live = false;
+  const void* ws = nullptr;
+  const float* grads = nullptr;
+  uint64_t step = 0;
+  hipStream_t items_stream = nullptr;
+  CqlAdamFix fix = {};
+};
+constexpr int EARLY_SLOTS = 4;
+EarlyItems g_early[CQL_MAX_DEVICES][EARLY_SLOTS];
+int g_early_next[CQL_MAX_DEVICES] = {};
+
+// a new forward of this workspace at this parity overwrites the step vectors the recorded launch belongs to
+void early_drop(const cqlrec_train_ctx* c, uint64_t step) {
+  for (EarlyItems& e : g_early[cql_device_slot()])
+    if (e.live && e.ws == c->ws && ((e.step ^ step) & 1) == 0) e.live = false;
+}
+EarlyItems* early_find(const cqlrec_train_ctx* c, uint64_t step) {
+  for (EarlyItems& e : g_early[cql_device_slot()])
+    if (e.live && e.ws == c->ws && e.grads == c->grads && e.step == step) return &e;
+  return nullptr;
+}
+EarlyItems& early_take_slot() {
+  const int dev = cql_device_slot();
+  for (EarlyItems& e : g_early[dev])
+    if (!e.live) return e;
+  EarlyItems& e = g_early[dev][g_early_next[dev]];      // full: the oldest goes (its step falls back to the full form)
+  g_early_next[dev] = (g_early_next[dev] + 1) % EARLY_SLOTS;
+  return e;
+}
 }  // namespace
 
 // phase 1: sample + forward + loss (+ the sort for the gather backward, forked onto the side stream)
 extern "C" int cqlrec_train_step_forward(const cqlrec_train_ctx* c, uint64_t step, float* loss_out,
                                          cqlrec_stream stream) {
   CQL_TRY(check_ctx(c));
+  early_drop(c, step);
   return forward_impl(c, step, loss_out, stream, nullptr);
 }
 
 extern "C" int cqlrec_train_step_forward_after(const cqlrec_train_ctx* c, uint64_t step, float* loss_out,
                                                cqlrec_stream stream, void* items_ready) {
   CQL_TRY(check_ctx(c));
+  early_drop(c, step);
   return forward_impl(c, step, loss_out, stream, (hipEvent_t)items_ready);
 }
 
-// phase 1 + the long kernel of phase 2 (see the header).  The cut pieces of that kernel wait, by step parity, for the
+// phase 1 + the long kernel of phase 2 (see the header).  The cut pieces of that kernel wait, in the record above, for the
 // backward_items call of the same step.
-static CqlAdamFix g_early_fix[2];
-static bool g_early_long[2] = {false, false};
 extern "C" int cqlrec_train_step_forward_early_items(const cqlrec_train_ctx* c, uint64_t step, float* loss_out,
                                                      cqlrec_stream stream, void* items_ready, cqlrec_stream items_stream) {
   CQL_TRY(check_ctx(c));
   SideStream& ss = side_stream();
   const bool early = items_stream && items_stream != stream && need_side_streams(ss) && ss.ok;
-  g_early_long[step & 1] = false;
+  early_drop(c, step);
   if (!early) return forward_impl(c, step, loss_out, stream, (hipEvent_t)items_ready);
-  g_early_fix[step & 1] = CqlAdamFix{};
-  CQL_TRY(forward_impl(c, step, loss_out, stream, (hipEvent_t)items_ready, nullptr, (hipStream_t)items_stream,
-                       &g_early_fix[step & 1]));
-  g_early_long[step & 1] = true;
+  CqlAdamFix fix = {};
+  CQL_TRY(forward_impl(c, step, loss_out, stream, (hipEvent_t)items_ready, nullptr, (hipStream_t)items_stream, &fix));
+  EarlyItems& e = early_take_slot();
+  e.live = true;
+  e.ws = c->ws;
+  e.grads = c->grads;
+  e.step = step;
+  e.items_stream = (hipStream_t)items_stream;
+  e.fix = fix;
   return CQLREC_OK;
 }
 
@@ -617,11 +659,16 @@ extern "C" int cqlrec_train_step_forward_early_items(const cqlrec_train_ctx* c, 
 // their all-reduce while phase 3 runs)
 extern "C" int cqlrec_train_step_backward_items(const cqlrec_train_ctx* c, uint64_t step, cqlrec_stream stream) {
   CQL_TRY(check_ctx(c));
-  if (g_early_long[step & 1]) {      // the long kernel is running (or done) on this stream: one-hot rows, then the cut pieces
-    g_early_long[step & 1] = false;
+  if (EarlyItems* e = early_find(c, step)) {
+    // the long kernel is running (or done) on e->items_stream; on any other stream the parts below would race with it
+    CQL_REQUIRE((hipStream_t)stream == e->items_stream,
+                "train_step_backward_items: step %llu was started by forward_early_items; call it on that call's "
+                "item-side stream (items_stream)", (unsigned long long)step);
+    const CqlAdamFix fix = e->fix;
+    e->live = false;
     const cqlrec_layout& L = c->layout;
-    CQL_TRY(backward_items_onehot_impl(c, step, stream));
-    return cql_qde_fixup_deferred(g_early_fix[step & 1], c->grads + L.off_E_out, c->grads + L.off_b_out, (hipStream_t)stream);
+    CQL_TRY(backward_items_onehot_impl(c, step, stream));      // one-hot rows, then the cut pieces
+    return cql_qde_fixup_deferred(fix, c->grads + L.off_E_out, c->grads + L.off_b_out, (hipStream_t)stream);
   }
   return backward_items_impl(c, step, stream);
 }
@@ -694,6 +741,7 @@ extern "C" int cqlrec_train_steps(const cqlrec_train_ctx* c, uint64_t step0, int
   hipEvent_t pending = nullptr;   // item-side Adam of the previous step
   hipEvent_t sampled = nullptr;   // transitions + sorted pairs of this step, prepared during the previous backward
   need_side_streams(side_stream(), true);
+  for (int32_t i = 0; i < n_steps && i < 2; ++i) early_drop(c, step0 + (uint64_t)i);      // (the parities this call overwrites)
   const bool use_map = n_steps > 1 && L.off_E_in == 0;
   CqlAdamSteps adam_tab = {};     // (step_size, sqrt_bc2) of the steps of this call, slot = step % CQL_ADAM_DEFER_CAP
   if (use_map) {                  // every E_in row is up to date when a call starts

@@ -279,6 +279,86 @@ def softmax_grad_rows(hb, lse, E_b, b_out, scale, g_E_out=None, g_b_out=None, dH
     return report
 
 
+def qde_geometry(B, N, d, n_cu=256):
+    """(form, G, T, W, grid, cut) of the long item-side backward kernel for a batch of B states, N items, width d -- the
+    arithmetic of de_form2 / de_waves / de_grid / cql_qde_launch (csrc/qhead_de.hip) and cql_qde3_supported
+    (csrc/qhead_de3.hip), restated (tests/test_step_phase_geometry_cpu.py holds it to hand-worked rows).
+      form   qde2 (d = 128, B % 64 = 0), qde3 (d = 256, B % 32 = 0), else the generic qde_kernel<d>
+      G      item groups: 256 items (8 waves x 32), 128 for d = 256 (4 waves)
+      T      stages: 64 states, 32 for d = 256;  W = G T stage-units
+      grid   min(W, n_cu): one persistent block per CU; block p works on stage-units [p W / grid, (p + 1) W / grid)
+      cut    some block starts inside a group (p W / grid is no multiple of T for a p in [1, grid)): the piece of a group
+             that does not hold stage 0 goes to a slab, and a fix-up (a launch, or the item-side Adam through CqlAdamFix)
+             adds the slabs to the gradient rows.
+    n_cu: the device's CU count as the library reads it (anything outside 1..256 counts as 256)."""
+    assert d in (64, 128, 256) and B > 0 and N > 0
+    if n_cu <= 0 or n_cu > 256:
+        n_cu = 256
+    if d == 128 and B % 64 == 0:
+        form = "qde2"
+    elif d == 256 and B % 32 == 0:
+        form = "qde3"
+    else:
+        form = f"qde_kernel<{d}>"
+    items = 32 * (4 if d == 256 else 8)
+    ti = 32 if d == 256 else 64
+    G, T = (N + items - 1) // items, (B + ti - 1) // ti
+    W = G * T
+    grid = min(W, n_cu)
+    cut = any((p * W // grid) % T != 0 for p in range(1, grid))
+    return form, G, T, W, grid, cut
+
+
+def check_step_against_oracle(core, lay, theta, target, csr, seed, step, B, L, loss=None, gamma=0.99, alpha=1.0, tag="step"):
+    """The intermediates and gradients that `core` holds after the forward + backward of `step` (before its update)
+    against the float64 oracle run from the parameters (theta, target: flat fp32 numpy, layout `lay`) the step started
+    from, on the log csr = (offsets, items, rewards): the sampled transitions exactly, the forward values within P3,
+    every gradient segment normwise, the padding untouched, and the softmax part of the Q-head gradients row by row from
+    the step's own states, lse, coef and actions (the one-hot term dominates the norms).  loss: the step's device loss."""
+    off, items, rew = csr
+    Nn = lay.n_items
+    v = core.views(step)
+    pos = O.sample_positions(seed, step, 0, B, int(off[-1]))
+    users, tpos = O.positions_to_transitions(pos, off)
+    out = O.loss_and_grads(lay, theta, target, off, items, rew, users, tpos, L, gamma, alpha)
+    assert np.array_equal(v["users"].cpu().numpy(), users) and np.array_equal(v["tpos"].cpu().numpy(), tpos)
+    np.testing.assert_allclose(v["h0_s"].cpu().numpy(), out.h0_s, rtol=1e-5, atol=1e-6)
+    # bf16 state vectors: identical up to one bf16 ulp on rare rounding ties of an fp32 sum
+    for name, ref in (("hb_s", out.hb_s), ("hb_sn", out.hb_sn)):
+        got = bf16_to_np(v[name])
+        print(f"STEPCHECK {tag} B={B} N={Nn} d={lay.d} {name}: {int(np.sum(got != ref))} of {got.size} bf16 values differ")
+        assert np.mean(got != ref) < 2e-3
+        np.testing.assert_allclose(got, ref, rtol=1e-2, atol=1e-3)
+    np.testing.assert_allclose(v["q_a"].cpu().numpy(), out.q_a, atol=1e-3)          # P3 |dQ| <= 1e-3
+    np.testing.assert_allclose(v["lse"].cpu().numpy(), out.lse, atol=1e-3)
+    np.testing.assert_allclose(v["q_targ"].cpu().numpy(), out.q_targ, atol=1e-3)
+    np.testing.assert_allclose(v["y"].cpu().numpy(), out.y, atol=1e-3)
+    bad = O.argmax_margin_violations(v["a_star"].cpu().numpy(), out.a_star, out.qn_max, out.hb_sn,
+                                     lay.view(O.shadow(theta), "E_out"), lay.view(theta, "b_out"),
+                                     hb_got=bf16_to_np(v["hb_sn"]))
+    assert bad.size == 0, bad                                                    # per row, P3 margin rule
+    if loss is not None:
+        assert abs(loss.item() - out.loss) < 1e-3 * abs(out.loss)
+    assert rel_err(v["dH"].cpu().numpy(), out.dH) < 5e-3
+    assert rel_err(v["dh0"].cpu().numpy(), out.dh0) < 5e-3
+    g = core.grads.cpu().numpy()
+    for nm in ("E_in", "E_out", "b_out", "W1", "b1", "W2", "b2"):
+        assert rel_err(lay.view(g, nm), lay.view(out.grads, nm)) < 5e-3, nm
+    # padding and the PAD row never receive gradient
+    mask = np.ones(lay.total, bool)
+    for nm in ("E_in", "E_out", "b_out", "W1", "b1", "W2", "b2"):
+        mask[lay.off[nm]: lay.off[nm] + int(np.prod(lay.shape(nm)))] = False
+    assert np.all(g[mask] == 0) and np.all(lay.view(g, "E_in")[Nn] == 0)
+    # the softmax part of the Q-head gradients row by row, from the step's own states, lse, coef and actions (the
+    # one-hot term dominates the norms above)
+    rep = softmax_grad_rows(bf16_to_np(v["hb_s"]), v["lse"].cpu().numpy(), lay.view(O.shadow(theta), "E_out"),
+                            lay.view(theta, "b_out"), np.float32(alpha / B), g_E_out=lay.view(g, "E_out"),
+                            g_b_out=lay.view(g, "b_out"), dH=v["dH"].cpu().numpy(), coef=v["coef"].cpu().numpy(),
+                            act=v["act"].cpu().numpy())
+    print(f"ROWCHECK {tag} B={B} N={Nn} d={lay.d} " + " ".join(f"{k}={x:.3f}" for k, x in rep.items()))
+    return rep
+
+
 def topk_rule_violations(idx, val, cnt, Q, k, set_tol=1e-4, val_tol=1e-3):
     """P3 for a block of top-k lists against the reference score matrix Q (rows = the same users, inadmissible items at
     -inf), PER ROW: the count of admissible items, descending order, every reported score within val_tol of the

@@ -61,17 +61,17 @@ def _report(tag, rep):
 
 
 # ---- item side (and the state side of the backward) ---------------------------------------------------------------
-# n_cu = 256.  Item-side form (qhead_de.hip: de_form2, cql_qde3_supported, de_grid; W = G * T stage-units, grid =
+# n_cu = 256; the rows are helpers.qde_geometry's (test_step_phase_geometry_cpu.py).  Item-side form (qhead_de.hip: de_form2, cql_qde3_supported, de_grid; W = G * T stage-units, grid =
 # min(W, 256), a range starts inside a group ("cut", slab + fix-up) when some p * W / grid is not a multiple of T):
 #   B     N      d    form                               G x T = W        grid  cut
 #   64    5003   128  qde2 (B % 64 = 0)                  20 x 1 = 20      20    no (T = 1)
 #   1024  20011  128  qde2                               79 x 16 = 1264   256   yes (stream-K)
 #   1000  20011  128  qde_kernel<128> (B % 64 != 0)      79 x 16 = 1264   256   yes
-#   100   1000   128  qde_kernel<128>                    4 x 2 = 8        8     no
+#   100   1000   128  qde_kernel<128>                    4 x 2 = 8        8     yes (grid = W and T > 1)
 #   512   5003   256  qde3 (B % 32 = 0)                  40 x 16 = 640    256   yes
 #   500   5003   256  qde_kernel<256> (B % 32 != 0)      40 x 16 = 640    256   yes
 #   1024  20011  64   qde_kernel<64> (8 waves)           79 x 16 = 1264   256   yes
-#   128   100    128  qde2, N < 128                      1 x 2 = 2        2     no
+#   128   100    128  qde2, N < 128                      1 x 2 = 2        2     yes (block 1 starts at stage 1)
 #   1     3001   128  qde_kernel<128>, B = 1             12 x 1 = 12      12    no
 #   1     777    256  qde_kernel<256>, B = 1             7 x 1 = 7        7     no
 # (groups: 256 items for qde2 and the 8-wave qde_kernel, 128 for d = 256; stages: 64 states, 32 for d = 256.)  Every N

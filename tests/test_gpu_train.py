@@ -6,7 +6,7 @@ import torch
 from oracle import cql_oracle as O
 from replay_cql_amd.core import CQLCore, CQLHyper
 
-from helpers import DEV, bf16_to_np, rel_err, small_log, softmax_grad_rows
+from helpers import DEV, bf16_to_np, check_step_against_oracle, rel_err, small_log
 
 pytestmark = pytest.mark.gpu
 
@@ -36,43 +36,8 @@ def test_step_intermediates_and_grads(U, Nn, d, B, L):
         assert core.layout.offset(nm) == lay.off[nm]
     loss = torch.zeros(1, device=DEV)
     core.forward_backward(loss)
-    v = core.views()
-    pos = O.sample_positions(11, 0, 0, B, int(off[-1]))
-    users, tpos = O.positions_to_transitions(pos, off)
-    out = O.loss_and_grads(lay, m.theta, m.target, off, items, rew, users, tpos, L, 0.99, 1.0)
-    assert np.array_equal(v["users"].cpu().numpy(), users) and np.array_equal(v["tpos"].cpu().numpy(), tpos)
-    np.testing.assert_allclose(v["h0_s"].cpu().numpy(), out.h0_s, rtol=1e-5, atol=1e-6)
-    # bf16 state vectors: identical up to one bf16 ulp on rare rounding ties of an fp32 sum
-    for name, ref in (("hb_s", out.hb_s), ("hb_sn", out.hb_sn)):
-        got = bf16_to_np(v[name])
-        assert np.mean(got != ref) < 2e-3
-        np.testing.assert_allclose(got, ref, rtol=1e-2, atol=1e-3)
-    np.testing.assert_allclose(v["q_a"].cpu().numpy(), out.q_a, atol=1e-3)          # P3 |dQ| <= 1e-3
-    np.testing.assert_allclose(v["lse"].cpu().numpy(), out.lse, atol=1e-3)
-    np.testing.assert_allclose(v["q_targ"].cpu().numpy(), out.q_targ, atol=1e-3)
-    np.testing.assert_allclose(v["y"].cpu().numpy(), out.y, atol=1e-3)
-    bad = O.argmax_margin_violations(v["a_star"].cpu().numpy(), out.a_star, out.qn_max, out.hb_sn,
-                                     lay.view(O.shadow(m.theta), "E_out"), lay.view(m.theta, "b_out"),
-                                     hb_got=bf16_to_np(v["hb_sn"]))
-    assert bad.size == 0, bad                                                    # per row, P3 margin rule
-    assert abs(loss.item() - out.loss) < 1e-3 * abs(out.loss)
-    assert rel_err(v["dH"].cpu().numpy(), out.dH) < 5e-3
-    assert rel_err(v["dh0"].cpu().numpy(), out.dh0) < 5e-3
-    g = core.grads.cpu().numpy()
-    for nm in ("E_in", "E_out", "b_out", "W1", "b1", "W2", "b2"):
-        assert rel_err(lay.view(g, nm), lay.view(out.grads, nm)) < 5e-3, nm
-    # padding and the PAD row never receive gradient
-    mask = np.ones(lay.total, bool)
-    for nm in ("E_in", "E_out", "b_out", "W1", "b1", "W2", "b2"):
-        mask[lay.off[nm]: lay.off[nm] + int(np.prod(lay.shape(nm)))] = False
-    assert np.all(g[mask] == 0) and np.all(lay.view(g, "E_in")[Nn] == 0)
-    # the softmax part of the Q-head gradients row by row, from the step's own states, lse, coef and actions (the
-    # one-hot term dominates the norms above)
-    rep = softmax_grad_rows(bf16_to_np(v["hb_s"]), v["lse"].cpu().numpy(), lay.view(O.shadow(m.theta), "E_out"),
-                            lay.view(m.theta, "b_out"), np.float32(1.0 / B), g_E_out=lay.view(g, "E_out"),
-                            g_b_out=lay.view(g, "b_out"), dH=v["dH"].cpu().numpy(), coef=v["coef"].cpu().numpy(),
-                            act=v["act"].cpu().numpy())
-    print(f"ROWCHECK step B={B} N={Nn} d={d} " + " ".join(f"{k}={x:.3f}" for k, x in rep.items()))
+    # sampled transitions, forward values, every gradient segment, padding, and the softmax gradient rows: one shared block
+    check_step_against_oracle(core, lay, m.theta, m.target, (off, items, rew), 11, 0, B, L, loss=loss)
 
 
 def test_dyadic_forward_bit_exact():
@@ -150,7 +115,7 @@ def test_pipelined_steps_match_step_by_step():
 # equality here carries that guarantee over to the Adam-fused fix-up.  (W = G x T stage-units, grid = min(W, 256).)
 #   U    N      d    B     form             G x T = W       cut
 #   300  5003   256  256   qde3             40 x 8 = 320    yes
-#   300  2000   64   128   qde_kernel<64>   8 x 2 = 16      no
+#   300  2000   64   128   qde_kernel<64>   8 x 2 = 16      yes
 #   300  20011  128  1024  qde2             79 x 16 = 1264  yes (stream-K)
 @pytest.mark.parametrize("U,Nn,d,B,L,steps", [(300, 5003, 256, 256, 8, 5), (300, 2000, 64, 128, 8, 5),
                                                (300, 20011, 128, 1024, 8, 5)])
