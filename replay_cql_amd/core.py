@@ -233,32 +233,12 @@ class CQLCore:
         s, lay = _stream(), self.layout
         lo_a, hi_a, total = int(lay.off_E_out), int(lay.off_W1), int(lay.total)
         main = torch.cuda.current_stream()
-        if self._side is None:
-            with torch.cuda.device(self.device):
-                self._side = N.aux_stream(0)          # library-owned (never a torch.cuda.Stream(): see _native.aux_stream)
-            self._ev = [torch.cuda.Event() for _ in range(3)]       # forward done, state-side backward done, items ready
-        side = self._side
-        ev_fwd, ev_rest, ev_items = self._ev
         pending = False
-        self._early_de = os.environ.get("CQL_EARLY_DE", "1") != "0"
         for i in range(n_steps):
-            lo = None if losses is None else losses[i:i + 1]
-            # the long dE_out kernel of this step is started by the forward itself, on the side stream, as soon as the
-            # fused forward has produced the logsumexp -- under the arg-max pass and the loss; backward_items below adds
-            # the parts that need the loss (CQL_EARLY_DE=0: all of it behind the loss)
-            N.check(self.lib.cqlrec_train_step_forward_early_items(
-                C.byref(c), self.step, _ptr(lo), s, ev_items.cuda_event if pending else None,
-                side.cuda_stream if self._early_de else None), "train_step_forward_early_items")
-            ev_fwd.record(main)
-            N.check(self.lib.cqlrec_train_step_backward_rest(C.byref(c), self.step, s), "train_step_backward_rest")
-            ev_rest.record(main)
+            side, ev_rest, ev_items = self._phased_front(c, main, None if losses is None else losses[i:i + 1], pending)
             # issue order matters: the collectives of one process group execute in the order they were issued (one
             # internal RCCL stream), so the state-side all-reduce -- whose gradients are ready first -- goes first and
             # runs under the item-side kernel; the item-side all-reduce queues behind it
-            with torch.cuda.stream(side):      # enqueue the long item-side kernel before the (slow to issue) collectives
-                side.wait_event(ev_fwd)
-                N.check(self.lib.cqlrec_train_step_backward_items(C.byref(c), self.step, side.cuda_stream),
-                        "train_step_backward_items")
             work_b = [self._allreduce_async(self.grads[0:lo_a]), self._allreduce_async(self.grads[hi_a:total])]
             with torch.cuda.stream(side):
                 work_a = self._allreduce_async(self.grads[lo_a:hi_a])
@@ -278,6 +258,32 @@ class CQLCore:
             self.step += 1
         if pending:
             main.wait_event(ev_items)
+
+    def _phased_front(self, c: N.TrainCtx, main: torch.cuda.Stream, loss: Optional[torch.Tensor], pending: bool):
+        """The front of one phased step, shared by the replicated and the row-sharded loop: forward and state-side backward
+        on `main`, item-side backward on the side stream.  pending: the item-side Adam of the step before is still running
+        there, ev_items marks its end.  Returns (side stream, ev_rest: state-side backward done, ev_items: for the caller)."""
+        if self._side is None:
+            with torch.cuda.device(self.device):
+                self._side = N.aux_stream(0)          # library-owned (never a torch.cuda.Stream(): see _native.aux_stream)
+            self._ev = [torch.cuda.Event() for _ in range(3)]       # forward done, state-side backward done, items ready
+            self._early_de = os.environ.get("CQL_EARLY_DE", "1") != "0"
+        side, s = self._side, main.cuda_stream
+        ev_fwd, ev_rest, ev_items = self._ev
+        # the long dE_out kernel of this step is started by the forward itself, on the side stream, as soon as the
+        # fused forward has produced the logsumexp -- under the arg-max pass and the loss; backward_items below adds
+        # the parts that need the loss (CQL_EARLY_DE=0: all of it behind the loss)
+        N.check(self.lib.cqlrec_train_step_forward_early_items(
+            C.byref(c), self.step, _ptr(loss), s, ev_items.cuda_event if pending else None,
+            side.cuda_stream if self._early_de else None), "train_step_forward_early_items")
+        ev_fwd.record(main)
+        N.check(self.lib.cqlrec_train_step_backward_rest(C.byref(c), self.step, s), "train_step_backward_rest")
+        ev_rest.record(main)
+        with torch.cuda.stream(side):      # the long item-side kernel is enqueued first: nothing the caller issues delays it
+            side.wait_event(ev_fwd)
+            N.check(self.lib.cqlrec_train_step_backward_items(C.byref(c), self.step, side.cuda_stream),
+                    "train_step_backward_items")
+        return side, ev_rest, ev_items
 
     # ------------------------------------------------------------------ row-sharded optimizer (opt-in)
     def _shard_plan(self):
@@ -307,10 +313,6 @@ class CQLCore:
         import torch.distributed as dist
         c, s, P = self._train_ctx(), _stream(), self._shard_plan()
         main = torch.cuda.current_stream()
-        if self._side is None:
-            with torch.cuda.device(self.device):
-                self._side = N.aux_stream(0)
-            self._ev = [torch.cuda.Event() for _ in range(3)]
         if self._gshard is None:
             self._gshard = (torch.empty(P["n"], dtype=torch.float32, device=self.device),
                             torch.empty(P["n"], dtype=torch.float32, device=self.device))
@@ -327,8 +329,6 @@ class CQLCore:
         st_in, st_out = self._agstage[:2], self._agstage[2:]
         g_tail_in = self.grads[P["tail_in"][0]: P["tail_in"][1]]
         g_tail_enc = self.grads[P["tail_enc"][0]: P["tail_enc"][1]]
-        side = self._side
-        ev_fwd, ev_rest, ev_items = self._ev
         pg = self.pg
 
         def ar(lo, hi):
@@ -343,20 +343,8 @@ class CQLCore:
                 N.check(self.lib.cqlrec_train_step_update_range(C.byref(c), self.step, lo, hi, stream), "update_range")
 
         pending = False
-        early_de = os.environ.get("CQL_EARLY_DE", "1") != "0"
         for i in range(n_steps):
-            lo_ = None if losses is None else losses[i:i + 1]
-            # (as in train_steps: the long dE_out kernel starts under the arg-max pass and the loss)
-            N.check(self.lib.cqlrec_train_step_forward_early_items(
-                C.byref(c), self.step, _ptr(lo_), s, ev_items.cuda_event if pending else None,
-                side.cuda_stream if early_de else None), "train_step_forward_early_items")
-            ev_fwd.record(main)
-            N.check(self.lib.cqlrec_train_step_backward_rest(C.byref(c), self.step, s), "train_step_backward_rest")
-            ev_rest.record(main)
-            with torch.cuda.stream(side):      # the long item-side kernel is enqueued first: nothing below delays it
-                side.wait_event(ev_fwd)
-                N.check(self.lib.cqlrec_train_step_backward_items(C.byref(c), self.step, side.cuda_stream),
-                        "train_step_backward_items")
+            side, ev_rest, ev_items = self._phased_front(c, main, None if losses is None else losses[i:i + 1], pending)
             # Collectives of one group execute in the order they were issued (one internal RCCL stream).  State side first:
             # its gradients are ready first, and its whole exchange (reduce-scatter, Adam on the own rows, all-gather
             # of the shadows the next prologue reads) then runs under the item-side kernel; the item side queues behind.

@@ -3,6 +3,8 @@
 forward only / forward+backward / full step, with and without intra-step concurrency.
 
     python tools/phase_timing.py [--reps 200]
+    rocprofv3 --kernel-trace --output-format csv -- python tools/phase_timing.py --trace-only [--phased]
+        (then tools/step_timeline.py on the trace; --order prints the launch order per stream)
 """
 import argparse
 import ctypes as C
@@ -26,6 +28,7 @@ def main():
     ap.add_argument("--d", type=int, default=128)
     ap.add_argument("--batch", type=int, default=4096)
     ap.add_argument("--trace-only", action="store_true", help="just run 3 x train_steps(32) (rocprofv3 target)")
+    ap.add_argument("--phased", action="store_true", help="with --trace-only: train_steps(32, phased=True), the data-parallel loop")
     a = ap.parse_args()
     lib = N.load()
     dev = torch.device("cuda:0")
@@ -37,7 +40,7 @@ def main():
     torch.cuda.synchronize()
     if a.trace_only:
         for _ in range(3):
-            core.train_steps(32)
+            core.train_steps(32, phased=a.phased)
         torch.cuda.synchronize()
         return
     c = core._train_ctx()
