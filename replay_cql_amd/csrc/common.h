@@ -54,7 +54,7 @@ struct CqlProfScope {
   ~CqlProfScope() { cql_prof_end(s); }
 };
 
-// deterministic one-hot scatter of the Q-head backward (gbwd.hip): sort of (act[b], b) ahead of time, then a segmented sum
+// misc.hip: cqlrec_encoder_bwd in parts (1: input-side products, 2: weight / bias gradients, 3: both)
 int cql_encoder_bwd_parts(const float* dH, const uint16_t* z_b, const uint16_t* h0_b, const uint16_t* W1_b,
                           const uint16_t* W2_b, int64_t rows, int32_t d, void* ws, int64_t ws_bytes, float* g_W1, float* g_b1,
                           float* g_W2, float* g_b2, float* dh0, int parts, hipStream_t s);
@@ -62,6 +62,7 @@ int cql_encoder_bwd_parts(const float* dH, const uint16_t* z_b, const uint16_t* 
 int cql_td_coef(const float* q_a, const float* lse, const float* q_targ, const float* rew, const float* done, int32_t batch,
                 float gamma, float alpha, float inv_batch, float* coef, float* y, float* term, hipStream_t s);
 int cql_td_loss_sum(const float* term, int32_t batch, float inv_batch, float* loss_out, hipStream_t s);
+// deterministic one-hot scatter of the Q-head backward (gbwd.hip): sort of (act[b], b) ahead of time, then a segmented sum
 int64_t cql_onehot_ws_bytes(int64_t batch, int32_t d);
 int cql_onehot_prepare(const int32_t* act, int64_t batch, int64_t n_items, int32_t d, void* ws, int64_t ws_bytes,
                        hipStream_t s);
@@ -120,37 +121,6 @@ __device__ __forceinline__ float f32_from_order_key(uint32_t k) {
   return __uint_as_float(u);
 }
 
-// Deferred sum of the cut pieces of the item-side backward (qhead_de.hip).  The persistent kernel writes the piece of a
-// cut item group that does not hold stage 0 to a slab; qde_fixup_kernel adds those slabs to the gradient rows.  The
-// single-rank step driver skips that launch: the Adam launch that consumes g_E_out / g_b_out right behind it adds the
-// same slabs, in the same order, while it reads the gradient (cql_adam_ema_fix) -- one launch and one read-modify-write
-// of the cut rows less on the step's critical path.
-struct CqlAdamFix {
-  int valid;                // 0: nothing deferred (the gradient is complete)
-  const float* slab;        // [nblk][items x D]
-  const float* slab_cs;     // [nblk][items]
-  int32_t G, T, nblk, items, D;
-  float scale;
-  int64_t n_items;
-  int64_t rows_off, cs_off; // element offsets of g_E_out / g_b_out inside the updated range
-};
-int cql_adam_ema_fix(float* theta, float* grads, float* m, float* v, float* target, uint16_t* theta_b, uint16_t* target_b,
-                     int64_t n, float step_size, float sqrt_bc2, float beta1, float beta2, float eps, float tau,
-                     int32_t zero_grads, const CqlAdamFix* fix, hipStream_t stream);
-// Adam over the whole embedding rows of E_in inside a cqlrec_train_steps call (misc.hip).  Only the rows
-// marked in `row_map` (one byte per row, n_rows of them) carry a gradient this step: the others take g = 0 and their gradient
-// elements are not read.  `age[r]` counts the steps row r is behind; a row is brought up to date -- the missed steps replayed in order with g = +0.0f, then this step's -- when it has a
-// gradient (`row_map`), when the next step's forward reads it (`read_next`; NULL: every row, the flush), or when its age
-// reaches the table's length.  `tab` holds the (step_size, sqrt_bc2) pairs of the last CQL_ADAM_DEFER_CAP steps, slot =
-// step % CQL_ADAM_DEFER_CAP, formed on the host in double like the dense launch's two scalars.
-#define CQL_ADAM_DEFER_CAP 64
-struct CqlAdamSteps {
-  float step_size[CQL_ADAM_DEFER_CAP], sqrt_bc2[CQL_ADAM_DEFER_CAP];
-};
-int cql_adam_ema_rows_deferred(float* theta, float* grads, float* m, float* v, float* target, uint16_t* theta_b,
-                               uint16_t* target_b, int64_t n, const CqlAdamSteps& tab, uint64_t step, float beta1, float beta2,
-                               float eps, float tau, int32_t zero_grads, const uint8_t* row_map, const uint8_t* read_next,
-                               uint8_t* age, int32_t d, int64_t n_rows, hipStream_t stream);
 // gbwd.hip: read_map[item] = 1 for every E_in row the forward of the sampled transitions gathers (the windows of s and of
 // s': items[base - min(tpos, L) .. base] with base = offsets[user] + tpos), 0 for the others; read_map has n_items bytes
 int cql_mark_read_rows(const int64_t* offsets, const int32_t* items, const int32_t* users, const int32_t* tpos,

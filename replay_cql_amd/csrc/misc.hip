@@ -749,25 +749,10 @@ __global__ __launch_bounds__(256) void adam_ema_kernel(float4* __restrict__ thet
                                                        uint2* __restrict__ target_b, int64_t n4, float step_size,
                                                        float sqrt_bc2, float beta1, float beta2, float eps, float tau,
                                                        int zero_grads) {
-  const float omb1 = 1.0f - beta1, omb2 = 1.0f - beta2, omt = 1.0f - tau;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
-    const float4 g4 = ld4<NT>(grads + i);
-    float4 p4 = ld4<NT>(theta + i), m4 = ld4<NT>(m + i), v4 = ld4<NT>(v + i), t4 = ld4<NT>(target + i);
-    const float g[4] = {g4.x, g4.y, g4.z, g4.w};
-    float p[4] = {p4.x, p4.y, p4.z, p4.w}, mm[4] = {m4.x, m4.y, m4.z, m4.w}, vv[4] = {v4.x, v4.y, v4.z, v4.w},
-          tt[4] = {t4.x, t4.y, t4.z, t4.w};
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      adam_ema_elem(g[k], p[k], mm[k], vv[k], tt[k], step_size, sqrt_bc2, beta1, beta2, eps, tau, omb1, omb2, omt);
-    }
-    st4<NT>(theta + i, p[0], p[1], p[2], p[3]);
-    st4<NT>(m + i, mm[0], mm[1], mm[2], mm[3]);
-    st4<NT>(v + i, vv[0], vv[1], vv[2], vv[3]);
-    st4<NT>(target + i, tt[0], tt[1], tt[2], tt[3]);
-    theta_b[i] = make_uint2(pack_bf16x2(p[0], p[1]), pack_bf16x2(p[2], p[3]));
-    target_b[i] = make_uint2(pack_bf16x2(tt[0], tt[1]), pack_bf16x2(tt[2], tt[3]));
-    if (zero_grads) st4<NT>(grads + i, 0.f, 0.f, 0.f, 0.f);
-  }
+  const AdamK k(beta1, beta2, eps, tau);
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x)
+    adam_ema_body<NT>(theta, grads, m, v, target, theta_b, target_b, i, k, step_size, sqrt_bc2, zero_grads,
+                      [](float (&)[4], int64_t) __attribute__((always_inline)) {});
 }
 
 // The E_in range of the pipelined single-rank driver.  `row_map[r] != 0` says that the window-gather backward of THIS step
@@ -799,7 +784,7 @@ __global__ __launch_bounds__(256) void adam_ema_rows_deferred_kernel(
   if (threadIdx.x < CQL_ADAM_DEFER_CAP)
     tab_s[threadIdx.x] = make_float2(tab.step_size[threadIdx.x], tab.sqrt_bc2[threadIdx.x]);
   __syncthreads();
-  const float omb1 = 1.0f - beta1, omb2 = 1.0f - beta2, omt = 1.0f - tau;
+  const AdamK kk(beta1, beta2, eps, tau);
   float zero = 0.f;
   asm volatile("" : "+v"(zero));
   const int64_t row_lane = ((int64_t)1 << ld4row) - 1;
@@ -814,26 +799,15 @@ __global__ __launch_bounds__(256) void adam_ema_rows_deferred_kernel(
       if ((i & row_lane) == 0) age[row] = go ? (uint8_t)0 : (uint8_t)k;
     }
     if (go) {
-      float4 p4 = ld4<NT>(theta + i), m4 = ld4<NT>(m + i), v4 = ld4<NT>(v + i), t4 = ld4<NT>(target + i);
+      Adam4 x = adam_load4<NT>(theta, m, v, target, i);
       float4 g4 = make_float4(zero, zero, zero, zero);
       if (live) g4 = ld4<NT>(grads + i);
-      const float gc[4] = {g4.x, g4.y, g4.z, g4.w};
-      float p[4] = {p4.x, p4.y, p4.z, p4.w}, mm[4] = {m4.x, m4.y, m4.z, m4.w}, vv[4] = {v4.x, v4.y, v4.z, v4.w},
-            tt[4] = {t4.x, t4.y, t4.z, t4.w};
       for (int a = k - 1; a >= 0; --a) {
         const float2 sc = tab_s[(step - (uint32_t)a) & (uint32_t)(CQL_ADAM_DEFER_CAP - 1)];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const float g = a == 0 ? gc[j] : zero;
-          adam_ema_elem(g, p[j], mm[j], vv[j], tt[j], sc.x, sc.y, beta1, beta2, eps, tau, omb1, omb2, omt);
-        }
+        const float g[4] = {a == 0 ? g4.x : zero, a == 0 ? g4.y : zero, a == 0 ? g4.z : zero, a == 0 ? g4.w : zero};
+        x.step(g, kk, sc.x, sc.y);
       }
-      st4<NT>(theta + i, p[0], p[1], p[2], p[3]);
-      st4<NT>(m + i, mm[0], mm[1], mm[2], mm[3]);
-      st4<NT>(v + i, vv[0], vv[1], vv[2], vv[3]);
-      st4<NT>(target + i, tt[0], tt[1], tt[2], tt[3]);
-      theta_b[i] = make_uint2(pack_bf16x2(p[0], p[1]), pack_bf16x2(p[2], p[3]));
-      target_b[i] = make_uint2(pack_bf16x2(tt[0], tt[1]), pack_bf16x2(tt[2], tt[3]));
+      adam_store4<NT>(theta, m, v, target, theta_b, target_b, i, x);
     }
     if (zero_grads) st4<NT>(grads + i, 0.f, 0.f, 0.f, 0.f);
   }
@@ -850,10 +824,8 @@ int cql_adam_ema_rows_deferred(float* theta, float* grads, float* m, float* v, f
   CQL_REQUIRE(n_rows >= 0 && n_rows * d <= n, "adam_ema_rows_deferred: %lld rows of %d do not fit n=%lld", (long long)n_rows,
               d, (long long)n);
   const int64_t n4 = n / 4;
-  int blocks = (int)((n4 + 255) / 256);
-  if (blocks > 8192) blocks = 8192;
   CqlProfScope prof(CQLREC_PH_ADAM, stream);
-  hipLaunchKernelGGL(adam_ema_rows_deferred_kernel<true>, dim3(blocks), dim3(256), 0, stream, (float4*)theta, (float4*)grads,
+  hipLaunchKernelGGL(adam_ema_rows_deferred_kernel<true>, dim3(float4_stream_grid(n4)), dim3(256), 0, stream, (float4*)theta, (float4*)grads,
                      (float4*)m, (float4*)v, (float4*)target, (uint2*)theta_b, (uint2*)target_b, n4, tab, (uint32_t)step,
                      beta1, beta2, eps, tau, zero_grads, row_map, read_next, age, __builtin_ctz((unsigned)d) - 2, n_rows);
   CQL_LAUNCH_CHECK("adam_ema (deferred rows)");
@@ -864,14 +836,15 @@ int cql_adam_ema_rows_deferred(float* theta, float* grads, float* m, float* v, f
 // updated range).  D and the items per group are powers of two and every offset is a multiple of 4, so the four elements
 // belong to one item (rows) or to four items of one group (column sums); 32-bit arithmetic (the host checks the range).
 __device__ __forceinline__ void adam_fix4(const CqlAdamFix& f, float (&g)[4], int64_t i4, int ld, int li) {
+  const QdeSlab& s = f.s;
   const int64_t e = 4 * i4;
   uint32_t item;
   int col = -1;
-  if (e >= f.rows_off && e < f.rows_off + f.n_items * f.D) {
+  if (e >= f.rows_off && e < f.rows_off + s.n_items * s.D) {
     const uint64_t r = (uint64_t)(e - f.rows_off);
     item = (uint32_t)(r >> ld);
-    col = (int)(r & (uint64_t)(f.D - 1));
-  } else if (e >= f.cs_off && e < f.cs_off + f.n_items) {
+    col = (int)(r & (uint64_t)(s.D - 1));
+  } else if (e >= f.cs_off && e < f.cs_off + s.n_items) {
     item = (uint32_t)(e - f.cs_off);
   } else {
     return;
@@ -879,21 +852,18 @@ __device__ __forceinline__ void adam_fix4(const CqlAdamFix& f, float (&g)[4], in
 #ifdef ADAMFIX_ABL_NOLOOP      // timing-only build: the gradient without the slabs
   return;
 #endif
-  const uint32_t grp = item >> li, row = item & (uint32_t)(f.items - 1);
-  const uint32_t W = (uint32_t)f.G * (uint32_t)f.T, nblk = (uint32_t)f.nblk, lo = grp * (uint32_t)f.T, hi = lo + (uint32_t)f.T;
-  for (uint32_t p = ((lo + 1) * nblk + W - 1) / W; p < nblk; ++p) {     // the pieces, in block order
-    const uint32_t u0 = (uint32_t)((uint64_t)p * W / nblk);
-    if (u0 >= hi) break;
-    if (u0 <= lo) continue;
-    if ((uint32_t)(((uint64_t)p + 1) * W / nblk) == u0) continue;
+  const uint32_t grp = item >> li, row = item & (uint32_t)(s.items - 1);
+  // (qde_axpy of qde_pieces.h, kept in place: through it hipcc builds this kernel's grid-stride loop differently -- 9 loops
+  // become 6, 4380 bytes 4400.  `g += scale * slab` is its product, then sum: this file is compiled without contraction)
+  QDE_FOR_SLAB_PIECES(uint32_t, uint64_t, s.pc, grp, p) {
     if (col >= 0) {
-      const float4 s4 = *reinterpret_cast<const float4*>(f.slab + ((int64_t)p * f.items + row) * f.D + col);
-      g[0] += f.scale * s4.x; g[1] += f.scale * s4.y; g[2] += f.scale * s4.z; g[3] += f.scale * s4.w;
+      const float4 s4 = *reinterpret_cast<const float4*>(s.row(p, row) + col);
+      g[0] += s.scale * s4.x; g[1] += s.scale * s4.y; g[2] += s.scale * s4.z; g[3] += s.scale * s4.w;
     } else {
-      const float* sc = f.slab_cs + (int64_t)p * f.items + row;
+      const float* sc = s.cs(p, row);
 #pragma unroll
       for (int k = 0; k < 4; ++k)
-        if ((int64_t)item + k < f.n_items) g[k] += f.scale * sc[k];
+        if ((int64_t)item + k < s.n_items) g[k] += s.scale * sc[k];
     }
   }
 }
@@ -905,66 +875,42 @@ __global__ __launch_bounds__(256) void adam_ema_fix_kernel(float4* __restrict__ 
                                                            uint2* __restrict__ target_b, int64_t n4, float step_size,
                                                            float sqrt_bc2, float beta1, float beta2, float eps, float tau,
                                                            int zero_grads, CqlAdamFix fix) {
-  const float omb1 = 1.0f - beta1, omb2 = 1.0f - beta2, omt = 1.0f - tau;
-  const int ld = __builtin_ctz((unsigned)fix.D), li = __builtin_ctz((unsigned)fix.items);
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
-    const float4 g4 = ld4<NT>(grads + i);
-    float4 p4 = ld4<NT>(theta + i), m4 = ld4<NT>(m + i), v4 = ld4<NT>(v + i), t4 = ld4<NT>(target + i);
-    float g[4] = {g4.x, g4.y, g4.z, g4.w};
-    adam_fix4(fix, g, i, ld, li);
-    float p[4] = {p4.x, p4.y, p4.z, p4.w}, mm[4] = {m4.x, m4.y, m4.z, m4.w}, vv[4] = {v4.x, v4.y, v4.z, v4.w},
-          tt[4] = {t4.x, t4.y, t4.z, t4.w};
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      adam_ema_elem(g[k], p[k], mm[k], vv[k], tt[k], step_size, sqrt_bc2, beta1, beta2, eps, tau, omb1, omb2, omt);
-    }
-    st4<NT>(theta + i, p[0], p[1], p[2], p[3]);
-    st4<NT>(m + i, mm[0], mm[1], mm[2], mm[3]);
-    st4<NT>(v + i, vv[0], vv[1], vv[2], vv[3]);
-    st4<NT>(target + i, tt[0], tt[1], tt[2], tt[3]);
-    theta_b[i] = make_uint2(pack_bf16x2(p[0], p[1]), pack_bf16x2(p[2], p[3]));
-    target_b[i] = make_uint2(pack_bf16x2(tt[0], tt[1]), pack_bf16x2(tt[2], tt[3]));
-    if (zero_grads) st4<NT>(grads + i, 0.f, 0.f, 0.f, 0.f);
-  }
+  const AdamK k(beta1, beta2, eps, tau);
+  const int ld = __builtin_ctz((unsigned)fix.s.D), li = __builtin_ctz((unsigned)fix.s.items);
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x)
+    adam_ema_body<NT>(theta, grads, m, v, target, theta_b, target_b, i, k, step_size, sqrt_bc2, zero_grads,
+                      [&](float (&g)[4], int64_t i4) __attribute__((always_inline)) { adam_fix4(fix, g, i4, ld, li); });
 }
 
+// one launch site for the dense form: with `fix` valid the kernel that adds the slab pieces, else the plain one
 int cql_adam_ema_fix(float* theta, float* grads, float* m, float* v, float* target, uint16_t* theta_b, uint16_t* target_b,
                      int64_t n, float step_size, float sqrt_bc2, float beta1, float beta2, float eps, float tau,
                      int32_t zero_grads, const CqlAdamFix* fix, hipStream_t stream) {
-  const bool pow2 = fix && fix->valid && (fix->D & (fix->D - 1)) == 0 && (fix->items & (fix->items - 1)) == 0 &&
+  const bool on = fix && fix->valid;
+  const bool pow2 = on && (fix->s.D & (fix->s.D - 1)) == 0 && (fix->s.items & (fix->s.items - 1)) == 0 &&
                     fix->rows_off % 4 == 0 && fix->cs_off % 4 == 0 &&
-                    (int64_t)fix->G * fix->T * ((int64_t)fix->nblk + 1) < (1ll << 31) && fix->n_items < (1ll << 31);
-  CQL_REQUIRE(!fix || !fix->valid || pow2, "adam_ema: deferred fix-up outside the supported range");
-  if (!fix || !fix->valid)
-    return cqlrec_adam_ema(theta, grads, m, v, target, theta_b, target_b, n, step_size, sqrt_bc2, beta1, beta2, eps, tau,
-                           zero_grads, (cqlrec_stream)stream);
+                    fix->s.pc.W() * ((int64_t)fix->s.pc.nblk + 1) < (1ll << 31) && fix->s.n_items < (1ll << 31);
+  CQL_REQUIRE(!on || pow2, "adam_ema: deferred fix-up outside the supported range");
   CQL_REQUIRE(theta && grads && m && v && target && theta_b && target_b, "adam_ema: NULL pointer");
   CQL_REQUIRE(n > 0 && n % 4 == 0, "adam_ema: n=%lld must be a positive multiple of 4", (long long)n);
   const int64_t n4 = n / 4;
-  int blocks = (int)((n4 + 255) / 256);
-  if (blocks > 8192) blocks = 8192;
   CqlProfScope prof(CQLREC_PH_ADAM, stream);
-  hipLaunchKernelGGL(adam_ema_fix_kernel<true>, dim3(blocks), dim3(256), 0, stream, (float4*)theta, (float4*)grads,
-                     (float4*)m, (float4*)v, (float4*)target, (uint2*)theta_b, (uint2*)target_b, n4, step_size, sqrt_bc2,
-                     beta1, beta2, eps, tau, zero_grads, *fix);
-  CQL_LAUNCH_CHECK("adam_ema (deferred fix-up)");
+#define ADAM_LAUNCH(kernel, ...)                                                                                       \
+  hipLaunchKernelGGL(kernel, dim3(float4_stream_grid(n4)), dim3(256), 0, stream, (float4*)theta, (float4*)grads, (float4*)m,    \
+                     (float4*)v, (float4*)target, (uint2*)theta_b, (uint2*)target_b, n4, step_size, sqrt_bc2, beta1, beta2, \
+                     eps, tau, zero_grads, ##__VA_ARGS__)
+  if (on) ADAM_LAUNCH(adam_ema_fix_kernel<true>, *fix);
+  else ADAM_LAUNCH(adam_ema_kernel<true>);
+#undef ADAM_LAUNCH
+  CQL_LAUNCH_CHECK(on ? "adam_ema (deferred fix-up)" : "adam_ema");
   return CQLREC_OK;
 }
 
 extern "C" int cqlrec_adam_ema(float* theta, float* grads, float* m, float* v, float* target, uint16_t* theta_b,
                                uint16_t* target_b, int64_t n, float step_size, float sqrt_bc2, float beta1, float beta2,
                                float eps, float tau, int32_t zero_grads, cqlrec_stream stream) {
-  CQL_REQUIRE(theta && grads && m && v && target && theta_b && target_b, "adam_ema: NULL pointer");
-  CQL_REQUIRE(n > 0 && n % 4 == 0, "adam_ema: n=%lld must be a positive multiple of 4", (long long)n);
-  const int64_t n4 = n / 4;
-  int blocks = (int)((n4 + 255) / 256);
-  if (blocks > 8192) blocks = 8192;
-  CqlProfScope prof(CQLREC_PH_ADAM, (hipStream_t)stream);
-  hipLaunchKernelGGL(adam_ema_kernel<true>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (float4*)theta,
-                     (float4*)grads, (float4*)m, (float4*)v, (float4*)target, (uint2*)theta_b, (uint2*)target_b, n4,
-                     step_size, sqrt_bc2, beta1, beta2, eps, tau, zero_grads);
-  CQL_LAUNCH_CHECK("adam_ema");
-  return CQLREC_OK;
+  return cql_adam_ema_fix(theta, grads, m, v, target, theta_b, target_b, n, step_size, sqrt_bc2, beta1, beta2, eps, tau,
+                          zero_grads, nullptr, (hipStream_t)stream);
 }
 
 __global__ __launch_bounds__(256) void cast_bf16_kernel(const float4* __restrict__ src, uint2* __restrict__ dst,
@@ -978,9 +924,7 @@ extern "C" int cqlrec_cast_bf16(const float* src, uint16_t* dst_b, int64_t n, cq
   CQL_REQUIRE(src && dst_b, "cast_bf16: NULL pointer");
   CQL_REQUIRE(n > 0 && n % 4 == 0, "cast_bf16: n=%lld must be a positive multiple of 4", (long long)n);
   const int64_t n4 = n / 4;
-  int blocks = (int)((n4 + 255) / 256);
-  if (blocks > 8192) blocks = 8192;
-  hipLaunchKernelGGL(cast_bf16_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const float4*)src,
+  hipLaunchKernelGGL(cast_bf16_kernel, dim3(float4_stream_grid(n4)), dim3(256), 0, (hipStream_t)stream, (const float4*)src,
                      (uint2*)dst_b, n4);
   CQL_LAUNCH_CHECK("cast_bf16");
   return CQLREC_OK;

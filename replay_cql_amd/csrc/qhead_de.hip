@@ -10,9 +10,8 @@
 //  * work = G item groups (128 items: 32 per wave, owner fragments in registers) x T stages of 64 states.  The G*T
 //    stage-units are cut into `gridDim.x` CONTIGUOUS, EQUAL ranges, one per persistent block (2 per CU), so every SIMD gets
 //    the same number of MFMAs -- the generic kernel gives a SIMD 3 or 4 item tiles (24 % of the slot-time idle at
-//    N = 100 000).  A group that straddles two ranges is summed in two pieces: the piece that holds stage 0 goes straight
-//    to g_E_out (on top of the one-hot part already scattered there), the other one to a slab that a small fix-up
-//    kernel adds afterwards, in block order -- deterministic, no atomics.  The stream of state tiles just wraps around at a
+//    N = 100 000).  A group that straddles ranges is summed in pieces, through a slab and a fix-up in block order --
+//    deterministic, no atomics: qde_pieces.h states that contract.  The stream of state tiles just wraps around at a
 //    group boundary, so the LDS-DMA ring never drains there.
 //  * zero VALU instructions for staging: `buffer_load_dwordx4 ... offen lds` with a per-lane constant voffset and the
 //    stage offset in an SGPR (the generic kernel spends ~35 VALU per stage on 64-bit addresses and tail clamps; the
@@ -38,14 +37,14 @@ __global__ __launch_bounds__(64 * WAVES, (D == 256 ? 1 : 2)) void qde_kernel(QDe
   const int r = lane & 31, h = lane >> 5;
 
   // ---- this block's range of stage-units ---------------------------------------------------------------------
-  const int64_t W = (int64_t)a.G * a.T;
-  const int64_t u0 = (int64_t)blockIdx.x * W / gridDim.x, u1 = ((int64_t)blockIdx.x + 1) * W / gridDim.x;
-  const int nst = (int)(u1 - u0);
+  const QdePieces pc = {a.G, a.T, (int32_t)gridDim.x};
+  const QdePieces::Range rg = pc.range(blockIdx.x);
+  const int nst = rg.nst;
   if (nst <= 0) return;
   unsigned long long stamp_tk = 0, stamp_rt = 0;
   if (a.stamps) qde_stamp(stamp_tk, stamp_rt);
-  int g = (int)(u0 / a.T);               // current item group
-  int t = (int)(u0 - (int64_t)g * a.T);  // current stage inside the group
+  const QdePieces::Unit beg = pc.unit(rg.u0);
+  int g = beg.g, t = beg.t;          // current item group, current stage inside the group
   int t_seg = t;                         // first stage of the current piece of the group
   int t_dma = t;                         // stage of the next DMA to issue
 
@@ -127,6 +126,8 @@ __global__ __launch_bounds__(64 * WAVES, (D == 256 ? 1 : 2)) void qde_kernel(QDe
       for (int i = 0; i < 16; ++i) y[ft][i] = 0.f;
     cs = 0.f;
   };
+  // (qde_store_group of qhead_image.h, kept in place: this kernel's accumulate fuses scale * csum into the column sum it
+  // adds to -- v_fmac_f32 under the file's default contraction -- where the shared form is a product and a sum)
   auto store_piece = [&](int grp, bool first) {
     const int64_t row = (int64_t)grp * QDE_ITEMS + wave * 32 + r;
     const bool ok = row < a.n_items;
@@ -150,14 +151,15 @@ __global__ __launch_bounds__(64 * WAVES, (D == 256 ? 1 : 2)) void qde_kernel(QDe
         if (h == 0) a.out_cs[row] = a.accumulate ? a.out_cs[row] + a.scale * csum : a.scale * csum;
       }
     } else {   // a piece that starts past stage 0: unscaled, to this block's slab (rows past n_items: harmless, not read)
-      float* dst = a.slab + ((int64_t)blockIdx.x * QDE_ITEMS + wave * 32 + r) * D;
+      const int64_t srow = qde_slab_row(blockIdx.x, QDE_ITEMS, wave * 32 + r);
+      float* dst = a.slab + srow * D;
 #pragma unroll
       for (int ft = 0; ft < C::FT; ++ft)
 #pragma unroll
         for (int q = 0; q < 4; ++q)
           *reinterpret_cast<float4*>(dst + ft * 32 + 8 * q + 4 * h) =
               make_float4(y[ft][4 * q + 0], y[ft][4 * q + 1], y[ft][4 * q + 2], y[ft][4 * q + 3]);
-      if (h == 0) a.slab_cs[(int64_t)blockIdx.x * QDE_ITEMS + wave * 32 + r] = csum;
+      if (h == 0) a.slab_cs[srow] = csum;
     }
   };
 
@@ -294,31 +296,21 @@ __global__ __launch_bounds__(64 * WAVES, (D == 256 ? 1 : 2)) void qde_kernel(QDe
   }
 }
 
-// out[group rows] += scale * slab pieces of the blocks whose range starts inside the group (in block order)
+// out[group rows] += scale * slab pieces of the group, in block order (one block per group)
 template <int D, int QDE_ITEMS>
-__global__ __launch_bounds__(256) void qde_fixup_kernel(QDeArgs a, int nblk) {
-#pragma clang fp contract(off)      // product, then sum: the bits of the deferred fix-up (cql_adam_ema_fix, misc.hip)
-  const int g = blockIdx.x;
-  const int64_t W = (int64_t)a.G * a.T;
-  const int64_t lo = (int64_t)g * a.T, hi = lo + a.T;
-  // first block p with u0(p) = floor(p W / nblk) > lo
-  int64_t p = ((lo + 1) * nblk + W - 1) / W;
-  for (; p < nblk; ++p) {
-    const int64_t u0 = p * W / nblk;
-    if (u0 >= hi) break;
-    if (u0 <= lo) continue;
-    if (((p + 1) * W / nblk) == u0) continue;          // an empty range wrote nothing
-    const float* src = a.slab + p * QDE_ITEMS * D;
+__global__ __launch_bounds__(256) void qde_fixup_kernel(QdeSlab sl, float* out, float* out_cs) {
+  const int64_t g = blockIdx.x;
+  QDE_FOR_SLAB_PIECES(int64_t, int64_t, sl.pc, g, p) {
     for (int idx = threadIdx.x; idx < QDE_ITEMS * (D / 4); idx += blockDim.x) {
       const int row = idx / (D / 4), c = idx % (D / 4);
-      const int64_t item = (int64_t)g * QDE_ITEMS + row;
-      if (item >= a.n_items) continue;
-      const float4 s = *reinterpret_cast<const float4*>(src + (int64_t)row * D + c * 4);
-      float4* pd = reinterpret_cast<float4*>(a.out + item * D + c * 4);
-      float4 o = *pd;
-      o.x += a.scale * s.x; o.y += a.scale * s.y; o.z += a.scale * s.z; o.w += a.scale * s.w;
-      *pd = o;
-      if (c == 0) a.out_cs[item] += a.scale * a.slab_cs[p * QDE_ITEMS + row];
+      const int64_t item = g * QDE_ITEMS + row;
+      if (item >= sl.n_items) continue;
+      const float4 s = *reinterpret_cast<const float4*>(sl.row(p, row) + c * 4);
+      float4* pd = reinterpret_cast<float4*>(out + item * D + c * 4);
+      const float4 o = *pd;
+      *pd = make_float4(qde_axpy(o.x, sl.scale, s.x), qde_axpy(o.y, sl.scale, s.y), qde_axpy(o.z, sl.scale, s.z),
+                        qde_axpy(o.w, sl.scale, s.w));
+      if (c == 0) out_cs[item] = qde_axpy(out_cs[item], sl.scale, *sl.cs(p, row));
     }
     __syncthreads();
   }
@@ -337,31 +329,25 @@ static int de_env_int(const char* name, int dflt) {
   const char* v = getenv(name);
   return (v && *v) ? atoi(v) : dflt;
 }
-// block shape: 8 waves (256 items per group, ONE block per CU, both waves of a SIMD stream the same tiles: half the LDS
-// fill traffic and half the LDS-DMA instructions per MFMA of the 4-wave form) unless the register budget forbids two
-// waves per SIMD (d = 256).  Form 2 has the same 256-item groups.
-static constexpr int de_waves(int d) { return d == 256 ? 4 : 8; }
+// block shape of qde_kernel: 32 items per wave, so 8 waves (256 items per group, ONE block per CU, both waves of a SIMD
+// stream the same tiles: half the LDS fill traffic and half the LDS-DMA instructions per MFMA of the 4-wave form) unless
+// the register budget forbids two waves per SIMD (d = 256)
+static constexpr int de_waves(int d) { return qde_items(d) / 32; }
 // LDS stage buffers of qde_kernel (prefetch distance 1 stage)
 #define QDE_NBUF 2
-// form 2 (64 items per wave, one wave per SIMD, in-wave pipeline: qhead_de2.hip) for d = 128
-static bool de_form2(int d, int64_t batch) { return d == 128 && batch % 64 == 0; }
-// one persistent block per CU (fewer when there are fewer stage-units than CUs)
-static int de_grid(int64_t n_items, int64_t batch, int d) {
-  const int ti = (d == 256) ? 32 : 64, items = 32 * de_waves(d);
-  const int64_t G = (n_items + items - 1) / items, T = (batch + ti - 1) / ti;
+// the device's CU count for qde_plan (0: unknown)
+static int de_n_cu() {
   static const int n_cu = [] {
     int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        n <= 0 || n > 256)
-      n = 256;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+      n = 0;
     return n;
   }();
-  const int64_t W = G * T;
-  return (int)(W < n_cu ? W : n_cu);
+  return n_cu;
 }
 
 int64_t cql_qde_ws_bytes(int64_t batch, int64_t n_items, int32_t d) {
-  const int64_t grid = 512;      // upper bound of de_grid() for every block shape
+  const int64_t grid = 512;      // upper bound of qde_plan()'s grid for every block shape
   return cql_align256(grid * QDE_MAX_ITEMS * d * 4) + cql_align256(grid * QDE_MAX_ITEMS * 4) + cql_align256(batch * 4) + cql_align256(grid * 16) + 256;
 }
 
@@ -376,9 +362,12 @@ static void qde_launch_n(const QDeArgs& a, int grid, hipStream_t s) {
   }
   hipLaunchKernelGGL((qde_kernel<D, NBUF, WAVES>), dim3(grid), dim3(64 * WAVES), smem, s, a);
 }
-template <int D>
-static void qde_fixup_d(const QDeArgs& a, int grid, hipStream_t s) {
-  hipLaunchKernelGGL((qde_fixup_kernel<D, 32 * de_waves(D)>), dim3(a.G), dim3(256), 0, s, a, grid);
+// the fix-up launch: the slab pieces of `sl` onto the gradient
+static void qde_fixup(const QdeSlab& sl, float* out, float* out_cs, hipStream_t s) {
+  CqlProfScope prof(CQLREC_PH_QHEAD_SMALL, s);
+#define FIXUP(DD) hipLaunchKernelGGL((qde_fixup_kernel<DD, qde_items(DD)>), dim3(sl.pc.G), dim3(256), 0, s, sl, out, out_cs)
+  if (sl.D == 64) FIXUP(64); else if (sl.D == 128) FIXUP(128); else FIXUP(256);
+#undef FIXUP
 }
 
 // g_E_out / g_b_out rows [0, n_items) of this call: out (+)= scale * dE (accumulate: on top of what is there)
@@ -388,8 +377,8 @@ int cql_qde_launch(const uint16_t* H_b, const float* nlse2, int64_t batch, const
   if (defer) defer->valid = 0;
   CQL_REQUIRE(ws_bytes >= cql_qde_ws_bytes(batch, n_items, d), "qde: workspace too small");
   CQL_REQUIRE(batch * 2 * d < (1ll << 31), "qde: batch=%lld too large for one buffer descriptor", (long long)batch);
-  const bool form2 = de_form2(d, batch);
-  const int ti = (d == 256) ? 32 : 64, items = 32 * de_waves(d);
+  const QdePlan pl = qde_plan(batch, n_items, d, de_n_cu());
+  const int grid = pl.pc.nblk, items = pl.items;
   QDeArgs a = {};
   a.H_b = H_b;
   a.nlse2 = nlse2;
@@ -401,17 +390,15 @@ int cql_qde_launch(const uint16_t* H_b, const float* nlse2, int64_t batch, const
   a.out_cs = out_cs;
   a.scale = scale;
   a.accumulate = accumulate;
-  a.G = (int32_t)((n_items + items - 1) / items);
-  a.T = (int32_t)((batch + ti - 1) / ti);
-  const int grid = de_grid(n_items, batch, d);
+  a.G = pl.pc.G;
+  a.T = pl.pc.T;
   a.slab = (float*)ws;
   a.slab_cs = (float*)((char*)ws + cql_align256((int64_t)grid * items * d * 4));
   static const int want_stamps = de_env_int("CQL_QDE_STAMPS", 0);     // diagnostic: in-kernel clock, synchronises
   unsigned long long* stamps_dev = (unsigned long long*)((char*)a.slab_cs + cql_align256((int64_t)grid * items * 4) +
                                                          cql_align256(batch * 4));
   a.stamps = want_stamps ? stamps_dev : nullptr;
-  const bool form3 = !form2 && cql_qde3_supported(d, batch);      // d = 256: same groups, stages and grid as qde_kernel<256>
-  if (form2 || form3) {
+  if (pl.form != QDE_FORM_GENERIC) {
     if (nlse_nat) {        // the caller's forward already wrote -lse in natural units
       a.nlse2 = nlse_nat;
     } else {
@@ -423,7 +410,7 @@ int cql_qde_launch(const uint16_t* H_b, const float* nlse2, int64_t batch, const
       a.nlse2 = nat;
     }
     CqlProfScope prof(CQLREC_PH_QHEAD_BWD_DE, s);
-    const int rc = form2 ? cql_qde2_run(a, d, grid, s) : cql_qde3_run(a, d, grid, s);
+    const int rc = pl.form == QDE_FORM_2 ? cql_qde2_run(a, d, grid, s) : cql_qde3_run(a, d, grid, s);
     if (rc != CQLREC_OK) return rc;
   } else {
     CqlProfScope prof(CQLREC_PH_QHEAD_BWD_DE, s);
@@ -431,25 +418,14 @@ int cql_qde_launch(const uint16_t* H_b, const float* nlse2, int64_t batch, const
     else if (d == 128) qde_launch_n<128, QDE_NBUF, de_waves(128)>(a, grid, s);
     else qde_launch_n<256, QDE_NBUF, de_waves(256)>(a, grid, s);
   }
-  const int64_t W = (int64_t)a.G * a.T;
-  bool cut = false;                    // does some range start inside a group?
-  for (int p = 1; p < grid && !cut; ++p) cut = ((int64_t)p * W / grid) % a.T != 0;
-  if (cut && defer) {     // the consumer of the gradient adds the slabs (see CqlAdamFix): same terms, same order
-    defer->valid = 1;
-    defer->slab = a.slab;
-    defer->slab_cs = a.slab_cs;
-    defer->G = a.G;
-    defer->T = a.T;
-    defer->nblk = grid;
-    defer->items = items;
-    defer->D = d;
-    defer->scale = a.scale;
-    defer->n_items = n_items;
-  } else if (cut) {
-    CqlProfScope prof(CQLREC_PH_QHEAD_SMALL, s);
-    if (d == 64) qde_fixup_d<64>(a, grid, s);
-    else if (d == 128) qde_fixup_d<128>(a, grid, s);
-    else qde_fixup_d<256>(a, grid, s);
+  if (pl.pc.any_cut()) {
+    const QdeSlab sl = {a.slab, a.slab_cs, pl.pc, items, d, scale, n_items};
+    if (defer) {          // the consumer of the gradient adds the slabs (see CqlAdamFix): same terms, same order
+      defer->valid = 1;
+      defer->s = sl;
+    } else {
+      qde_fixup(sl, out, out_cs, s);
+    }
   }
   CQL_LAUNCH_CHECK("qde");
   if (want_stamps) {      // median over blocks of shader ticks / 100 MHz ticks (MI355X_MICROARCH.md, DVFS give-back item 6)
@@ -489,19 +465,7 @@ int cql_qde_launch(const uint16_t* H_b, const float* nlse2, int64_t batch, const
 // the rows between the long kernel and the slabs: the one-hot part, see train.hip)
 int cql_qde_fixup_deferred(const CqlAdamFix& f, float* out, float* out_cs, hipStream_t s) {
   if (!f.valid) return CQLREC_OK;
-  QDeArgs a = {};
-  a.n_items = f.n_items;
-  a.out = out;
-  a.out_cs = out_cs;
-  a.scale = f.scale;
-  a.slab = const_cast<float*>(f.slab);
-  a.slab_cs = const_cast<float*>(f.slab_cs);
-  a.G = f.G;
-  a.T = f.T;
-  CqlProfScope prof(CQLREC_PH_QHEAD_SMALL, s);
-  if (f.D == 64) qde_fixup_d<64>(a, f.nblk, s);
-  else if (f.D == 128) qde_fixup_d<128>(a, f.nblk, s);
-  else qde_fixup_d<256>(a, f.nblk, s);
+  qde_fixup(f.s, out, out_cs, s);
   CQL_LAUNCH_CHECK("qde fix-up");
   return CQLREC_OK;
 }

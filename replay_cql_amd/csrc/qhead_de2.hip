@@ -19,26 +19,18 @@
 // enters the exponent as a per-lane constant:  P = exp2((S - lse) log2e + b log2e).
 // The accumulators of both groups (128 registers at d = 128) are touched by MFMAs only and live in the AGPR half of the
 // file; everything the VALU reads stays below 256.
-// Work decomposition, LDS image, staging and the deterministic two-piece sum of cut groups: as qde_kernel (qhead_de.hip).
+// Work decomposition and the deterministic sum of cut groups: qde_pieces.h.  LDS image and staging: as qde_kernel.
 #include <stdlib.h>
 #include <type_traits>
 #include "qhead_image.h"
 
-#define QDE2_ITEMS 256      // items per group: 4 waves x 2 x 32
+#define QDE2_ITEMS qde_items(128)      // items per group: 4 waves x 2 x 32
 #ifndef QDE2_NBUF
 #define QDE2_NBUF 2         // ring depth (stages of 64 states): with 2 the pieces a turn waits for were issued ONE stage
 #endif                      // earlier and the wave parks on vmcnt(0) (PMC r02: 23 % of the wave's life in s_waitcnt / barrier)
 #ifndef QDE2_VALU_PER_MFMA
 #define QDE2_VALU_PER_MFMA 8   // VALU instructions the scheduler is asked to place behind each MFMA of slots 2 and 3
 #endif
-
-// out + scale * y as a product and a sum (never an fma): the terms and their order are those of the fix-up kernel and of
-// the deferred fix-up (misc.hip is compiled without contraction), so every path to the gradient gives the same bits
-__device__ __forceinline__ float qde2_axpy(float w, float scale, float u) {
-#pragma clang fp contract(off)
-  const float su = scale * u;
-  return w + su;
-}
 
 template <int D, bool MASK>
 __global__ __launch_bounds__(256, 1) void qde2_kernel(QDeArgs a) {
@@ -50,14 +42,14 @@ __global__ __launch_bounds__(256, 1) void qde2_kernel(QDeArgs a) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int r = lane & 31, h = lane >> 5;
 
-  const int64_t W = (int64_t)a.G * a.T;
-  const int64_t u0 = (int64_t)blockIdx.x * W / gridDim.x, u1 = ((int64_t)blockIdx.x + 1) * W / gridDim.x;
-  const int nst = (int)(u1 - u0);
+  const QdePieces pc = {a.G, a.T, (int32_t)gridDim.x};
+  const QdePieces::Range rg = pc.range(blockIdx.x);
+  const int nst = rg.nst;
   if (nst <= 0) return;
   unsigned long long stamp_tk = 0, stamp_rt = 0;
   if (a.stamps) qde_stamp(stamp_tk, stamp_rt);
-  int g = (int)(u0 / a.T);
-  int t = (int)(u0 - (int64_t)g * a.T);
+  const QdePieces::Unit beg = pc.unit(rg.u0);
+  int g = beg.g, t = beg.t;          // current item group, current stage inside the group
   int t_seg = t;
   int t_dma = t;
 
@@ -107,43 +99,10 @@ __global__ __launch_bounds__(256, 1) void qde2_kernel(QDeArgs a) {
   };
   auto store_piece = [&](int grp, bool first) {
 #pragma unroll
-    for (int gi = 0; gi < 2; ++gi) {
-      const int64_t row = (int64_t)grp * QDE2_ITEMS + wave * 64 + gi * 32 + r;
-      const bool ok = row < a.n_items;
-      const float csum = cs[gi] + __shfl_xor(cs[gi], 32);
-      if (first) {
-        if (ok) {
-          float* dst = a.out + row * D;
-#pragma unroll
-          for (int ft = 0; ft < FT; ++ft)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-              float4* pd = reinterpret_cast<float4*>(dst + ft * 32 + 8 * q + 4 * h);
-              float4 o;
-              if (a.accumulate) {
-                const float4 old = *pd;
-                o = make_float4(qde2_axpy(old.x, a.scale, y[gi][ft][4 * q + 0]), qde2_axpy(old.y, a.scale, y[gi][ft][4 * q + 1]),
-                                qde2_axpy(old.z, a.scale, y[gi][ft][4 * q + 2]), qde2_axpy(old.w, a.scale, y[gi][ft][4 * q + 3]));
-              } else {
-                o = make_float4(a.scale * y[gi][ft][4 * q + 0], a.scale * y[gi][ft][4 * q + 1],
-                                a.scale * y[gi][ft][4 * q + 2], a.scale * y[gi][ft][4 * q + 3]);
-              }
-              *pd = o;
-            }
-          if (h == 0) a.out_cs[row] = a.accumulate ? qde2_axpy(a.out_cs[row], a.scale, csum) : a.scale * csum;
-        }
-      } else {
-        const int64_t srow = (int64_t)blockIdx.x * QDE2_ITEMS + wave * 64 + gi * 32 + r;
-        float* dst = a.slab + srow * D;
-#pragma unroll
-        for (int ft = 0; ft < FT; ++ft)
-#pragma unroll
-          for (int q = 0; q < 4; ++q)
-            *reinterpret_cast<float4*>(dst + ft * 32 + 8 * q + 4 * h) =
-                make_float4(y[gi][ft][4 * q + 0], y[gi][ft][4 * q + 1], y[gi][ft][4 * q + 2], y[gi][ft][4 * q + 3]);
-        if (h == 0) a.slab_cs[srow] = csum;
-      }
-    }
+    for (int gi = 0; gi < 2; ++gi)      // (both rows summed term by term in 64 bits: with the in-group row formed first, in
+                                        // 32 or in 64 bits, hipcc takes four more AccVGPRs or changes the periods)
+      qde_store_group<D>(a, first, (int64_t)grp * QDE2_ITEMS + wave * 64 + gi * 32 + r,
+                         qde_slab_row(blockIdx.x, QDE2_ITEMS, 0) + wave * 64 + gi * 32 + r, h, y[gi], cs[gi]);
   };
 
   // ---- the software pipeline ---------------------------------------------------------------------------------------
@@ -440,7 +399,7 @@ static void qde2_launch_n(const QDeArgs& a, int grid, hipStream_t s) {
 // rows [0, n_items): `a` prepared by cql_qde_launch (G, T for 256-item groups; nlse2 = -lse in NATURAL units here)
 int cql_qde2_run(const QDeArgs& a, int d, int grid, hipStream_t s) {
   // whole stages only (the caller keeps the generic form for batches that are not a multiple of 64 states)
-  if (d != 128 || (a.n_states % DeCfg<128, 4>::TI) != 0) return CQLREC_ERR_INVALID;
+  if (qde_form(d, a.n_states) != QDE_FORM_2) return CQLREC_ERR_INVALID;
   qde2_launch_n<128, false>(a, grid, s);
   return CQLREC_OK;
 }

@@ -11,23 +11,16 @@
 //   16       -- the ring turns: stage t+2 has landed for everyone, everyone has read tile t; its buffer takes stage t+3 --
 //   16-31    dE += H(t)^T . P(t)           (16)       --                         rows + strip of tile t+2; gaps 16-20: LDS-DMA
 //
-// Work decomposition (persistent blocks over contiguous, equal ranges of the group x stage grid), the two-piece sum of a
-// cut group, its slab and the fix-up: exactly those of qde_kernel / qde2_kernel (qhead_de.hip), with which this kernel
-// shares group size (128 items), stage size (32 states) and grid -- it replaces qde_kernel<256> launch for launch.
+// Work decomposition, the sum of a cut group in pieces, its slab and the fix-up: qde_pieces.h.  Group size (128 items),
+// stage size (32 states) and grid are those of qde_kernel<256>, which this kernel replaces launch for launch.
 // A piece starts by re-reading its first tile's rows (the pipeline has already replaced them by the rows two tiles ahead)
 // and forming that tile's scores on its own; the scores the previous piece formed for it with ITS items are dropped.
 #include <stdlib.h>
 #include <type_traits>
 #include "qhead_image.h"
 
-#define QDE3_ITEMS 128
+#define QDE3_ITEMS qde_items(256)
 #define QDE3_NBUF 3
-
-__device__ __forceinline__ float qde3_axpy(float w, float scale, float u) {
-#pragma clang fp contract(off)
-  const float su = scale * u;        // product, then sum: the terms and order of the fix-up paths (see qde2_axpy)
-  return w + su;
-}
 
 template <int D>
 __global__ __launch_bounds__(256, 1) void qde3_kernel(QDeArgs a) {
@@ -40,12 +33,12 @@ __global__ __launch_bounds__(256, 1) void qde3_kernel(QDeArgs a) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int r = lane & 31, h = lane >> 5;
 
-  const int64_t W = (int64_t)a.G * a.T;
-  const int64_t u0 = (int64_t)blockIdx.x * W / gridDim.x, u1 = ((int64_t)blockIdx.x + 1) * W / gridDim.x;
-  const int nst = (int)(u1 - u0);
+  const QdePieces pc = {a.G, a.T, (int32_t)gridDim.x};
+  const QdePieces::Range rg = pc.range(blockIdx.x);
+  const int nst = rg.nst;
   if (nst <= 0) return;
-  int g = (int)(u0 / a.T);
-  int t = (int)(u0 - (int64_t)g * a.T);
+  const QdePieces::Unit beg = pc.unit(rg.u0);
+  int g = beg.g, t = beg.t;          // current item group, current stage inside the group
   int t_seg = t;
   int t_dma = t;
 
@@ -97,41 +90,8 @@ __global__ __launch_bounds__(256, 1) void qde3_kernel(QDeArgs a) {
     cs = 0.f;
   };
   auto store_piece = [&](int grp, bool first) __attribute__((always_inline)) {
-    const int64_t row = (int64_t)grp * QDE3_ITEMS + wave * 32 + r;
-    const bool ok = row < a.n_items;
-    const float csum = cs + __shfl_xor(cs, 32);
-    if (first) {
-      if (ok) {
-        float* dst = a.out + row * D;
-#pragma unroll
-        for (int ft = 0; ft < FT; ++ft)
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            float4* pd = reinterpret_cast<float4*>(dst + ft * 32 + 8 * q + 4 * h);
-            float4 o;
-            if (a.accumulate) {
-              const float4 old = *pd;
-              o = make_float4(qde3_axpy(old.x, a.scale, y[ft][4 * q + 0]), qde3_axpy(old.y, a.scale, y[ft][4 * q + 1]),
-                              qde3_axpy(old.z, a.scale, y[ft][4 * q + 2]), qde3_axpy(old.w, a.scale, y[ft][4 * q + 3]));
-            } else {
-              o = make_float4(a.scale * y[ft][4 * q + 0], a.scale * y[ft][4 * q + 1], a.scale * y[ft][4 * q + 2],
-                              a.scale * y[ft][4 * q + 3]);
-            }
-            *pd = o;
-          }
-        if (h == 0) a.out_cs[row] = a.accumulate ? qde3_axpy(a.out_cs[row], a.scale, csum) : a.scale * csum;
-      }
-    } else {
-      const int64_t srow = (int64_t)blockIdx.x * QDE3_ITEMS + wave * 32 + r;
-      float* dst = a.slab + srow * D;
-#pragma unroll
-      for (int ft = 0; ft < FT; ++ft)
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-          *reinterpret_cast<float4*>(dst + ft * 32 + 8 * q + 4 * h) =
-              make_float4(y[ft][4 * q + 0], y[ft][4 * q + 1], y[ft][4 * q + 2], y[ft][4 * q + 3]);
-      if (h == 0) a.slab_cs[srow] = csum;
-    }
+    const int lrow = wave * 32 + r;
+    qde_store_group<D>(a, first, (int64_t)grp * QDE3_ITEMS + lrow, qde_slab_row(blockIdx.x, QDE3_ITEMS, lrow), h, y, cs);
   };
 
 #define QDE3_FENCE() __builtin_amdgcn_sched_barrier(0)
@@ -300,14 +260,10 @@ __global__ __launch_bounds__(256, 1) void qde3_kernel(QDeArgs a) {
 // =============================================================================================================
 // host side
 // =============================================================================================================
-bool cql_qde3_supported(int d, int64_t batch) {
-  return d == 256 && batch % 32 == 0;
-}
-
 // rows [0, n_items): `a` prepared by cql_qde_launch (G, T for 128-item groups and 32-state stages; nlse2 = -lse in
 // NATURAL units here)
 int cql_qde3_run(const QDeArgs& a, int d, int grid, hipStream_t s) {
-  if (!cql_qde3_supported(d, a.n_states)) return CQLREC_ERR_INVALID;
+  if (qde_form(d, a.n_states) != QDE_FORM_3) return CQLREC_ERR_INVALID;
   constexpr int smem = QDE3_NBUF * DeCfg<256, 4>::BUF_BYTES;
   hipLaunchKernelGGL((qde3_kernel<256>), dim3(grid), dim3(256), smem, s, a);
   return CQLREC_OK;

@@ -268,8 +268,49 @@ __device__ __forceinline__ void owner_fence() {
 }
 
 
-// qhead_de2.hip: 64 items per wave, one wave per SIMD (d = 64, 128).  `a.nlse2` holds -lse in NATURAL units there.
+// End of a piece (qde_pieces.h), one wave's 32 items: y = the FT accumulators of gradient row `row` (lane's item) and its
+// slab twin `srow` (qde_slab_row of this block), cs = this lane half's column sum.  The piece that holds stage 0 goes to
+// the gradient, scaled (written, or added to what is there); any other unscaled to the slab (rows past n_items: harmless,
+// not read).  No caller of cql_qde_launch passes accumulate != 0 today: that branch, here and in qde_kernel's own store,
+// is reached by no entry point and covered by no test.
+template <int D>
+__device__ __forceinline__ void qde_store_group(const QDeArgs& a, bool first, int64_t row, int64_t srow, int h,
+                                                const f32x16 (&y)[D / 32], float cs) {
+  const float csum = cs + __shfl_xor(cs, 32);
+  if (first) {
+    if (row < a.n_items) {
+      float* dst = a.out + row * D;
+#pragma unroll
+      for (int ft = 0; ft < D / 32; ++ft)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          float4* pd = reinterpret_cast<float4*>(dst + ft * 32 + 8 * q + 4 * h);
+          float4 o;
+          if (a.accumulate) {
+            const float4 old = *pd;
+            o = make_float4(qde_axpy(old.x, a.scale, y[ft][4 * q + 0]), qde_axpy(old.y, a.scale, y[ft][4 * q + 1]),
+                            qde_axpy(old.z, a.scale, y[ft][4 * q + 2]), qde_axpy(old.w, a.scale, y[ft][4 * q + 3]));
+          } else {
+            o = make_float4(a.scale * y[ft][4 * q + 0], a.scale * y[ft][4 * q + 1], a.scale * y[ft][4 * q + 2],
+                            a.scale * y[ft][4 * q + 3]);
+          }
+          *pd = o;
+        }
+      if (h == 0) a.out_cs[row] = a.accumulate ? qde_axpy(a.out_cs[row], a.scale, csum) : a.scale * csum;
+    }
+  } else {
+    float* dst = a.slab + srow * D;
+#pragma unroll
+    for (int ft = 0; ft < D / 32; ++ft)
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+        *reinterpret_cast<float4*>(dst + ft * 32 + 8 * q + 4 * h) =
+            make_float4(y[ft][4 * q + 0], y[ft][4 * q + 1], y[ft][4 * q + 2], y[ft][4 * q + 3]);
+    if (h == 0) a.slab_cs[srow] = csum;
+  }
+}
+
+// qhead_de2.hip: 64 items per wave, one wave per SIMD (d = 128).  `a.nlse2` holds -lse in NATURAL units there.
 int cql_qde2_run(const QDeArgs& a, int d, int grid, hipStream_t s);
 // qhead_de3.hip: 32 items per wave, one wave per SIMD, in-wave pipeline (d = 256).  -lse in NATURAL units as for qde2.
-bool cql_qde3_supported(int d, int64_t batch);
 int cql_qde3_run(const QDeArgs& a, int d, int grid, hipStream_t s);

@@ -1,6 +1,7 @@
 // Internal interface of the streaming Q-head skeleton (shared by qhead.hip and topk.hip).
 #pragma once
 #include "common.h"
+#include "qde_pieces.h"
 
 #define QM_LSE 1
 #define QM_ARGMAX 2

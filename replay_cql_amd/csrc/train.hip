@@ -5,7 +5,7 @@
 #include <math.h>
 #include <stdlib.h>
 #include <optional>
-#include "common.h"
+#include "adam_math.h"
 #include "qhead_internal.h"
 #include "step_streams.h"
 

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../include/cqlrec.h"
+#include "../../replay_cql_amd/csrc/qde_pieces.h"
 
 static int fails = 0;
 #define EXPECT(cond)                                                         \
@@ -130,7 +131,67 @@ static void threads() {
   for (auto& x : th) x.join();
 }
 
-int main() {
+// csrc/qde_pieces.h (the cut of the item-side backward) against a direct enumeration of block starts: a block contributes a
+// slab piece to group g iff its start lies strictly inside (g T, (g + 1) T) and its range is not empty.  nblk > W is
+// included, so empty ranges occur.  Both index widths of the iteration, in block order; any_cut(); the block prologue.
+static void qde_pieces_brute_force() {
+  for (int32_t G = 1; G <= 12; ++G)
+    for (int32_t T = 1; T <= 9; ++T)
+      for (int32_t nblk = 1; nblk <= 40; ++nblk) {
+        const QdePieces pc = {G, T, nblk};
+        const int64_t W = (int64_t)G * T;
+        std::vector<int64_t> start(nblk + 1);
+        for (int64_t p = 0; p <= nblk; ++p) start[p] = p * W / nblk;
+        EXPECT(pc.W() == W && start[0] == 0 && start[nblk] == W);
+        bool cut = false, any_piece = false;
+        int64_t covered = 0;
+        for (int64_t p = 0; p < nblk; ++p) {
+          EXPECT(pc.start(p) == start[p] && pc.empty(p) == (start[p + 1] == start[p]));
+          const QdePieces::Range rg = pc.range(p);
+          EXPECT(rg.u0 == start[p] && rg.nst == start[p + 1] - start[p] && rg.u0 == covered);
+          covered += rg.nst;
+          if (rg.nst > 0) {
+            const QdePieces::Unit u = pc.unit(rg.u0);
+            EXPECT(u.t >= 0 && u.t < T && (int64_t)u.g * T + u.t == rg.u0);
+          }
+          if (p > 0 && start[p] % T != 0) cut = true;
+        }
+        EXPECT(covered == W);
+        for (int32_t g = 0; g < G; ++g) {
+          std::vector<int64_t> want, got64, got32;
+          for (int64_t p = 0; p < nblk; ++p)
+            if (start[p] > (int64_t)g * T && start[p] < ((int64_t)g + 1) * T && start[p + 1] != start[p]) want.push_back(p);
+          QDE_FOR_SLAB_PIECES(int64_t, int64_t, pc, (int64_t)g, p) got64.push_back(p);
+          QDE_FOR_SLAB_PIECES(uint32_t, uint64_t, pc, (uint32_t)g, p) got32.push_back(p);
+          EXPECT(got64 == want && got32 == want);
+          any_piece = any_piece || !want.empty();
+        }
+        EXPECT(pc.any_cut() == cut && cut == any_piece);
+      }
+  EXPECT(qde_slab_row(3, 256, 17) == 3 * 256 + 17);
+  // product, then sum: (1 + 2^-12)^2 rounds to 1 + 2^-11 (a tie, to even), so the sum is 0; an fma would leave 2^-24
+  const float a = 1.0f + 0x1p-12f;
+  EXPECT(qde_axpy(-(1.0f + 0x1p-11f), a, a) == 0.0f && __builtin_fmaf(a, a, -(1.0f + 0x1p-11f)) == 0x1p-24f);
+}
+
+// `host_driver qde_plan B N d n_cu [B N d n_cu ...]`: one line "form G T W grid cut" per shape, for
+// tests/test_step_phase_geometry_cpu.py to hold tests/helpers.qde_geometry to
+static int print_qde_plans(int argc, char** argv) {
+  if ((argc - 2) % 4 != 0) return 2;
+  for (int i = 2; i + 3 < argc; i += 4) {
+    const int d = atoi(argv[i + 2]);
+    const QdePlan pl = qde_plan(atoll(argv[i]), atoll(argv[i + 1]), d, atoi(argv[i + 3]));
+    char form[32];
+    if (pl.form == QDE_FORM_GENERIC) snprintf(form, sizeof form, "qde_kernel<%d>", d);
+    else snprintf(form, sizeof form, "qde%d", pl.form);
+    printf("%s %d %d %lld %d %d\n", form, pl.pc.G, pl.pc.T, (long long)pl.pc.W(), pl.pc.nblk, pl.pc.any_cut() ? 1 : 0);
+  }
+  return 0;
+}
+
+int main(int argc, char** argv) {
+  if (argc > 1 && strcmp(argv[1], "qde_plan") == 0) return print_qde_plans(argc, argv);
+  qde_pieces_brute_force();
   layouts();
   workspace_sizes();
   refused_calls();

@@ -281,8 +281,8 @@ def softmax_grad_rows(hb, lse, E_b, b_out, scale, g_E_out=None, g_b_out=None, dH
 
 def qde_geometry(B, N, d, n_cu=256):
     """(form, G, T, W, grid, cut) of the long item-side backward kernel for a batch of B states, N items, width d -- the
-    arithmetic of de_form2 / de_waves / de_grid / cql_qde_launch (csrc/qhead_de.hip) and cql_qde3_supported
-    (csrc/qhead_de3.hip), restated (tests/test_step_phase_geometry_cpu.py holds it to hand-worked rows).
+    arithmetic of qde_plan and QdePieces::any_cut (csrc/qde_pieces.h), restated (tests/test_step_phase_geometry_cpu.py
+    holds it to hand-worked rows and to that C code itself).
       form   qde2 (d = 128, B % 64 = 0), qde3 (d = 256, B % 32 = 0), else the generic qde_kernel<d>
       G      item groups: 256 items (8 waves x 32), 128 for d = 256 (4 waves)
       T      stages: 64 states, 32 for d = 256;  W = G T stage-units

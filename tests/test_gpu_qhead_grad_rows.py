@@ -61,7 +61,7 @@ def _report(tag, rep):
 
 
 # ---- item side (and the state side of the backward) ---------------------------------------------------------------
-# n_cu = 256; the rows are helpers.qde_geometry's (test_step_phase_geometry_cpu.py).  Item-side form (qhead_de.hip: de_form2, cql_qde3_supported, de_grid; W = G * T stage-units, grid =
+# n_cu = 256; the rows are helpers.qde_geometry's (test_step_phase_geometry_cpu.py).  Item-side form (qde_pieces.h: qde_plan; W = G * T stage-units, grid =
 # min(W, 256), a range starts inside a group ("cut", slab + fix-up) when some p * W / grid is not a multiple of T):
 #   B     N      d    form                               G x T = W        grid  cut
 #   64    5003   128  qde2 (B % 64 = 0)                  20 x 1 = 20      20    no (T = 1)

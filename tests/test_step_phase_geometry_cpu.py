@@ -1,11 +1,13 @@
-"""helpers.qde_geometry -- the restated launch geometry of the long item-side backward kernel (csrc/qhead_de.hip) -- held
-to rows worked out by hand.  The GPU tests assert the form and the cut they claim to exercise against this helper
+"""helpers.qde_geometry -- the restated launch geometry of the long item-side backward kernel (csrc/qde_pieces.h) -- held
+to rows worked out by hand and to the C code itself.  The GPU tests assert the form and the cut they claim to exercise against this helper
 (tests/test_gpu_step_phases.py), and the shape tables in the comments of tests/test_gpu_qhead_grad_rows.py and
 tests/test_gpu_train.py are its rows at 256 CUs.
 
 How a row is worked: groups of 256 items (128 for d = 256), stages of 64 states (32 for d = 256), W = G T stage-units
 dealt to grid = min(W, CUs) blocks; block p starts at unit floor(p W / grid), inside a group iff that is no multiple of T.
 With W <= CUs every block holds one unit, so the kernel cuts as soon as T > 1."""
+import os
+
 import pytest
 
 from helpers import qde_geometry
@@ -45,6 +47,24 @@ ROWS = [
 @pytest.mark.parametrize("args,want", ROWS, ids=[f"B{a[0]}-N{a[1]}-d{a[2]}-cu{a[3]}" for a, _ in ROWS])
 def test_hand_worked_rows(args, want):
     assert qde_geometry(*args) == want
+
+
+def test_helper_agrees_with_the_c_plan_on_every_row():
+    """helpers.qde_geometry against csrc/qde_pieces.h itself -- qde_plan and QdePieces::any_cut, the code cql_qde_launch
+    runs -- through the stand-alone host driver's `qde_plan` mode (tests/asan/host_driver.cpp; nothing is loaded into
+    Python), over every shape and CU count of ROWS"""
+    import subprocess
+    from replay_cql_amd import build as B
+    exe = B.build_asan()
+    argv = [str(x) for args, _ in ROWS for x in args]
+    r = subprocess.run([str(exe), "qde_plan"] + argv, capture_output=True, text=True, timeout=120,
+                       env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0", HIP_VISIBLE_DEVICES=""))
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = r.stdout.split("\n")[:-1]
+    assert len(lines) == len(ROWS)
+    for (args, _), line in zip(ROWS, lines):
+        form, G, T, W, grid, cut = line.split()
+        assert (form, int(G), int(T), int(W), int(grid), bool(int(cut))) == qde_geometry(*args), (args, line)
 
 
 def test_small_shapes_cut_as_soon_as_there_are_two_stages():
