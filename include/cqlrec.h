@@ -1009,6 +1009,32 @@ int cqlrec_admm_compact(const double* C, int64_t n, int64_t n_rows, int64_t* off
                         cqlrec_stream stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * f12  SLIM on the device (SLIM of replay/models/slim.py; DESIGN.md section 3.15 is the normative text).  The rules of
+ * f5 - f11 carry over: integer atomics only, no floating-point atomics, the same input gives the same bytes, arguments
+ * are validated on the host before any HIP call, expressions are evaluated as written (no contraction).
+ * --------------------------------------------------------------------------------------------------------- */
+#define CQLREC_SLIM_MAX_ITEMS 16384 /* the largest n of cqlrec_slim_fit: q of one column (8 n bytes) lives in the LDS */
+
+/* Per target column j in [col_begin, col_end): the minimiser over w >= 0, w_j = 0 of
+ *   1/(2 nu) |x_j - X w|^2 + lambda_ |w|_1 + beta/2 |w|^2,   nu = n_users,
+ * by cyclic coordinate descent on G = X^T X [n][n] (symmetric, as cqlrec_dense_gram writes it; rows are read where the
+ * text says columns).  From w = 0, q = G[:, j]; a sweep visits i = 0 .. n-1 ascending, i != j: d = G_ii + nu * beta; if
+ * d <= 0 the coordinate stays 0; otherwise new = max(0, (q_i + G_ii * w_i) - nu * lambda_) / d, and where new != w_i:
+ * q = q - (new - w_i) * G[i, :], w_i = new.  After every full sweep q is recomputed from w, element by element
+ * ((G_ej - w_k1 G_k1,e) - w_k2 G_k2,e) - ... over the support k ascending, and the certificate is taken from it:
+ *   g_i = ((-q_i) / nu + beta * w_i) + lambda_;  v_i = g_i where w_i > 0, min(g_i, 0) where w_i = 0;  v_j = 0.
+ * The column is done when max |v_i| <= tol * lambda_ or after max_iter sweeps.  A column with G_jj = 0 is all zeros,
+ * without a sweep (sweeps = 0, kkt = 0).
+ * S [n][lds] (row-major): S[i, j] = w_i of column j; only the columns of the range are written, all n rows of them.
+ * sweeps, kkt, updates [n], indexed by j: the number of sweeps, the last max |v_i|, the number of non-zero updates; only
+ * the entries of the range are written.  A column's bytes do not depend on the range or on which workgroup ran it.
+ * No synchronisation. */
+int64_t cqlrec_slim_fit_ws_bytes(int64_t n); /* 0: n out of range (1 .. CQLREC_SLIM_MAX_ITEMS) */
+int cqlrec_slim_fit(const double* G, int64_t ldg, int64_t n, int64_t n_users, double beta, double lambda_, double tol,
+                    int32_t max_iter, int64_t col_begin, int64_t col_end, void* ws, int64_t ws_bytes, double* S, int64_t lds,
+                    int32_t* sweeps, double* kkt, int64_t* updates, cqlrec_stream stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * Measurement hooks (bench.py): when enabled, every launcher brackets its kernel with a pair of HIP events on
  * the stream it launches on; cqlrec_prof_read synchronises those events and returns, per phase, the summed
  * kernel time in ms and the number of launches, then resets the pool.  Not capturable in a hipGraph; off by

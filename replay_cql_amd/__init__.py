@@ -6,7 +6,7 @@ __version__ = "0.1.0"
 
 # the train/test splitters (splitters.py), the filters (filters.py), the Indexer (indexer.py) and the history-based
 # feature processors (history_based_fp.py), the neighbourhood models (neighbour.py), association rules
-# (association_rules.py), ALS (als.py) and ADMM SLIM (admm_slim.py), importable from the package without loading torch until they are asked for
+# (association_rules.py), ALS (als.py), ADMM SLIM (admm_slim.py) and SLIM (slim.py), importable from the package without loading torch until they are asked for
 _SPLITTERS = ("Splitter", "UserSplitter", "DateSplitter", "RandomSplitter", "NewUsersSplitter", "ColdUserRandomSplitter",
               "k_folds")
 _FILTERS = ("filter_by_min_count", "filter_out_low_ratings", "take_num_user_interactions", "take_num_days_of_user_hist",
@@ -14,7 +14,7 @@ _FILTERS = ("filter_by_min_count", "filter_out_low_ratings", "take_num_user_inte
 _FEATURES = ("EmptyFeatureProcessor", "LogStatFeaturesProcessor", "ConditionalPopularityProcessor",
              "HistoryBasedFeaturesProcessor")
 _NEIGHBOUR = ("NeighbourRec", "ItemKNN")
-__all__ = list(_SPLITTERS) + list(_FILTERS) + ["Indexer"] + list(_FEATURES) + list(_NEIGHBOUR) + ["ALSWrap", "AssociationRulesItemRec", "ADMMSLIM"]
+__all__ = list(_SPLITTERS) + list(_FILTERS) + ["Indexer"] + list(_FEATURES) + list(_NEIGHBOUR) + ["ALSWrap", "AssociationRulesItemRec", "ADMMSLIM", "SLIM"]
 
 
 def __getattr__(name):
@@ -36,6 +36,9 @@ def __getattr__(name):
     if name == "ADMMSLIM":
         from . import admm_slim          # pylint: disable=import-outside-toplevel
         return admm_slim.ADMMSLIM
+    if name == "SLIM":
+        from . import slim               # pylint: disable=import-outside-toplevel
+        return slim.SLIM
     if name == "ALSWrap":
         from . import als                # pylint: disable=import-outside-toplevel
         return als.ALSWrap

@@ -89,6 +89,7 @@ ALS_PIECE, ALS_GRAM_BLOCK, ALS_MAX_RANK, ALS_MAX_K = 1024, 4096, 128, 512
 ALS_EXPLICIT, ALS_IMPLICIT = 0, 1
 
 DENSE_GRAM_PIECE, DENSE_BLOCK = 1024, 64
+SLIM_MAX_ITEMS = 16384
 
 # name -> (restype, argtypes); every symbol include/cqlrec.h declares
 SIGNATURES = {
@@ -225,6 +226,8 @@ SIGNATURES = {
     "cqlrec_admm_iteration_ws_bytes": (i64, [i64]),
     "cqlrec_admm_iteration": (i32, [vp, vp, vp, vp, i64, f64, f64, vp, i64, vp, vp]),
     "cqlrec_admm_compact": (i32, [vp, i64, i64, vp, vp, vp, vp]),
+    "cqlrec_slim_fit_ws_bytes": (i64, [i64]),
+    "cqlrec_slim_fit": (i32, [vp, i64, i64, i64, f64, f64, f64, i32, i64, i64, vp, i64, vp, i64, vp, vp, vp, vp]),
     "cqlrec_prof_enable": (i32, [i32]),
     "cqlrec_prof_select": (i32, [C.c_uint32]),
     "cqlrec_debug_marks_enable": (i32, [i32]),

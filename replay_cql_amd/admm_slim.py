@@ -91,7 +91,47 @@ class Dense(P.Feat):
         return off, col, val
 
 
-class ADMMSLIM(NeighbourRec):
+class CsrTable:
+    """The similarity table of a model whose `_sim` is a CSR triple of an n_items x n_items matrix (ADMMSLIM, SLIM), as
+    `NeighbourRec` reads it; listed in front of `NeighbourRec` among the bases."""
+
+    @property
+    def similarity_device(self):
+        """the CSR triple (offsets int64 [n_items + 1], item_idx_two int32 ascending inside a row, similarity float64) on
+        the device -- NOT the padded (ids, values, counts) of the other neighbourhood models: row i holds the non-zeros
+        of row i of the fitted matrix"""
+        return self._fitted()
+
+    def _n_rows(self) -> int:
+        return int(self._fitted()[0].numel()) - 1
+
+    def _csr(self, n_rows: int):
+        """the table with n_rows >= n_items rows; the columns of a row ascend, so one CSR serves both readers"""
+        cache = self.__dict__.setdefault("_csr_cache", {})
+        if n_rows not in cache:
+            off, col, val = self._fitted()
+            if n_rows + 1 > off.numel():
+                off = torch.cat([off, off[-1:].expand(n_rows + 1 - off.numel())])
+            cache.clear()
+            cache[n_rows] = ((off, col, val), (off, col, val))
+        return cache[n_rows]
+
+    @property
+    def similarity(self) -> pd.DataFrame:
+        """[item_idx_one, item_idx_two, similarity]: the non-zeros of the fitted matrix, row-major"""
+        if "_similarity_frame" not in self.__dict__:
+            off, col, val = self._fitted()
+            lens = (off[1:] - off[:-1]).cpu().numpy()
+            self._similarity_frame = pd.DataFrame({"item_idx_one": np.repeat(np.arange(len(lens), dtype=np.int32), lens),
+                                                   "item_idx_two": col.cpu().numpy(), "similarity": val.cpu().numpy()})
+        return self._similarity_frame
+
+    @property
+    def _dataframes(self) -> Dict[str, Any]:
+        return {"similarity": self.similarity}
+
+
+class ADMMSLIM(CsrTable, NeighbourRec):
     """ADMM SLIM: Sparse Recommendations for Many Users (Steck et al., WSDM 2020) -- SLIM's item-to-item weights with the
     zero diagonal as a constraint, found by the alternating direction method of multipliers."""
 
@@ -173,39 +213,3 @@ class ADMMSLIM(NeighbourRec):
         self._sim = D.to_csr(C)
         self.rho, self.rho_sequence, self.n_iterations = rho, rhos, it
         self.residuals = (r_p, r_d, e_p, e_d)
-
-    # -------------------------------------------------------------------------------- the table
-    @property
-    def similarity_device(self):
-        """the CSR triple (offsets int64 [n_items + 1], item_idx_two int32 ascending inside a row, similarity float64) on
-        the device -- NOT the padded (ids, values, counts) of the other neighbourhood models: row i holds the non-zeros
-        of row i of the final C"""
-        return self._fitted()
-
-    def _n_rows(self) -> int:
-        return int(self._fitted()[0].numel()) - 1
-
-    def _csr(self, n_rows: int):
-        """the table with n_rows >= n_items rows; the columns of a row ascend, so one CSR serves both readers"""
-        cache = self.__dict__.setdefault("_csr_cache", {})
-        if n_rows not in cache:
-            off, col, val = self._fitted()
-            if n_rows + 1 > off.numel():
-                off = torch.cat([off, off[-1:].expand(n_rows + 1 - off.numel())])
-            cache.clear()
-            cache[n_rows] = ((off, col, val), (off, col, val))
-        return cache[n_rows]
-
-    @property
-    def similarity(self) -> pd.DataFrame:
-        """[item_idx_one, item_idx_two, similarity]: the non-zeros of C, row-major"""
-        if "_similarity_frame" not in self.__dict__:
-            off, col, val = self._fitted()
-            lens = (off[1:] - off[:-1]).cpu().numpy()
-            self._similarity_frame = pd.DataFrame({"item_idx_one": np.repeat(np.arange(len(lens), dtype=np.int32), lens),
-                                                   "item_idx_two": col.cpu().numpy(), "similarity": val.cpu().numpy()})
-        return self._similarity_frame
-
-    @property
-    def _dataframes(self) -> Dict[str, Any]:
-        return {"similarity": self.similarity}

@@ -15,7 +15,7 @@ PKG = Path(__file__).resolve().parent
 CSRC = PKG / "csrc"
 LIB = PKG / "libcqlrec.so"
 TORCH_LIB = PKG / "libcqlrec_torch.so"      # torch.ops.cqlrec.* registration shim over the C ABI (csrc/torch_ops.cpp)
-SOURCES = ["misc.hip", "qhead.hip", "qhead_de.hip", "qhead_de2.hip", "qhead_de3.hip", "qhead_argmax2.hip", "qhead_fwd2.hip", "qhead_fwd3.hip", "qhead_topk2.hip", "qhead_topk4.hip", "select_common.hip", "segment_common.hip", "topk.hip", "item_knn.hip", "pairs_topk.hip", "gbwd.hip", "prep.hip", "metrics.hip", "split.hip", "prepare.hip", "features.hip", "neighbour.hip", "als.hip", "dense.hip", "step_streams.hip", "train.hip"]
+SOURCES = ["misc.hip", "qhead.hip", "qhead_de.hip", "qhead_de2.hip", "qhead_de3.hip", "qhead_argmax2.hip", "qhead_fwd2.hip", "qhead_fwd3.hip", "qhead_topk2.hip", "qhead_topk4.hip", "select_common.hip", "segment_common.hip", "topk.hip", "item_knn.hip", "pairs_topk.hip", "gbwd.hip", "prep.hip", "metrics.hip", "split.hip", "prepare.hip", "features.hip", "neighbour.hip", "als.hip", "dense.hip", "slim.hip", "step_streams.hip", "train.hip"]
 # misc.hip holds the Adam kernel whose expression order is normative: no fma contraction anywhere in that file
 EXTRA = {
     "misc.hip": ["-ffp-contract=off"],
@@ -46,6 +46,8 @@ EXTRA = {
     "als.hip": ["-ffp-contract=off"],
     # the element-wise chain of an ADMM iteration is evaluated as written; the matrix pipe rounds as it rounds
     "dense.hip": ["-ffp-contract=off", "-mllvm", "-amdgpu-mfma-vgpr-form=1"],
+    # the coordinate update, the refresh of q and the certificate of SLIM are normative in their operation order
+    "slim.hip": ["-ffp-contract=off"],
 }
 ARCH = "gfx950"
 
