@@ -1,10 +1,23 @@
 """The calls into csrc/prepare.hip and csrc/features.hip (sections f6 and f7 of include/cqlrec.h) that filters.py,
-indexer.py, history_based_fp.py and the device-fitted models share."""
+indexer.py, history_based_fp.py and the device-fitted models share; `Feat.view` is the one builder of a CSR view of the
+log."""
 from __future__ import annotations
+
+from typing import Optional
 
 import torch
 
 from ._device import Engine, Ws, _ptr
+
+
+def count_pieces(offsets: torch.Tensor, rows: Optional[torch.Tensor] = None, piece: int = 1024) -> int:
+    """the `n_pieces` argument of the row entry points of csrc/als.hip and csrc/dense.hip (CQLREC_ALS_PIECE and
+    CQLREC_DENSE_GRAM_PIECE are both 1024): the pieces of the (listed) rows longer than one piece"""
+    lens = offsets[1:] - offsets[:-1]
+    if rows is not None:
+        lens = lens[rows.long()]
+    long = lens[lens > piece]
+    return int(((long + piece - 1) // piece).sum().item()) if long.numel() else 0
 
 
 class Prep(Engine):
@@ -78,6 +91,13 @@ class Feat(Prep):
         perm, offsets = self._empty(n, torch.int32), self._empty(n_groups + 1, torch.int64)
         self.call("features_segments", group, key, n, n_groups, Ws(n, n_groups), perm, offsets)
         return perm, offsets
+
+    def view(self, group, n_groups: int, other, weight=None):
+        """A view of the log: its rows ordered by (group, other id, row) as the CSR triple (offsets int64 [n_groups + 1],
+        other id [n], weight [n] or None), and the int32 permutation that orders them"""
+        perm, offsets = self.segments(group, n_groups, other.to(torch.int64))
+        rows = perm.long()
+        return (offsets, other[rows].contiguous(), None if weight is None else weight[rows].contiguous()), perm
 
     def segment_stats(self, perm, offsets, value, n_groups: int):
         """float64 [n_groups, 6]: count, mean, std, quantile_05, quantile_5, quantile_95"""

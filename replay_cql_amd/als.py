@@ -23,20 +23,12 @@ from . import _log as L
 from . import _prepare as P
 from . import data as D
 from ._device import Ws
+from ._prepare import count_pieces
 from .device_recommender import DeviceRecommender
 
 __all__ = ["ALSWrap"]
 
 MAX_RANK, MAX_K, PIECE = 128, 512, 1024
-
-
-def count_pieces(offsets: torch.Tensor, rows: Optional[torch.Tensor] = None, piece: int = PIECE) -> int:
-    """the `n_pieces` argument of the row entry points: the pieces of the (listed) rows longer than one piece"""
-    lens = offsets[1:] - offsets[:-1]
-    if rows is not None:
-        lens = lens[rows.long()]
-    long = lens[lens > piece]
-    return int(((long + piece - 1) // piece).sum().item()) if long.numel() else 0
 
 
 class Als(P.Feat):
@@ -147,12 +139,10 @@ class ALSWrap(DeviceRecommender):
         rel = L.float_column(lg, "relevance")
         if bool(torch.isnan(rel).any()):
             raise ValueError("relevance contains NaN")
-        perm_i, off_i = eng.segments(item, n_items, user.to(torch.int64))
-        perm_u, off_u = eng.segments(user, n_users, item.to(torch.int64))
-        perm_i, perm_u = perm_i.long(), perm_u.long()
-        item_side = (off_i, user[perm_i].contiguous(), rel[perm_i].contiguous())
-        user_side = (off_u, item[perm_u].contiguous(), rel[perm_u].contiguous())
-        np_i, np_u = count_pieces(off_i), count_pieces(off_u)
+        item_side, _ = eng.view(item, n_items, user, rel)
+        user_side, _ = eng.view(user, n_users, item, rel)
+        off_u = user_side[0]
+        np_i, np_u = count_pieces(item_side[0]), count_pieces(off_u)
         r, dev = self.rank, lg.device
         U = self._init_factors(n_users, r, self._seed, dev)
         U = (U * (off_u[1:] > off_u[:-1]).to(torch.float32)[:, None]).contiguous()     # an id without rows has a zero row
@@ -200,8 +190,8 @@ class ALSWrap(DeviceRecommender):
                 users = torch.unique(user.to(torch.int64))
             if filter_seen_items:
                 n_rows = max(n_log_users, U.shape[0])
-                perm, off = eng.segments(user, n_rows, item.to(torch.int64))
-                seen = (off, item[perm.long()].contiguous())
+                (off, seen_items, _), _ = eng.view(user, n_rows, item)
+                seen = (off, seen_items)
         if users is None:
             users = torch.nonzero(has_u).flatten()
         users = users[users < (1 << 31) - 1]

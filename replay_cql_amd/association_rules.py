@@ -14,13 +14,13 @@ NEIGHBOUR_MAX_K + 1 items (k = n_items - 1 must fit the engine's limit; beyond i
 Nothing here has a CPU path: without a GPU every call that computes raises CqlrecError."""
 from __future__ import annotations
 
-from typing import Any, Dict, List, Optional
+from typing import List, Optional
 
-import numpy as np
 import pandas as pd
 import torch
 
 from ._log import dense_ids, float_column
+from ._similarity import Padded
 from .neighbour import DEFAULT_MAX_TUPLES, Neigh, NeighbourRec
 
 __all__ = ["AssociationRulesItemRec"]
@@ -40,7 +40,6 @@ class AssociationRulesItemRec(NeighbourRec):
         "use_relevance": {"type": "categorical", "args": [True, False]},
         "similarity_metric": {"type": "categorical", "args": ["confidence", "lift"]},
     }
-    _PLANES = {"confidence": 1, "lift": 2, "confidence_gain": 3}
 
     # pylint: disable=too-many-arguments
     def __init__(self, session_col: Optional[str] = None, min_item_count: int = 5, min_pair_count: int = 5,
@@ -98,52 +97,24 @@ class AssociationRulesItemRec(NeighbourRec):
         rows = N.compact((item_count[item.long()] >= int(self.min_item_count)).to(torch.uint8))
         session, item, w = session[rows].contiguous(), item[rows].contiguous(), w[rows].contiguous()
         if rows.numel():
-            perm_i, off_i = N.segments(item, n_items, session.to(torch.int64))
-            perm_s, off_s = N.segments(session, n_sessions, item.to(torch.int64))
-            perm_i, perm_s = perm_i.long(), perm_s.long()
+            L, _ = N.view(item, n_items, session, w)
+            R, _ = N.view(session, n_sessions, item, w)
         else:                                                                # no row left: an empty product
-            perm_i = perm_s = rows
-            off_i = torch.zeros(n_items + 1, dtype=torch.int64, device=lg.device)
-            off_s = torch.zeros(n_sessions + 1, dtype=torch.int64, device=lg.device)
-        L = (off_i, session[perm_i].contiguous(), w[perm_i].contiguous())
-        R = (off_s, item[perm_s].contiguous(), w[perm_s].contiguous())
+            L = (torch.zeros(n_items + 1, dtype=torch.int64, device=lg.device), session, w)
+            R = (torch.zeros(n_sessions + 1, dtype=torch.int64, device=lg.device), item, w)
         self._clear_cache()
-        *table, item_rel = N.rules_topk(L, R, n_sessions, k, self.max_tuples, num_sessions, int(self.min_pair_count))
-        self._sim = tuple(table)
+        ids, conf, lift, gain, count, item_rel = N.rules_topk(L, R, n_sessions, k, self.max_tuples, num_sessions,
+                                                              int(self.min_pair_count))
+        # row a holds the consequents of item a, largest lift first
+        self._sim = Padded(ids, {"confidence": conf, "lift": lift, "confidence_gain": gain}, count)
         self.num_sessions, self.item_count, self.item_relevance = num_sessions, item_count, item_rel
         self.expansion, self.row_prefix = N.expansion, N.row_prefix        # the host row prefix: where the chunks were cut
 
     # -------------------------------------------------------------------------------- the table
     @property
-    def similarity_device(self):
-        """(ids int32 [n_items, K] padded with -1, confidence, lift, confidence_gain float64 [n_items, K], counts int32
-        [n_items]) on the device; row a holds the consequents of item a, largest lift first"""
-        return self._fitted()
-
-    def _table(self):
-        t = self._fitted()
-        return t[0], t[self._PLANES[self._similarity_metric]], t[4]
-
-    @property
-    def similarity(self) -> pd.DataFrame:
-        """[item_idx_one, item_idx_two, confidence, lift, confidence_gain], by item_idx_one ascending, then rank"""
-        if "_similarity_frame" not in self.__dict__:
-            ids, conf, lift, gain, count = self._fitted()
-            keep = self._first(ids, count).cpu().numpy()
-            one = np.broadcast_to(np.arange(ids.shape[0], dtype=np.int32)[:, None], keep.shape)[keep]
-            self._similarity_frame = pd.DataFrame({"item_idx_one": one, "item_idx_two": ids.cpu().numpy()[keep],
-                                                   "confidence": conf.cpu().numpy()[keep], "lift": lift.cpu().numpy()[keep],
-                                                   "confidence_gain": gain.cpu().numpy()[keep]})
-        return self._similarity_frame
-
-    @property
     def get_similarity(self) -> pd.DataFrame:
         """the measures calculated during `fit`"""
         return self.similarity
-
-    @property
-    def _dataframes(self) -> Dict[str, Any]:
-        return {"similarity": self.similarity}
 
     # -------------------------------------------------------------------------------- item to item
     def get_nearest_items(self, items, k: int, metric: str = "lift", candidates=None):
@@ -152,11 +123,3 @@ class AssociationRulesItemRec(NeighbourRec):
         if metric not in self.item_to_item_metrics:
             raise ValueError(f"Select one of the valid distance metrics: {self.item_to_item_metrics}")
         return self._get_nearest_items_wrap(items=items, k=k, metric=metric, candidates=candidates)
-
-    def _get_nearest_items(self, items: pd.DataFrame, metric: Optional[str] = None,
-                           candidates: Optional[pd.DataFrame] = None) -> pd.DataFrame:
-        sim = self.similarity
-        sim = sim[sim["item_idx_one"].isin(items["item_idx"])]
-        if candidates is not None:
-            sim = sim[sim["item_idx_two"].isin(candidates["item_idx"])]
-        return sim[["item_idx_one", "item_idx_two", metric]]

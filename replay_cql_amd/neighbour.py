@@ -22,6 +22,7 @@ import torch
 from . import _prepare as P
 from ._device import Ws
 from ._log import dense_ids, float_column, normalise, open_log
+from ._similarity import Padded
 from .device_recommender import DeviceRecommender
 
 __all__ = ["NeighbourRec", "ItemKNN"]
@@ -168,29 +169,20 @@ class NeighbourRec(DeviceRecommender):
     # -------------------------------------------------------------------------------- the table
     @property
     def similarity_device(self):
-        """(ids int32 [n_items, K] padded with -1, values float64 [n_items, K], counts int32 [n_items]) on the device;
-        row i holds the neighbours of item i, best first"""
+        """the fitted table on the device, a tuple of tensors in one of the two formats of `_similarity`: `Padded` (ids,
+        a value plane per measure, counts) or `Csr` (offsets, columns, values)"""
         return self._fitted()
 
     @property
     def similarity(self) -> pd.DataFrame:
-        """[item_idx_one, item_idx_two, similarity], by item_idx_one ascending, then rank"""
+        """[item_idx_one, item_idx_two, a column per measure], by item_idx_one ascending, then in the table's order"""
         if "_similarity_frame" not in self.__dict__:
-            ids, vals, count = self._fitted()
-            keep = self._first(ids, count).cpu().numpy()
-            one = np.broadcast_to(np.arange(ids.shape[0], dtype=np.int32)[:, None], keep.shape)[keep]
-            self._similarity_frame = pd.DataFrame({"item_idx_one": one, "item_idx_two": ids.cpu().numpy()[keep],
-                                                   "similarity": vals.cpu().numpy()[keep]})
+            self._similarity_frame = self._fitted().frame()
         return self._similarity_frame
 
     def _n_rows(self) -> int:
         """the number of rows of the fitted table: one per item id below the largest fitted one + 1"""
-        return int(self._fitted()[0].shape[0])
-
-    def _table(self):
-        """(ids, the value plane that `similarity_metric` names, count): what predict reads.  A model with one plane
-        holds exactly this; one with several (AssociationRulesItemRec) picks here."""
-        return self._fitted()
+        return self._fitted().n_rows
 
     def _csr(self, n_rows: int):
         """the table as CSR with n_rows >= n_items rows: (offsets, columns, values) in rank order, and sorted by column;
@@ -198,16 +190,8 @@ class NeighbourRec(DeviceRecommender):
         cache = self.__dict__.setdefault("_csr_cache", {})
         key = (n_rows, self._similarity_metric)
         if key not in cache:
-            ids, vals, count = self._table()
-            off = torch.zeros(n_rows + 1, dtype=torch.int64, device=ids.device)
-            off[1:ids.shape[0] + 1] = torch.cumsum(count.to(torch.int64), 0)
-            off[ids.shape[0] + 1:] = off[ids.shape[0]]
-            keep = self._first(ids, count)
-            col, val = ids[keep].contiguous(), vals[keep].contiguous()
-            row = torch.arange(ids.shape[0], device=ids.device, dtype=torch.int64)[:, None].expand_as(ids)[keep]
-            by_col = torch.argsort(row * max(1, ids.shape[0]) + col.to(torch.int64))
             cache.clear()
-            cache[key] = ((off, col, val), (off, col[by_col].contiguous(), val[by_col].contiguous()))
+            cache[key] = self._fitted().csr(n_rows, self._similarity_metric)
         return cache[key]
 
     # -------------------------------------------------------------------------------- predict on the device
@@ -215,8 +199,8 @@ class NeighbourRec(DeviceRecommender):
         """(engine, users' CSR offsets, items of the rows ordered by (user, item, row), n_users, largest item + 1)"""
         (user, n_users), (item, n_items) = dense_ids(lg, ["user_idx", "item_idx"])
         eng = Neigh(lg.device)
-        perm, off = eng.segments(user, n_users, item.to(torch.int64))
-        return eng, off, item[perm.long()].contiguous(), n_users, n_items
+        (off, h_item, _), _ = eng.view(user, n_users, item)
+        return eng, off, h_item, n_users, n_items
 
     def _recommend(self, log, k: int, users, items, filter_seen_items: bool):
         """(users int64 [m], ids int32 [m, k], vals float64 [m, k], count int32 [m]) on the device"""
@@ -283,7 +267,7 @@ class NeighbourRec(DeviceRecommender):
         sim = sim[sim["item_idx_one"].isin(items["item_idx"])]
         if candidates is not None:
             sim = sim[sim["item_idx_two"].isin(candidates["item_idx"])]
-        return sim[["item_idx_one", "item_idx_two", "similarity"]]
+        return sim[["item_idx_one", "item_idx_two", metric or "similarity"]]
 
 
 class ItemKNN(NeighbourRec):
@@ -332,13 +316,11 @@ class ItemKNN(NeighbourRec):
         ucount, icount = N.count(user, n_users), N.count(item, n_items)
         distinct = int((icount > 0).sum().item())
         w = N.weights(user, item, rel, ucount, icount, distinct, self.weighting, self.bm25_k1, self.bm25_b)
-        perm_i, off_i = N.segments(item, n_items, user.to(torch.int64))
-        perm_u, off_u = N.segments(user, n_users, item.to(torch.int64))
-        norm = N.norms(perm_i, off_i, w, n_items)
-        perm_i, perm_u = perm_i.long(), perm_u.long()
-        L = (off_i, user[perm_i].contiguous(), w[perm_i].contiguous())
-        R = (off_u, item[perm_u].contiguous(), w[perm_u].contiguous())
+        L, perm_i = N.view(item, n_items, user, w)
+        R, _ = N.view(user, n_users, item, w)
+        norm = N.norms(perm_i, L[0], w, n_items)
         self._clear_cache()
-        self._sim = N.topk(N.N.NEIGHBOUR_FIT, L, R, n_users, n_items, k, self.max_tuples, norm_q=norm, norm_j=norm,
-                           shrink=float(self.shrink))
+        ids, vals, count = N.topk(N.N.NEIGHBOUR_FIT, L, R, n_users, n_items, k, self.max_tuples, norm_q=norm, norm_j=norm,
+                                  shrink=float(self.shrink))
+        self._sim = Padded(ids, {"similarity": vals}, count)
         self.row_weights, self.item_norms, self.expansion = w, norm, N.expansion

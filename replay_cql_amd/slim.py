@@ -23,15 +23,15 @@ from typing import Optional
 
 import torch
 
+from ._dense import Dense
 from ._device import Ws
-from ._log import dense_ids, float_column, has_column
-from .admm_slim import CsrTable, Dense
+from ._similarity import Csr
 from .neighbour import NeighbourRec
 
 __all__ = ["SLIM"]
 
 
-class SLIM(CsrTable, NeighbourRec):
+class SLIM(NeighbourRec):
     """SLIM: Sparse Linear Methods for Top-N Recommender Systems (Ning and Karypis, ICDM 2011)."""
 
     tol: float = 1.0e-4            # a column is done at certificate <= tol * lambda_ (not sklearn's dual-gap rule)
@@ -69,25 +69,12 @@ class SLIM(CsrTable, NeighbourRec):
 
     def _fit_device(self, lg) -> None:
         D = Dense(lg.device)
-        (user, n_users), (item, n_items) = dense_ids(lg, ["user_idx", "item_idx"])
-        if has_column(lg.src, "relevance"):
-            rel = float_column(lg, "relevance")
-            if not bool(torch.isfinite(rel).all()):
-                raise ValueError("relevance contains NaN or an infinite value")
-        else:
-            rel = torch.ones(user.numel(), dtype=torch.float64, device=lg.device)
-        n = int(n_items)
-        if D.ws_bytes("slim_fit", n) == 0:
-            raise ValueError(f"SLIM holds a dense n_items x n_items matrix and one column in the LDS: {n} items are out of range")
-        perm_i, off_i = D.segments(item, n_items, user.to(torch.int64))
-        perm_u, off_u = D.segments(user, n_users, item.to(torch.int64))
-        perm_i, perm_u = perm_i.long(), perm_u.long()
-        G = D.gram((off_i, user[perm_i].contiguous(), rel[perm_i].contiguous()),
-                   (off_u, item[perm_u].contiguous(), rel[perm_u].contiguous()), n, n_users)
-        S, sweeps, kkt, updates = self.solve(D, G, int(n_users))
+        G, n, n_users = D.log_gram(lg, "slim_fit", "SLIM holds a dense n_items x n_items matrix and one column in the LDS: "
+                                   "{n} items are out of range")
+        S, sweeps, kkt, updates = self.solve(D, G, n_users)
         del G
         self._clear_cache()
-        self._sim = D.to_csr(S)
+        self._sim = Csr(*D.to_csr(S))
         self.n_sweeps, self.kkt = sweeps, kkt
         self.n_updates = int(updates.sum().item())
         self.n_not_converged = int((kkt > float(self.tol) * float(self.lambda_)).sum().item())

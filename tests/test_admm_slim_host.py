@@ -15,6 +15,7 @@ import torch
 
 import replay_cql_amd
 from replay_cql_amd import _native as N
+from replay_cql_amd import _similarity as SIM
 from replay_cql_amd import admm_slim as AS
 from replay_cql_amd import build as B
 from replay_cql_amd import neighbour as NB
@@ -68,8 +69,8 @@ def test_the_csr_table_serves_the_base_class():
         m.similarity_device
     with pytest.raises(RuntimeError, match="not fitted"):
         m.recommend(frame(), 1)
-    m._sim = (torch.tensor([0, 1, 3, 3], dtype=torch.int64), torch.tensor([2, 0, 1], dtype=torch.int32),
-              torch.tensor([0.5, -0.25, 1.5], dtype=torch.float64))
+    m._sim = SIM.Csr(torch.tensor([0, 1, 3, 3], dtype=torch.int64), torch.tensor([2, 0, 1], dtype=torch.int32),
+                     torch.tensor([0.5, -0.25, 1.5], dtype=torch.float64))
     assert m._n_rows() == 3 and len(m.similarity_device) == 3
     sim = m.similarity
     assert sim.to_dict("list") == {"item_idx_one": [0, 1, 1], "item_idx_two": [2, 0, 1], "similarity": [0.5, -0.25, 1.5]}
@@ -84,7 +85,8 @@ def test_the_csr_table_serves_the_base_class():
     m._clear_cache()
     assert "_csr_cache" not in m.__dict__ and "_similarity_frame" not in m.__dict__
     knn = NB.ItemKNN()                                   # the padded table of the other models counts its rows as before
-    knn._sim = (torch.zeros((4, 2), dtype=torch.int32), torch.zeros((4, 2), dtype=torch.float64), torch.zeros(4, dtype=torch.int32))
+    knn._sim = SIM.Padded(torch.zeros((4, 2), dtype=torch.int32), {"similarity": torch.zeros((4, 2), dtype=torch.float64)},
+                          torch.zeros(4, dtype=torch.int32))
     assert knn._n_rows() == 4
 
 
@@ -96,7 +98,7 @@ def test_the_model_refuses_to_run_without_gpu():
     with pytest.raises(N.CqlrecError, match="no CPU path"):
         AS.ADMMSLIM().fit({"user_idx": torch.tensor([0, 1]), "item_idx": torch.tensor([0, 1])})
     m = AS.ADMMSLIM()
-    m._sim = (torch.zeros(3, dtype=torch.int64), torch.zeros(0, dtype=torch.int32), torch.zeros(0, dtype=torch.float64))
+    m._sim = SIM.Csr(torch.zeros(3, dtype=torch.int64), torch.zeros(0, dtype=torch.int32), torch.zeros(0, dtype=torch.float64))
     with pytest.raises(N.CqlrecError, match="no CPU path"):
         m.recommend(frame(), 1)
     with pytest.raises(N.CqlrecError, match="no CPU path"):

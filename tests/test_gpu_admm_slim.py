@@ -23,7 +23,8 @@ import torch
 import admm_slim_reference as AR
 import neighbour_reference as NR
 from replay_cql_amd import _native as N
-from replay_cql_amd.admm_slim import ADMMSLIM, Dense
+from replay_cql_amd._dense import Dense
+from replay_cql_amd.admm_slim import ADMMSLIM
 
 pytestmark = pytest.mark.gpu
 

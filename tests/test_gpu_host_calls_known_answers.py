@@ -3,8 +3,9 @@ sequence of native calls it makes (entry point, every argument rendered by its d
 a pointer as null / non-null, an integer as its value, a float as float.hex, anything else as its ctypes type's name)
 and a SHA-256 of what it returns, on one fixed log in each form the API takes (pandas, pyarrow, a dict of device
 tensors).  tests/golden/host_calls_known_answers.json holds both as the tree recorded them before the host layer was
-given one home; these paths are deterministic (sections 3.4-3.10), so a refactor of the host
-code must reproduce every trace and every digest.
+given one home, and the scenarios of the rules, ADMMSLIM and SLIM as it recorded them before those
+models were given one view builder and one table type per format; these paths are deterministic (sections 3.4-3.10 and
+3.13-3.15), so a refactor of the host code must reproduce every trace and every digest.
 
 Only the public API is used, so the file runs unchanged on any checkout:
     python tests/test_gpu_host_calls_known_answers.py --record OUT.json"""
@@ -154,9 +155,12 @@ def scenarios():
     from replay_cql_amd import history_based_fp as H
     from replay_cql_amd import metrics as M
     from replay_cql_amd import splitters as S
+    from replay_cql_amd.admm_slim import ADMMSLIM
     from replay_cql_amd.als import ALSWrap
+    from replay_cql_amd.association_rules import AssociationRulesItemRec
     from replay_cql_amd.indexer import Indexer
     from replay_cql_amd.neighbour import ItemKNN
+    from replay_cql_amd.slim import SLIM
 
     out = {}
     log_pd = as_form(LOG, "pandas")
@@ -229,6 +233,33 @@ def scenarios():
                     m.predict_pairs(pairs, log_pd), m.get_nearest_items([0, 1, 2, 11], 3)]
         return res
 
+    def item_to_item(m, form, extra, nearest):
+        """what every neighbourhood model of the three newer ones is digested by; `extra` names fit's own attributes"""
+        m.fit(as_form(LOG, form))
+        res = [m.similarity_device, m.similarity, m.recommend(as_form(LOG, form), 5),
+               m.recommend(as_form(LOG, form), 5, users=[0, 3, 17, 39], items=subset, filter_seen_items=False)]
+        res += [getattr(m, name) for name in extra]
+        if form == "pandas":
+            res += [m.predict(log_pd, 5), m.predict_pairs(pairs, log_pd), m.get_nearest_items([0, 1, 2, 11], 3, **nearest)]
+        return m, res
+
+    def rules(form, **kw):
+        m, res = item_to_item(AssociationRulesItemRec(**kw), form, (), {"metric": "confidence_gain"})
+        if form == "pandas":
+            m.similarity_metric = "confidence"                # the cached CSR has to follow the metric
+            res.append(m.predict(log_pd, 5))
+        return res
+
+    rules_a = {"num_neighbours": 5}
+    rules_b = {"min_item_count": 1, "min_pair_count": 1, "num_neighbours": None, "use_relevance": True,
+               "similarity_metric": "lift"}                   # None: k = 29, the all-pairs path
+
+    def admm_slim(form):
+        return item_to_item(ADMMSLIM(lambda_1=5, lambda_2=50, seed=7), form, ("rho_sequence", "n_iterations"), {})[1]
+
+    def slim(form):
+        return item_to_item(SLIM(beta=50, lambda_=100), form, ("n_sweeps", "kkt", "n_updates", "n_not_converged"), {})[1]
+
     def als(form, implicit):
         m = ALSWrap(rank=4, implicit_prefs=implicit, seed=1, max_iter=2)
         m.fit(as_form(LOG, form))
@@ -283,7 +314,12 @@ def scenarios():
             out[f"item_knn.{w}[{form}]"] = lambda form=form, w=w: item_knn(form, w)
         for implicit in (True, False):
             out[f"als.{'implicit' if implicit else 'explicit'}[{form}]"] = lambda form=form, i=implicit: als(form, i)
+        out[f"rules.a[{form}]"] = lambda form=form: rules(form, **rules_a)
+        out[f"rules.b[{form}]"] = lambda form=form: rules(form, **rules_b)
+        out[f"admm_slim[{form}]"] = lambda form=form: admm_slim(form)
+        out[f"slim[{form}]"] = lambda form=form: slim(form)
     out["item_knn.chunked[device]"] = lambda: item_knn("device", None, max_tuples=500)
+    out["rules.chunked[device]"] = lambda: rules("device", max_tuples=500, **rules_a)
     out["build_csr[host]"] = lambda: build_csr("host")
     out["build_csr[device]"] = lambda: build_csr("device")
     out["core"] = core

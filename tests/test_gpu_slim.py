@@ -21,7 +21,8 @@ import torch
 import neighbour_reference as NR
 import slim_reference as SR
 from replay_cql_amd import _native as N
-from replay_cql_amd.admm_slim import ADMMSLIM, Dense
+from replay_cql_amd._dense import Dense
+from replay_cql_amd.admm_slim import ADMMSLIM
 from replay_cql_amd.slim import SLIM
 
 pytestmark = pytest.mark.gpu

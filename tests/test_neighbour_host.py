@@ -15,6 +15,7 @@ import torch
 import replay_cql_amd
 from replay_cql_amd import _native as N
 from replay_cql_amd import build as B
+from replay_cql_amd import _similarity as SIM
 from replay_cql_amd import neighbour as NB
 
 ROOT = Path(__file__).resolve().parents[1]
@@ -85,7 +86,8 @@ def test_unfitted_and_logless_calls_raise():
     with pytest.raises(RuntimeError, match="not fitted"):
         m.recommend(frame(), 1)
     m._clear_cache()                                        # nothing to drop yet
-    m._sim = (torch.zeros((2, 1), dtype=torch.int32), torch.zeros((2, 1), dtype=torch.float64), torch.zeros(2, dtype=torch.int32))
+    m._sim = SIM.Padded(torch.zeros((2, 1), dtype=torch.int32), {"similarity": torch.zeros((2, 1), dtype=torch.float64)},
+                        torch.zeros(2, dtype=torch.int32))
     with pytest.raises(ValueError, match="^log is not provided, but it is required for prediction$"):
         m.recommend(None, 1)
     with pytest.raises(ValueError, match="^log is not provided, but it is required for prediction$"):

@@ -14,6 +14,7 @@ import torch
 
 import replay_cql_amd
 from replay_cql_amd import _native as N
+from replay_cql_amd import _similarity as SIM
 from replay_cql_amd import association_rules as AR
 from replay_cql_amd import build as B
 from replay_cql_amd import neighbour as NB
@@ -88,7 +89,7 @@ def test_the_metric_picks_the_plane_and_the_csr_cache_follows():
         m.similarity_device
     ids = torch.tensor([[1, -1], [0, 2], [1, -1]], dtype=torch.int32)
     planes = [torch.tensor([[x, 0.0], [x + 1, x + 2], [x + 3, 0.0]], dtype=torch.float64) for x in (10.0, 20.0, 30.0)]
-    m._sim = (ids, *planes, torch.tensor([1, 2, 1], dtype=torch.int32))
+    m._sim = SIM.Padded(ids, dict(zip(("confidence", "lift", "confidence_gain"), planes)), torch.tensor([1, 2, 1], dtype=torch.int32))
     assert len(m.similarity_device) == 5
     assert list(m.similarity.columns) == ["item_idx_one", "item_idx_two", "confidence", "lift", "confidence_gain"]
     assert m.similarity["item_idx_one"].tolist() == [0, 1, 1, 2] and m.similarity["item_idx_two"].tolist() == [1, 0, 2, 1]
@@ -96,7 +97,7 @@ def test_the_metric_picks_the_plane_and_the_csr_cache_follows():
     assert m.get_similarity is m.similarity and m._dataframes["similarity"] is m.similarity
     for metric, base in (("confidence", 10.0), ("lift", 20.0), ("confidence_gain", 30.0), ("confidence", 10.0)):
         m.similarity_metric = metric
-        assert m._table()[1] is planes[("confidence", "lift", "confidence_gain").index(metric)]
+        assert m._sim.plane(m.similarity_metric) is planes[("confidence", "lift", "confidence_gain").index(metric)]
         (off, col, val), (_, col_sorted, val_sorted) = m._csr(4)
         assert off.tolist() == [0, 1, 3, 4, 4] and col.tolist() == [1, 0, 2, 1]
         assert val.tolist() == [base, base + 1, base + 2, base + 3] == val_sorted.tolist()
@@ -119,8 +120,8 @@ def test_the_model_refuses_to_run_without_gpu():
     with pytest.raises(N.CqlrecError, match="no CPU path"):
         AR.AssociationRulesItemRec().fit({"user_idx": torch.tensor([0, 1]), "item_idx": torch.tensor([0, 1])})
     m = AR.AssociationRulesItemRec()
-    m._sim = tuple(torch.zeros((2, 1), dtype=dt) for dt in (torch.int32, torch.float64, torch.float64, torch.float64)) + \
-        (torch.zeros(2, dtype=torch.int32),)
+    m._sim = SIM.Padded(torch.zeros((2, 1), dtype=torch.int32),
+                        {name: torch.zeros((2, 1), dtype=torch.float64) for name in ("confidence", "lift", "confidence_gain")}, torch.zeros(2, dtype=torch.int32))
     with pytest.raises(N.CqlrecError, match="no CPU path"):
         m.recommend(frame(), 1)
     with pytest.raises(N.CqlrecError, match="no CPU path"):

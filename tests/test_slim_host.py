@@ -15,7 +15,9 @@ import torch
 
 import replay_cql_amd
 from replay_cql_amd import _native as N
+from replay_cql_amd import _similarity as SIM
 from replay_cql_amd import admm_slim as AS
+from replay_cql_amd import association_rules as AR
 from replay_cql_amd import build as B
 from replay_cql_amd import neighbour as NB
 from replay_cql_amd import slim as SL
@@ -39,8 +41,10 @@ def frame():
 def test_package_exports_the_model():
     assert SL.__all__ == ["SLIM"]
     assert replay_cql_amd.SLIM is SL.SLIM and "SLIM" in replay_cql_amd.__all__
-    assert issubclass(SL.SLIM, NB.NeighbourRec) and issubclass(SL.SLIM, AS.CsrTable)
-    assert issubclass(AS.ADMMSLIM, AS.CsrTable) and AS.ADMMSLIM.similarity is AS.CsrTable.similarity is SL.SLIM.similarity
+    for model in (NB.ItemKNN, AR.AssociationRulesItemRec, AS.ADMMSLIM, SL.SLIM):     # one implementation: NeighbourRec's
+        assert model.__mro__[1] is NB.NeighbourRec
+        for name in ("similarity", "similarity_device", "_csr", "_n_rows", "_dataframes"):
+            assert name not in vars(model) and getattr(model, name) is getattr(NB.NeighbourRec, name), (model, name)
 
 
 def test_constructor_arguments_attributes_and_errors():
@@ -71,8 +75,8 @@ def test_the_csr_table_serves_the_base_class():
         m.similarity_device
     with pytest.raises(RuntimeError, match="not fitted"):
         m.recommend(frame(), 1)
-    m._sim = (torch.tensor([0, 1, 3, 3], dtype=torch.int64), torch.tensor([2, 0, 1], dtype=torch.int32),
-              torch.tensor([0.5, 0.25, 1.5], dtype=torch.float64))
+    m._sim = SIM.Csr(torch.tensor([0, 1, 3, 3], dtype=torch.int64), torch.tensor([2, 0, 1], dtype=torch.int32),
+                     torch.tensor([0.5, 0.25, 1.5], dtype=torch.float64))
     assert m._n_rows() == 3 and len(m.similarity_device) == 3
     sim = m.similarity
     assert sim.to_dict("list") == {"item_idx_one": [0, 1, 1], "item_idx_two": [2, 0, 1], "similarity": [0.5, 0.25, 1.5]}
@@ -95,7 +99,7 @@ def test_the_model_refuses_to_run_without_gpu():
     with pytest.raises(N.CqlrecError, match="no CPU path"):
         SL.SLIM().fit({"user_idx": torch.tensor([0, 1]), "item_idx": torch.tensor([0, 1])})
     m = SL.SLIM()
-    m._sim = (torch.zeros(3, dtype=torch.int64), torch.zeros(0, dtype=torch.int32), torch.zeros(0, dtype=torch.float64))
+    m._sim = SIM.Csr(torch.zeros(3, dtype=torch.int64), torch.zeros(0, dtype=torch.int32), torch.zeros(0, dtype=torch.float64))
     with pytest.raises(N.CqlrecError, match="no CPU path"):
         m.recommend(frame(), 1)
     with pytest.raises(N.CqlrecError, match="no CPU path"):

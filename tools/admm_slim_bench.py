@@ -8,7 +8,7 @@ synchronise), with the spread (max - min):
   gemm n               cqlrec_dense_gemm_f64 on two random n x n matrices, beside torch.matmul in fp64 on the same matrices in
                        the same process, the two sides alternating call by call; TFLOP/s = 2 n^3 / time, beside the 78.6
                        TFLOP/s of the fp64 VECTOR peak (nobody has published the matrix figure of this chip)
-  per item count n     the cfg3 log (tools/split_bench.make_log: 1 M users, 100 000 items, about 48 M rows) cut to its n most
+  per item count n     the cfg3 log (tools/bench_record.make_log: 1 M users, 100 000 items, about 48 M rows) cut to its n most
                        frequent items with the package's own filter_by_min_count and Indexer; then
                        ADMMSLIM().fit (the defaults lambda_1 = 5, lambda_2 = 5000, seed 0), with its iteration count;
                        one cqlrec_admm_iteration alone on the fitted W and P; cqlrec_dense_spd_inverse alone;
@@ -22,7 +22,6 @@ import argparse
 import json
 import statistics
 import sys
-import time
 from pathlib import Path
 
 import torch
@@ -31,7 +30,7 @@ ROOT = Path(__file__).resolve().parents[1]
 if str(ROOT) not in sys.path:
     sys.path.insert(0, str(ROOT))
 
-from tools.split_bench import make_log, spread          # noqa: E402  pylint: disable=wrong-import-position
+from tools.bench_record import Recorder, make_log, timed, repeat as bench_repeat          # noqa: E402  pylint: disable=wrong-import-position
 
 FP64_VECTOR_PEAK_TFLOPS = 78.6
 
@@ -51,37 +50,19 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("admm_slim_bench needs a GPU: a CPU run gives no time")
     from replay_cql_amd import admm_slim as AS
+    from replay_cql_amd._dense import Dense
     from replay_cql_amd.filters import filter_by_min_count
     from replay_cql_amd.indexer import Indexer
     dev = torch.device("cuda:0")
-    D = AS.Dense(dev)
+    D = Dense(dev)
     result = {"device": torch.cuda.get_device_name(0), "repeats": args.repeats, "fp64_vector_peak_tflops": FP64_VECTOR_PEAK_TFLOPS,
               "calls": {}}
 
-    def timed(fn):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        out = fn()
-        torch.cuda.synchronize()
-        return time.perf_counter() - t0, out
-
-    def save():
-        if args.out:
-            path = Path(args.out)
-            path.parent.mkdir(parents=True, exist_ok=True)
-            path.write_text(json.dumps(result, indent=1) + "\n")
-
-    def record(name, times, **more):
-        row = {"s": times, "median_s": statistics.median(times), "spread_s": spread(times), **more}
-        result["calls"][name] = row
-        print(json.dumps({"call": name, **{k: v for k, v in row.items() if not isinstance(v, list)}}), flush=True)
-        save()
-        return row["median_s"]
+    rec = Recorder(result, args.out)
+    record, save = rec.record, rec.save
 
     def repeat(fn):
-        timed(fn)
-        runs = [timed(fn) for _ in range(args.repeats)]
-        return [t for t, _ in runs], runs[-1][1]
+        return bench_repeat(fn, args.repeats)
 
     # ---- the GEMM alone, beside torch.matmul --------------------------------------------------------------------
     gen = torch.Generator(device=dev).manual_seed(1)
@@ -129,14 +110,11 @@ def main():
 
         # the pieces, on the matrices of this log
         item, user = small["item_idx"], small["user_idx"]
-        perm_i, off_i = D.segments(item, n_items, user.to(torch.int64))
-        perm_u, off_u = D.segments(user, n_users, item.to(torch.int64))
-        perm_i, perm_u = perm_i.long(), perm_u.long()
         rel = small["relevance"].to(torch.float64)
-        views = ((off_i, user[perm_i].contiguous(), rel[perm_i].contiguous()), (off_u, item[perm_u].contiguous(), rel[perm_u].contiguous()))
+        views = (D.view(item, n_items, user, rel)[0], D.view(user, n_users, item, rel)[0])
         times, G = repeat(lambda: D.gram(*views, n_items, n_users))
         record(f"dense_gram items={n}", times, **shape)
-        del views, perm_i, perm_u
+        del views
         times, W = repeat(lambda: D.spd_inverse(G, 2.0 * model.lambda_2))
         inv_s = record(f"dense_spd_inverse items={n}", times, tflops_of_3n3=3.0 * n_items ** 3 / statistics.median(times) / 1e12)
         Pm = D.gemm(W, G)

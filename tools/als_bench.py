@@ -4,7 +4,7 @@ every time.
     python tools/als_bench.py [--users 1000000] [--items 100000] [--ranks 10 128] [--repeats 5] [--k 10]
                               [--out profiles/als_bench.json]
 
-The log is tools/split_bench.make_log's (1 M users, 100 000 items, about 48 M rows, device columns in, fixed random row
+The log is tools/bench_record.make_log's (1 M users, 100 000 items, about 48 M rows, device columns in, fixed random row
 order).  Timed per rank, each as the median of `repeats` whole calls after one warm-up (host clock around a call that
 ends in a device synchronise), with the spread (max - min):
   one iteration            Gram matrix + item half step + Gram matrix + user half step, on the two CSR views built once
@@ -24,7 +24,6 @@ import argparse
 import json
 import statistics
 import sys
-import time
 from pathlib import Path
 
 import torch
@@ -33,7 +32,7 @@ ROOT = Path(__file__).resolve().parents[1]
 if str(ROOT) not in sys.path:
     sys.path.insert(0, str(ROOT))
 
-from tools.split_bench import make_log, spread          # noqa: E402  pylint: disable=wrong-import-position
+from tools.bench_record import Recorder, make_log, repeat          # noqa: E402  pylint: disable=wrong-import-position
 
 FP32_VECTOR_PEAK = 157.3e12
 FP64_VECTOR_PEAK = FP32_VECTOR_PEAK / 2
@@ -67,37 +66,22 @@ def main():
               "repeats": args.repeats, "k": args.k, "piece": A.PIECE, "gather_rates_bytes_per_s": [slow, fast],
               "fp64_vector_peak_flops": FP64_VECTOR_PEAK, "fp32_vector_peak_flops": FP32_VECTOR_PEAK, "ranks": {}}
 
-    def timed(fn):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        out = fn()
-        torch.cuda.synchronize()
-        return time.perf_counter() - t0, out
+    rec = Recorder(result, args.out, calls={})
+    record = rec.record
 
-    def median_of(fn):
-        timed(fn)
-        times = [timed(fn)[0] for _ in range(args.repeats)]
-        return {"s": times, "median_s": statistics.median(times), "spread_s": spread(times)}
-
-    def save():
-        if args.out:
-            path = Path(args.out)
-            path.parent.mkdir(parents=True, exist_ok=True)
-            path.write_text(json.dumps(result, indent=1) + "\n")
+    def times_of(fn):
+        return repeat(fn, args.repeats)[0]
 
     # the two CSR views, as ALSWrap._fit_device builds them
     eng = A.Als(dev)
     lg = L.open_log(log, "als_bench")
     (user, n_users), (item, n_items) = L.dense_ids(lg, ["user_idx", "item_idx"])
     rel = L.float_column(lg, "relevance")
-    perm_i, off_i = eng.segments(item, n_items, user.to(torch.int64))
-    perm_u, off_u = eng.segments(user, n_users, item.to(torch.int64))
-    item_side = (off_i, user[perm_i.long()].contiguous(), rel[perm_i.long()].contiguous())
-    user_side = (off_u, item[perm_u.long()].contiguous(), rel[perm_u.long()].contiguous())
+    item_side, user_side = eng.view(item, n_items, user, rel)[0], eng.view(user, n_users, item, rel)[0]
+    off_i, off_u = item_side[0], user_side[0]
     np_i, np_u = A.count_pieces(off_i), A.count_pieces(off_u)
     result.update(item_pieces=np_i, user_pieces=np_u, longest_item_row=int((off_i[1:] - off_i[:-1]).max().item()),
                   longest_user_row=int((off_u[1:] - off_u[:-1]).max().item()))
-    del perm_i, perm_u
 
     for r in args.ranks:
         model = A.ALSWrap(rank=r, seed=1, max_iter=1)
@@ -122,24 +106,19 @@ def main():
                   "fp64_ops": fp64_ops, "fp64_floor_s": fp64_ops / FP64_VECTOR_PEAK}
         row = {"floors_of_one_iteration": floors, "calls": {}}
         result["ranks"][str(r)] = row
+        rec.calls, rec.tag = row["calls"], {"rank": r}
 
-        def record(name, m, **more):
-            row["calls"][name] = {**m, **more}
-            print(json.dumps({"rank": r, "call": name, **{k: v for k, v in row["calls"][name].items() if not isinstance(v, list)}}),
-                  flush=True)
-            save()
-
-        m = median_of(iteration)
+        times = times_of(iteration)
+        med = statistics.median(times)
         floor = max(floors["gather_floor_s"][0], floors["fp64_floor_s"])
-        record("iteration", m, over_gather_floor=[m["median_s"] / f for f in floors["gather_floor_s"]],
-               over_fp64_floor=m["median_s"] / floors["fp64_floor_s"], over_larger_floor=m["median_s"] / floor,
-               failed=int(failed.item()))
-        record("gram(user factors)", median_of(lambda: eng.gram(U)))
-        record("gram(item factors)", median_of(lambda: eng.gram(V)))
+        record("iteration", times, over_gather_floor=[med / f for f in floors["gather_floor_s"]],
+               over_fp64_floor=med / floors["fp64_floor_s"], over_larger_floor=med / floor, failed=int(failed.item()))
+        record("gram(user factors)", times_of(lambda: eng.gram(U)))
+        record("gram(item factors)", times_of(lambda: eng.gram(V)))
         G_u, G_v = eng.gram(U), eng.gram(V)
-        record("half_step(items)", median_of(lambda: eng.half_step(item_side, U, G_u, True, 1.0, 0.1, V, has_v, failed, n_pieces=np_i)),
+        record("half_step(items)", times_of(lambda: eng.half_step(item_side, U, G_u, True, 1.0, 0.1, V, has_v, failed, n_pieces=np_i)),
                fp64_floor_s=(nnz * r * (r + 1) + n_items * r ** 3 / 3) / FP64_VECTOR_PEAK)
-        record("half_step(users)", median_of(lambda: eng.half_step(user_side, V, G_v, True, 1.0, 0.1, U, has_u, failed, n_pieces=np_u)),
+        record("half_step(users)", times_of(lambda: eng.half_step(user_side, V, G_v, True, 1.0, 0.1, U, has_u, failed, n_pieces=np_u)),
                fp64_floor_s=(nnz * r * (r + 1) + n_users * r ** 3 / 3) / FP64_VECTOR_PEAK)
 
         def fit():
@@ -147,16 +126,14 @@ def main():
             mm.fit(log)
             return mm
 
-        timed(fit)
-        runs = [timed(fit) for _ in range(args.repeats)]
-        times, model = [t for t, _ in runs], runs[-1][1]
-        del runs
-        record("ALSWrap.fit(max_iter=1)", {"s": times, "median_s": statistics.median(times), "spread_s": spread(times)})
+        times, model = repeat(fit, args.repeats)
+        record("ALSWrap.fit(max_iter=1)", times)
 
         score_floor = args.users * args.items * r / (FP32_VECTOR_PEAK / 2)          # FMAs per second = FLOP/s / 2
-        m = median_of(lambda: model.recommend(log, args.k))
-        record(f"recommend(all users, k={args.k})", m, score_fmas=args.users * args.items * r, fp32_floor_s=score_floor,
-               over_fp32_floor=m["median_s"] / score_floor, users_per_s=args.users / m["median_s"])
+        times = times_of(lambda: model.recommend(log, args.k))
+        med = statistics.median(times)
+        record(f"recommend(all users, k={args.k})", times, score_fmas=args.users * args.items * r, fp32_floor_s=score_floor,
+               over_fp32_floor=med / score_floor, users_per_s=args.users / med)
         del model, U, V
 
 

@@ -4,7 +4,7 @@ and, beside them in the same process, a pandas implementation of the same fit an
     python tools/features_bench.py [--users 1000000] [--candidates 100] [--repeats 5] [--pandas-repeats 1]
                                    [--out profiles/features_bench.json]
 
-The log is tools/split_bench.make_log's (1 M users, 100 000 items, about 48 M rows, device columns in, fixed random row
+The log is tools/bench_record.make_log's (1 M users, 100 000 items, about 48 M rows, device columns in, fixed random row
 order); its timestamp (start + position inside the user) is taken as HOURS, so that a user's history spans days.  The
 categorical features are user_idx % 7 and item_idx % 13, listed for every id.
 
@@ -34,7 +34,7 @@ ROOT = Path(__file__).resolve().parents[1]
 if str(ROOT) not in sys.path:
     sys.path.insert(0, str(ROOT))
 
-from tools.split_bench import make_log, spread          # noqa: E402  pylint: disable=wrong-import-position
+from tools.bench_record import make_log, spread          # noqa: E402  pylint: disable=wrong-import-position
 
 DAY_S = 86400
 

@@ -4,7 +4,7 @@ same process, the two yardsticks of its design: the radix sort of as many tuples
     python tools/neighbour_bench.py [--users 1000000] [--items 100000] [--repeats 5] [--baseline-blocks 4]
                                     [--block-rows 1000] [--out profiles/neighbour_bench.json]
 
-The log is tools/split_bench.make_log's (1 M users, 100 000 items, about 48 M rows, device columns in, fixed random row
+The log is tools/bench_record.make_log's (1 M users, 100 000 items, about 48 M rows, device columns in, fixed random row
 order).  Timed, each as the median of `repeats` whole calls after one warm-up (host clock around a call that ends in a
 device synchronise), with the spread (max - min):
   ItemKNN(10).fit                 weighting None and bm25; device columns in, the similarity block on the device out
@@ -24,10 +24,8 @@ values.  Needs a GPU."""
 from __future__ import annotations
 
 import argparse
-import json
 import statistics
 import sys
-import time
 from pathlib import Path
 
 import torch
@@ -36,7 +34,7 @@ ROOT = Path(__file__).resolve().parents[1]
 if str(ROOT) not in sys.path:
     sys.path.insert(0, str(ROOT))
 
-from tools.split_bench import make_log, spread          # noqa: E402  pylint: disable=wrong-import-position
+from tools.bench_record import Recorder, make_log, timed, repeat as bench_repeat          # noqa: E402  pylint: disable=wrong-import-position
 
 
 def main():
@@ -61,21 +59,10 @@ def main():
     result = {"device": torch.cuda.get_device_name(0), "users": args.users, "items": args.items, "rows": n_rows,
               "repeats": args.repeats, "neighbours": args.neighbours, "k": args.k, "max_tuples": max_tuples, "calls": {}}
 
-    def timed(fn):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        out = fn()
-        torch.cuda.synchronize()
-        return time.perf_counter() - t0, out
+    record = Recorder(result, args.out).record
 
-    def record(name, times, **more):
-        row = {"s": times, "median_s": statistics.median(times), "spread_s": spread(times), **more}
-        result["calls"][name] = row
-        print(json.dumps({"call": name, **{k: v for k, v in row.items() if not isinstance(v, list)}}), flush=True)
-        if args.out:                                     # after every call: a later one running long loses nothing
-            path = Path(args.out)
-            path.parent.mkdir(parents=True, exist_ok=True)
-            path.write_text(json.dumps(result, indent=1) + "\n")
+    def repeat(fn):
+        return bench_repeat(fn, args.repeats)
 
     def fit(weighting):
         model = NB.ItemKNN(args.neighbours, weighting=weighting, max_tuples=max_tuples)
@@ -84,32 +71,26 @@ def main():
 
     model = None
     for weighting in (None, "bm25"):
-        timed(lambda: fit(weighting))
-        runs = [timed(lambda: fit(weighting)) for _ in range(args.repeats)]
-        times, model = [t for t, _ in runs], runs[-1][1]
+        times, model = repeat(lambda: fit(weighting))
         total, largest = model.expansion
         record(f"ItemKNN.fit(weighting={weighting})", times, expansion_tuples=total, largest_row_tuples=largest,
                tuples_per_s=total / statistics.median(times), rows_per_s=n_rows / statistics.median(times),
                chunks_at_least=-(-total // max_tuples))
-        del runs
     fit_tuples = model.expansion[0]
 
-    timed(lambda: model.recommend(log, args.k))
-    runs = [timed(lambda: model.recommend(log, args.k)) for _ in range(args.repeats)]
-    times, out = [t for t, _ in runs], runs[-1][1]
+    times, out = repeat(lambda: model.recommend(log, args.k))
     total, largest = model.expansion
     record(f"ItemKNN.recommend(all users, k={args.k})", times, expansion_tuples=total, largest_row_tuples=largest,
            tuples_per_s=total / statistics.median(times), rows_out=int(out["item_idx"].numel()),
            users_per_s=args.users / statistics.median(times))
-    del runs, out
+    del out
 
     # the sort alone: as many tuples as the fit expands to, in chunks of max_tuples
     gen = torch.Generator(device=dev).manual_seed(3)
     chunk = min(max_tuples, fit_tuples)
     keys = torch.randint(0, 1 << 62, (chunk,), device=dev, generator=gen)
     n_chunks = -(-fit_tuples // chunk)
-    timed(lambda: torch.sort(keys))
-    per_chunk = [timed(lambda: torch.sort(keys))[0] for _ in range(args.repeats)]
+    per_chunk = repeat(lambda: torch.sort(keys))[0]
     del keys
     record("sort_alone(torch.sort, int64 keys + int64 index, 64 bits)", [t * n_chunks for t in per_chunk],
            tuples=fit_tuples, chunk_tuples=chunk, chunks=n_chunks, per_chunk_median_s=statistics.median(per_chunk),

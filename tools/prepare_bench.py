@@ -32,7 +32,7 @@ ROOT = Path(__file__).resolve().parents[1]
 if str(ROOT) not in sys.path:
     sys.path.insert(0, str(ROOT))
 
-from tools.split_bench import make_log, spread          # noqa: E402  pylint: disable=wrong-import-position
+from tools.bench_record import make_log, spread          # noqa: E402  pylint: disable=wrong-import-position
 
 
 # ---- the pandas side: the keep mask of each filter -------------------------------------------------------------

@@ -4,7 +4,7 @@ value plane instead of three, no dedup in front) and the radix sort of as many t
 
     python tools/rules_bench.py [--users 1000000] [--items 100000] [--repeats 5] [--out profiles/rules_bench.json]
 
-The log is tools/split_bench.make_log's, as in tools/neighbour_bench.py (1 M users, 100 000 items, about 48 M rows, device
+The log is tools/bench_record.make_log's, as in tools/neighbour_bench.py (1 M users, 100 000 items, about 48 M rows, device
 columns in, fixed random row order); sessions are the users.  Timed, each as the median of `repeats` whole calls after
 one warm-up (host clock around a call that ends in a device synchronise), with the spread (max - min):
   AssociationRulesItemRec().fit                                   the defaults: min_item_count = min_pair_count = 5, k = 1000
@@ -21,7 +21,6 @@ import argparse
 import json
 import statistics
 import sys
-import time
 from pathlib import Path
 
 import torch
@@ -30,7 +29,7 @@ ROOT = Path(__file__).resolve().parents[1]
 if str(ROOT) not in sys.path:
     sys.path.insert(0, str(ROOT))
 
-from tools.split_bench import make_log, spread          # noqa: E402  pylint: disable=wrong-import-position
+from tools.bench_record import Recorder, make_log, repeat as bench_repeat          # noqa: E402  pylint: disable=wrong-import-position
 
 
 def chunk_count(prefix, max_tuples: int) -> int:
@@ -66,29 +65,11 @@ def main():
     result = {"device": torch.cuda.get_device_name(0), "users": args.users, "items": args.items, "rows": n_rows,
               "repeats": args.repeats, "k": args.k, "max_tuples": max_tuples, "calls": {}}
 
-    def timed(fn):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        out = fn()
-        torch.cuda.synchronize()
-        return time.perf_counter() - t0, out
-
-    def save():
-        if args.out:                                     # after every call: a later one running long loses nothing
-            path = Path(args.out)
-            path.parent.mkdir(parents=True, exist_ok=True)
-            path.write_text(json.dumps(result, indent=1) + "\n")
-
-    def record(name, times, **more):
-        row = {"s": times, "median_s": statistics.median(times), "spread_s": spread(times), **more}
-        result["calls"][name] = row
-        print(json.dumps({"call": name, **{k: v for k, v in row.items() if not isinstance(v, list)}}), flush=True)
-        save()
+    rec = Recorder(result, args.out)
+    record, save = rec.record, rec.save
 
     def repeat(fn):
-        timed(fn)
-        runs = [timed(fn) for _ in range(args.repeats)]
-        return [t for t, _ in runs], runs[-1][1]
+        return bench_repeat(fn, args.repeats)
 
     def rules(**more):
         model = AssociationRulesItemRec(max_tuples=max_tuples, **more)

@@ -2,7 +2,7 @@
 
     python tools/slim_bench.py [--fit-items 16384 4096] [--repeats 5] [--out profiles/slim_bench.json]
 
-The cfg3 log (tools/split_bench.make_log: 1 M users, 100 000 items, about 48 M rows) is cut with the package's own
+The cfg3 log (tools/bench_record.make_log: 1 M users, 100 000 items, about 48 M rows) is cut with the package's own
 filter_by_min_count and Indexer to the largest catalogue of at most n items (a tie at the cut would add items, so the
 threshold moves up by one count where it must): n = CQLREC_SLIM_MAX_ITEMS, where G is 2 GiB and every update streams a
 128 KB row from HBM, and n = 4096, where G (128 MiB) sits in the 256 MiB Infinity Cache.
@@ -31,7 +31,7 @@ ROOT = Path(__file__).resolve().parents[1]
 if str(ROOT) not in sys.path:
     sys.path.insert(0, str(ROOT))
 
-from tools.split_bench import make_log, spread          # noqa: E402  pylint: disable=wrong-import-position
+from tools.bench_record import Recorder, make_log, repeat as bench_repeat          # noqa: E402  pylint: disable=wrong-import-position
 
 STREAMING_TBPS = 4.87          # profiles/README.md, r02_hbm_traffic.json: Adam over 268 M parameters, 0.61 of the nominal 8 TB/s
 
@@ -82,40 +82,21 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("slim_bench needs a GPU: a CPU run gives no time")
     from replay_cql_amd import _native as N
-    from replay_cql_amd import admm_slim as AS
+    from replay_cql_amd._dense import Dense
     from replay_cql_amd import slim as SL
     from replay_cql_amd.filters import filter_by_min_count
     from replay_cql_amd.indexer import Indexer
     dev = torch.device("cuda:0")
-    D = AS.Dense(dev)
+    D = Dense(dev)
     sizes = args.fit_items or [N.SLIM_MAX_ITEMS, 4096]
     result = {"device": torch.cuda.get_device_name(0), "repeats": args.repeats, "streaming_tbps": STREAMING_TBPS,
               "defaults": {"beta": 0.01, "lambda_": 0.01, "tol": SL.SLIM.tol, "max_iter": SL.SLIM.max_iter}, "calls": {}}
 
-    def timed(fn):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        out = fn()
-        torch.cuda.synchronize()
-        return time.perf_counter() - t0, out
-
-    def save():
-        if args.out:
-            path = Path(args.out)
-            path.parent.mkdir(parents=True, exist_ok=True)
-            path.write_text(json.dumps(result, indent=1) + "\n")
-
-    def record(name, times, **more):
-        row = {"s": times, "median_s": statistics.median(times), "spread_s": spread(times), **more}
-        result["calls"][name] = row
-        print(json.dumps({"call": name, **{k: v for k, v in row.items() if not isinstance(v, list)}}), flush=True)
-        save()
-        return row["median_s"]
+    rec = Recorder(result, args.out)
+    record, save = rec.record, rec.save
 
     def repeat(fn):
-        timed(fn)
-        runs = [timed(fn) for _ in range(args.repeats)]
-        return [t for t, _ in runs], runs[-1][1]
+        return bench_repeat(fn, args.repeats)
 
     log = make_log(args.users, args.items, dev)
     counts = torch.bincount(log["item_idx"].long(), minlength=args.items)
@@ -146,14 +127,11 @@ def main():
                        kkt_max=float(model.kkt.max().item()), table_nnz=int(model.similarity_device[1].numel()), **shape)
 
         item, user = small["item_idx"], small["user_idx"]
-        perm_i, off_i = D.segments(item, n_items, user.to(torch.int64))
-        perm_u, off_u = D.segments(user, n_users, item.to(torch.int64))
-        perm_i, perm_u = perm_i.long(), perm_u.long()
         rel = small["relevance"].to(torch.float64)
-        views = ((off_i, user[perm_i].contiguous(), rel[perm_i].contiguous()), (off_u, item[perm_u].contiguous(), rel[perm_u].contiguous()))
+        views = (D.view(item, n_items, user, rel)[0], D.view(user, n_users, item, rel)[0])
         times, G = repeat(lambda: D.gram(*views, n_items, n_users))
         gram_s = record(f"dense_gram items={n}", times)
-        del views, perm_i, perm_u
+        del views
         S = torch.zeros((n_items, n_items), dtype=torch.float64, device=dev)
         solver = SL.SLIM()
         times, out = repeat(lambda: solver.solve(D, G, n_users, S=S))

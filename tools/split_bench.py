@@ -32,17 +32,7 @@ if str(ROOT) not in sys.path:
     sys.path.insert(0, str(ROOT))
 
 
-def make_log(n_users: int, n_items: int, dev):
-    from replay_cql_amd import data as D
-    offsets, items, rewards = D.synth_log_device(n_users, n_items, device=dev)
-    lens = offsets[1:] - offsets[:-1]
-    user = torch.repeat_interleave(torch.arange(n_users, dtype=torch.int32, device=dev), lens)
-    pos = torch.arange(items.numel(), dtype=torch.int64, device=dev) - offsets[user.long()]
-    start = D._lsr(D._mix64(torch.arange(n_users, dtype=torch.int64, device=dev)), 1) % 1000
-    ts = start[user.long()] + pos
-    order = torch.randperm(items.numel(), device=dev, generator=torch.Generator(device=dev).manual_seed(5))
-    return {"user_idx": user[order].contiguous(), "item_idx": items[order].contiguous(),
-            "timestamp": ts[order].contiguous(), "relevance": rewards[order].to(torch.float64).contiguous()}
+from tools.bench_record import make_log, spread          # noqa: E402  pylint: disable=wrong-import-position
 
 
 # ---- the pandas side: (train mask, test mask) of each split -----------------------------------------------------
@@ -70,10 +60,6 @@ def pandas_new_users(df, test_size=0.1):
     thr = by_date[by_date >= len(starts) * test_size].index.max()
     ts = df["timestamp"].to_numpy()
     return ts < thr, (start >= thr) & (df["relevance"] > 0.0).to_numpy()
-
-
-def spread(xs):
-    return max(xs) - min(xs)
 
 
 def main():
