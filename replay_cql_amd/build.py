@@ -15,10 +15,12 @@ PKG = Path(__file__).resolve().parent
 CSRC = PKG / "csrc"
 LIB = PKG / "libcqlrec.so"
 TORCH_LIB = PKG / "libcqlrec_torch.so"      # torch.ops.cqlrec.* registration shim over the C ABI (csrc/torch_ops.cpp)
-SOURCES = ["misc.hip", "qhead.hip", "qhead_de.hip", "qhead_de2.hip", "qhead_de3.hip", "qhead_argmax2.hip", "qhead_fwd2.hip", "qhead_fwd3.hip", "qhead_topk2.hip", "qhead_topk4.hip", "select_common.hip", "segment_common.hip", "topk.hip", "item_knn.hip", "pairs_topk.hip", "gbwd.hip", "prep.hip", "metrics.hip", "split.hip", "prepare.hip", "features.hip", "neighbour.hip", "als.hip", "dense.hip", "slim.hip", "step_streams.hip", "train.hip"]
-# misc.hip holds the Adam kernel whose expression order is normative: no fma contraction anywhere in that file
+SOURCES = ["library.hip", "state_side.hip", "adam.hip", "qhead.hip", "qhead_de.hip", "qhead_de2.hip", "qhead_de3.hip", "qhead_argmax2.hip", "qhead_fwd2.hip", "qhead_fwd3.hip", "qhead_topk2.hip", "qhead_topk4.hip", "select_common.hip", "segment_common.hip", "topk.hip", "item_knn.hip", "pairs_topk.hip", "gbwd.hip", "prep.hip", "metrics.hip", "split.hip", "prepare.hip", "features.hip", "neighbour.hip", "als.hip", "dense.hip", "slim.hip", "step_streams.hip", "train.hip"]
 EXTRA = {
-    "misc.hip": ["-ffp-contract=off"],
+    # gather_dot_kernel is what pairs_topk.hip is tied to bit for bit; the state-side kernels are evaluated as written
+    "state_side.hip": ["-ffp-contract=off"],
+    # the expression order of the Adam + Polyak kernels is normative: no fma contraction anywhere in that file
+    "adam.hip": ["-ffp-contract=off"],
     # MFMA results straight into VGPRs (gfx950 has a unified file): no v_accvgpr_read per accumulator register
     "qhead.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
     "qhead_de.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
@@ -32,7 +34,7 @@ EXTRA = {
     "topk.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
     # the metric expressions of get_nearest_items are normative in their operation order (as NumPy float32 evaluates them)
     "item_knn.hip": ["-ffp-contract=off", "-mllvm", "-amdgpu-mfma-vgpr-form=1"],
-    # pair scores are tied to gather_dot_kernel (misc.hip) bit for bit: the same flag as that file
+    # pair scores are tied to gather_dot_kernel (state_side.hip) bit for bit: the same flag as that file
     "pairs_topk.hip": ["-ffp-contract=off"],
     # the proportion rule's division and the uniform draws are tied to their IEEE double expressions
     "split.hip": ["-ffp-contract=off"],

@@ -1,4 +1,4 @@
-// The Adam + Polyak arithmetic of one parameter and the one loop body the streaming optimizer kernels (misc.hip) are made
+// The Adam + Polyak arithmetic of one parameter and the one loop body the streaming optimizer kernels (adam.hip) are made
 // of, plus the internal entry points of those kernels.  The expression order is the normative one (oracle.adam_ema_step):
 // no fma contraction, IEEE division and square root -- whichever kernel updates a parameter, the bits are the same.
 #pragma once
@@ -10,7 +10,7 @@
 int cql_adam_ema_fix(float* theta, float* grads, float* m, float* v, float* target, uint16_t* theta_b, uint16_t* target_b,
                      int64_t n, float step_size, float sqrt_bc2, float beta1, float beta2, float eps, float tau,
                      int32_t zero_grads, const CqlAdamFix* fix, hipStream_t stream);
-// Adam over the whole embedding rows of E_in inside a cqlrec_train_steps call (misc.hip).  Only the rows
+// Adam over the whole embedding rows of E_in inside a cqlrec_train_steps call (adam.hip).  Only the rows
 // marked in `row_map` (one byte per row, n_rows of them) carry a gradient this step: the others take g = 0 and their gradient
 // elements are not read.  `age[r]` counts the steps row r is behind; a row is brought up to date -- the missed steps replayed in order with g = +0.0f, then this step's -- when it has a
 // gradient (`row_map`), when the next step's forward reads it (`read_next`; NULL: every row, the flush), or when its age

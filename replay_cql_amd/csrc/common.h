@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <stdarg.h>
+#include <type_traits>
 
 #include "../../include/cqlrec.h"
 
@@ -36,6 +37,23 @@ void cql_set_error(const char* fmt, ...);
     }                                                                       \
   } while (0)
 
+// ---- run-time value -> template argument (host) -------------------------------------------------------------
+// f(std::integral_constant<int, V>{}) for the V among Vals that equals v; any other value runs nothing and is refused
+template <int... Vals, class F>
+static inline int cql_dispatch(int v, F&& f) {
+  const bool hit = ((v == Vals ? (f(std::integral_constant<int, Vals>{}), true) : false) || ...);
+  return hit ? CQLREC_OK : CQLREC_ERR_INVALID;
+}
+// the embedding widths the kernels are built for: the one list.  Entry points check with cql_d_ok (and their own error
+// text); launch sites turn d into a template argument with cql_by_d(d, [&](auto D) { ...<decltype(D)::value>... })
+static inline bool cql_d_ok(int d) { return d == 64 || d == 128 || d == 256; }
+template <class F>
+static inline int cql_by_d(int d, F&& f) {
+  const int rc = cql_dispatch<64, 128, 256>(d, f);
+  if (rc != CQLREC_OK) cql_set_error("d=%d unsupported (64, 128 or 256)", d);
+  return rc;
+}
+
 // index of the calling thread's current device into small per-device state tables (internal streams, "opt-in done"
 // flags): a process that drives several devices gets one set per device instead of silently sharing the first one's
 #define CQL_MAX_DEVICES 16
@@ -54,11 +72,11 @@ struct CqlProfScope {
   ~CqlProfScope() { cql_prof_end(s); }
 };
 
-// misc.hip: cqlrec_encoder_bwd in parts (1: input-side products, 2: weight / bias gradients, 3: both)
+// state_side.hip: cqlrec_encoder_bwd in parts (1: input-side products, 2: weight / bias gradients, 3: both)
 int cql_encoder_bwd_parts(const float* dH, const uint16_t* z_b, const uint16_t* h0_b, const uint16_t* W1_b,
                           const uint16_t* W2_b, int64_t rows, int32_t d, void* ws, int64_t ws_bytes, float* g_W1, float* g_b1,
                           float* g_W2, float* g_b2, float* dh0, int parts, hipStream_t s);
-// misc.hip: cqlrec_td_loss in two launches (coefficients by many blocks; the loss value by one, off the critical path)
+// state_side.hip: cqlrec_td_loss in two launches (coefficients by many blocks; the loss value by one, off the critical path)
 int cql_td_coef(const float* q_a, const float* lse, const float* q_targ, const float* rew, const float* done, int32_t batch,
                 float gamma, float alpha, float inv_batch, float* coef, float* y, float* term, hipStream_t s);
 int cql_td_loss_sum(const float* term, int32_t batch, float inv_batch, float* loss_out, hipStream_t s);

@@ -165,17 +165,19 @@ __global__ __launch_bounds__(256) void segsum_pass2_kernel(const uint32_t* __res
   if (SRC_BF16 && lane == 0) dst_w[k] = accumulate ? dst_w[k] + accw : accw;
 }
 
-// host side of the two passes
+// host side of the two passes; the dispatcher's status (both callers return it)
 template <bool SRC_BF16, int CH>
-static void segsum_launch(const void* src, const float* w, const uint32_t* keys, const uint32_t* vals, int64_t n_pairs,
+static int segsum_launch(const void* src, const float* w, const uint32_t* keys, const uint32_t* vals, int64_t n_pairs,
                           uint32_t pad_key, int d, float* dst, float* dst_w, float* edge, float* edge_w, hipStream_t s,
                           int accumulate = 0) {
   dim3 grid(cql_ceil_div((n_pairs + CH - 1) / CH, 4)), block(256);
-#define SS1(DD) hipLaunchKernelGGL((segsum_pass1_kernel<DD, SRC_BF16, CH>), grid, block, 0, s, src, w, keys, vals, n_pairs, pad_key, dst, dst_w, edge, edge_w, accumulate)
-#define SS2(DD) hipLaunchKernelGGL((segsum_pass2_kernel<DD, SRC_BF16, CH>), grid, block, 0, s, keys, n_pairs, pad_key, edge, edge_w, dst, dst_w, accumulate)
-  if (d == 64) { SS1(64); SS2(64); } else if (d == 128) { SS1(128); SS2(128); } else { SS1(256); SS2(256); }
-#undef SS1
-#undef SS2
+  return cql_by_d(d, [&](auto D) {
+    constexpr int DD = decltype(D)::value;
+    hipLaunchKernelGGL((segsum_pass1_kernel<DD, SRC_BF16, CH>), grid, block, 0, s, src, w, keys, vals, n_pairs, pad_key, dst,
+                       dst_w, edge, edge_w, accumulate);
+    hipLaunchKernelGGL((segsum_pass2_kernel<DD, SRC_BF16, CH>), grid, block, 0, s, keys, n_pairs, pad_key, edge, edge_w, dst,
+                       dst_w, accumulate);
+  });
 }
 
 #define GB_CH 64   // pairs per wave, window gather
@@ -224,7 +226,7 @@ extern "C" int cqlrec_gather_pool_bwd_prepare(const int64_t* offsets, const int3
                                               int32_t d, int64_t n_items, void* ws, int64_t ws_bytes,
                                               cqlrec_stream stream) {
   CQL_REQUIRE(offsets && items && users && ws, "gather_pool_bwd_prepare: NULL pointer");
-  CQL_REQUIRE(d == 64 || d == 128 || d == 256, "gather_pool_bwd_prepare: d=%d unsupported", d);
+  CQL_REQUIRE(cql_d_ok(d), "gather_pool_bwd_prepare: d=%d unsupported", d);
   CQL_REQUIRE(n_items > 0 && n_items < (1ll << 31), "gather_pool_bwd_prepare: n_items=%lld", (long long)n_items);
   if (n_states <= 0) return CQLREC_OK;
   CQL_REQUIRE(ws_bytes >= cqlrec_gather_pool_bwd_ws_bytes(n_states, L, d), "gather_pool_bwd_prepare: workspace too small");
@@ -244,7 +246,7 @@ extern "C" int cqlrec_gather_pool_bwd_prepare(const int64_t* offsets, const int3
 
 // Which rows of g_E_in will phase 2 write?  One byte per item: cleared, then set from the sorted keys (every pair of a run
 // stores the same 1: plain byte stores, no atomics; sorted keys keep the stores of a wave on a few cache lines).  The
-// pipelined step driver hands the map to its state-side optimizer launch (misc.hip, adam_ema_rows_deferred_kernel).
+// pipelined step driver hands the map to its state-side optimizer launch (adam.hip, adam_ema_rows_deferred_kernel).
 __global__ __launch_bounds__(256) void gbwd_mark_rows_kernel(const uint32_t* __restrict__ keys, int64_t n_pairs,
                                                              uint32_t pad_key, uint8_t* __restrict__ row_map) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -300,7 +302,7 @@ int cql_mark_read_rows(const int64_t* offsets, const int32_t* items, const int32
 extern "C" int cqlrec_gather_pool_bwd_apply(const float* dh0, int64_t n_states, int32_t L, int32_t d, int64_t n_items,
                                             void* ws, int64_t ws_bytes, float* g_E_in, cqlrec_stream stream) {
   CQL_REQUIRE(dh0 && ws && g_E_in, "gather_pool_bwd_apply: NULL pointer");
-  CQL_REQUIRE(d == 64 || d == 128 || d == 256, "gather_pool_bwd_apply: d=%d unsupported", d);
+  CQL_REQUIRE(cql_d_ok(d), "gather_pool_bwd_apply: d=%d unsupported", d);
   if (n_states <= 0) return CQLREC_OK;
   CQL_REQUIRE(ws_bytes >= cqlrec_gather_pool_bwd_ws_bytes(n_states, L, d), "gather_pool_bwd_apply: workspace too small");
   const GbWs w = gb_carve(ws, n_states, L, d);
@@ -311,9 +313,9 @@ extern "C" int cqlrec_gather_pool_bwd_apply(const float* dh0, int64_t n_states, 
   const int64_t n4 = n_states * (d / 4);
   hipLaunchKernelGGL(gbwd_scale_kernel, dim3(cql_ceil_div(n4, 256)), dim3(256), 0, s, (const float4*)dh0, w.lens, n4,
                      d / 4, (float4*)w.g);
-  segsum_launch<false, GB_CH>(w.g, nullptr, w.keys_out, w.vals_out, n, pad_key, d, g_E_in, nullptr, w.edge, nullptr, s);
+  const int rc = segsum_launch<false, GB_CH>(w.g, nullptr, w.keys_out, w.vals_out, n, pad_key, d, g_E_in, nullptr, w.edge, nullptr, s);
   CQL_LAUNCH_CHECK("gather_pool_bwd_apply");
-  return CQLREC_OK;
+  return rc;
 }
 
 extern "C" int cqlrec_gather_pool_bwd_sorted(const float* dh0, const int64_t* offsets, const int32_t* items,
@@ -387,7 +389,7 @@ int cql_onehot_apply(const float* coef, const uint16_t* H_b, int64_t batch, int6
   CQL_REQUIRE(coef && H_b && ws && g_E_out && g_b_out, "onehot_apply: NULL pointer");
   const OhWs w = oh_carve(ws, batch, d);
   CqlProfScope prof(CQLREC_PH_QHEAD_SMALL, s);
-  segsum_launch<true, OH_CH>(H_b, coef, w.keys_out, w.vals_out, batch, (uint32_t)n_items, d, g_E_out, g_b_out, w.edge, w.edge_w, s, accumulate);
+  const int rc = segsum_launch<true, OH_CH>(H_b, coef, w.keys_out, w.vals_out, batch, (uint32_t)n_items, d, g_E_out, g_b_out, w.edge, w.edge_w, s, accumulate);
   CQL_LAUNCH_CHECK("onehot_apply");
-  return CQLREC_OK;
+  return rc;
 }

@@ -352,21 +352,21 @@ static KnnWs knn_ws_layout(int64_t n_query, int64_t n_cand, int32_t d) {
 
 extern "C" int64_t cqlrec_item_knn_ws_bytes(int64_t n_query, int64_t n_cand, int32_t d, int32_t k) {
   (void)k;
-  if (n_query <= 0 || n_cand <= 0 || !(d == 64 || d == 128 || d == 256)) return 0;
+  if (n_query <= 0 || n_cand <= 0 || !cql_d_ok(d)) return 0;
   return knn_ws_layout(n_query, n_cand, d).total;
 }
 
 extern "C" int cqlrec_item_norms(const uint16_t* E_b, int64_t n_rows, int32_t d, float* norms, cqlrec_stream stream) {
   CQL_REQUIRE(E_b && norms, "item_norms: NULL pointer");
-  CQL_REQUIRE(d == 64 || d == 128 || d == 256, "item_norms: d=%d unsupported", d);
+  CQL_REQUIRE(cql_d_ok(d), "item_norms: d=%d unsupported", d);
   CQL_REQUIRE(n_rows > 0 && n_rows < (1ll << 31), "item_norms: n_rows=%lld", (long long)n_rows);
   hipStream_t s = (hipStream_t)stream;
   const dim3 grid(cql_ceil_div(n_rows * 8, 256)), block(256);
-  if (d == 64) hipLaunchKernelGGL((item_norms_kernel<64>), grid, block, 0, s, E_b, n_rows, norms);
-  else if (d == 128) hipLaunchKernelGGL((item_norms_kernel<128>), grid, block, 0, s, E_b, n_rows, norms);
-  else hipLaunchKernelGGL((item_norms_kernel<256>), grid, block, 0, s, E_b, n_rows, norms);
+  const int rc = cql_by_d(d, [&](auto D) {
+    hipLaunchKernelGGL((item_norms_kernel<decltype(D)::value>), grid, block, 0, s, E_b, n_rows, norms);
+  });
   CQL_LAUNCH_CHECK("item_norms");
-  return CQLREC_OK;
+  return rc;
 }
 
 template <int D, int M>
@@ -401,7 +401,7 @@ extern "C" int cqlrec_item_knn(const uint16_t* E_b, const float* norms, int64_t 
                                int64_t n_query, const int32_t* cand_rows, int64_t n_cand, int32_t metric, int32_t k, void* ws,
                                int64_t ws_bytes, int32_t* out_idx, float* out_val, int32_t* out_cnt, cqlrec_stream stream) {
   CQL_REQUIRE(E_b && norms && query_rows && ws && out_idx && out_val && out_cnt, "item_knn: NULL pointer");
-  CQL_REQUIRE(d == 64 || d == 128 || d == 256, "item_knn: d=%d unsupported", d);
+  CQL_REQUIRE(cql_d_ok(d), "item_knn: d=%d unsupported", d);
   CQL_REQUIRE(n_rows > 0 && n_rows < (1ll << 31), "item_knn: n_rows=%lld", (long long)n_rows);
   CQL_REQUIRE(n_query > 0 && n_query < (1ll << 31), "item_knn: n_query=%lld", (long long)n_query);
   CQL_REQUIRE(n_cand > 0 && n_cand <= n_rows, "item_knn: n_cand=%lld (1..n_rows=%lld)", (long long)n_cand, (long long)n_rows);
@@ -412,16 +412,12 @@ extern "C" int cqlrec_item_knn(const uint16_t* E_b, const float* norms, int64_t 
   const KnnWs w = knn_ws_layout(n_query, n_cand, d);
   CQL_REQUIRE(ws_bytes >= w.total, "item_knn: workspace too small");
   hipStream_t s = (hipStream_t)stream;
-#define KNN_ARGS E_b, norms, n_rows, query_rows, n_query, cand_rows, n_cand, k, (char*)ws, w, out_idx, out_val, out_cnt, s
-#define KNN_BY_METRIC(DD)                                                         \
-  do {                                                                            \
-    if (metric == CQLREC_SIM_DOT) knn_launch<DD, CQLREC_SIM_DOT>(KNN_ARGS);       \
-    else if (metric == CQLREC_SIM_COSINE) knn_launch<DD, CQLREC_SIM_COSINE>(KNN_ARGS); \
-    else knn_launch<DD, CQLREC_SIM_EUCLID>(KNN_ARGS);                             \
-  } while (0)
-  if (d == 64) KNN_BY_METRIC(64); else if (d == 128) KNN_BY_METRIC(128); else KNN_BY_METRIC(256);
-#undef KNN_BY_METRIC
-#undef KNN_ARGS
+  const int rc = cql_by_d(d, [&](auto D) {
+    cql_dispatch<CQLREC_SIM_DOT, CQLREC_SIM_COSINE, CQLREC_SIM_EUCLID>(metric, [&](auto M) {   // metric: checked above
+      knn_launch<decltype(D)::value, decltype(M)::value>(E_b, norms, n_rows, query_rows, n_query, cand_rows, n_cand, k,
+                                                         (char*)ws, w, out_idx, out_val, out_cnt, s);
+    });
+  });
   CQL_LAUNCH_CHECK("item_knn");
-  return CQLREC_OK;
+  return rc;
 }

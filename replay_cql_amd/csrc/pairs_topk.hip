@@ -9,7 +9,7 @@
 //   score         the wave holds its row's h in registers (read once per piece): lane c of a group of d/8 lanes keeps
 //                 elements 8c..8c+7.  64 / (d/8) groups each gather one E_out row per step, four steps in flight
 //                 (4 rows in flight per lane group: 4 KiB per wave), the next steps' item ids already loaded.  Arithmetic
-//                 is gather_dot_kernel's (misc.hip), operation for operation: eight sequential fmaf from 0 per lane, the
+//                 is gather_dot_kernel's (state_side.hip), operation for operation: eight sequential fmaf from 0 per lane, the
 //                 xor butterfly over the group, + b[item] -- the same bits, which is what lets predict_pairs(k) return
 //                 the frame the host path returned.  Scores of a chunk of 256 candidates wait in LDS.
 //   admit         all 64 lanes then take one candidate each: the score goes to out_score (coalesced), the row's seen
@@ -21,7 +21,7 @@
 //                 output (the only or first piece) or, as keys, to the piece's slot of the workspace.
 //   merge         one wave per cut row: the keys of its output and of its further pieces through the same buffer.
 //   Integer atomics hand out table slots (their order varies; what the slots hold does not); no float atomics, every
-//   output is a pure function of the inputs.  Compiled with -ffp-contract=off like misc.hip.
+//   output is a pure function of the inputs.  Compiled with -ffp-contract=off like state_side.hip.
 #include "common.h"
 #include "select_common.h"
 
@@ -305,7 +305,7 @@ static PtWs pt_ws_layout(int32_t k) {
 }
 
 extern "C" int64_t cqlrec_pairs_topk_ws_bytes(int64_t n_sel, int64_t nnz, int32_t d, int32_t k) {
-  if (n_sel <= 0 || n_sel > PT_MAX_ROWS || nnz < 0 || !(d == 64 || d == 128 || d == 256) || k < 0 || k > PT_MAX_K) return 0;
+  if (n_sel <= 0 || n_sel > PT_MAX_ROWS || nnz < 0 || !cql_d_ok(d) || k < 0 || k > PT_MAX_K) return 0;
   return pt_ws_layout(k).total;       // the piece table is bounded whatever the list lengths: see the head of this file
 }
 
@@ -315,7 +315,7 @@ extern "C" int cqlrec_pairs_topk(const uint16_t* H_b, const uint16_t* E_b, const
                                  int64_t ws_bytes, float* out_score, int32_t* out_idx, float* out_val, int32_t* out_cnt,
                                  cqlrec_stream stream) {
   CQL_REQUIRE(H_b && E_b && b && pair_off && pair_items && ws, "pairs_topk: NULL pointer");
-  CQL_REQUIRE(d == 64 || d == 128 || d == 256, "pairs_topk: d=%d unsupported", d);
+  CQL_REQUIRE(cql_d_ok(d), "pairs_topk: d=%d unsupported", d);
   CQL_REQUIRE(k >= 0 && k <= PT_MAX_K, "pairs_topk: k=%d out of range (0..%d)", k, PT_MAX_K);
   CQL_REQUIRE(n_items > 0 && n_items < (1ll << 31), "pairs_topk: n_items=%lld", (long long)n_items);
   // one 64-thread block per row: 2^26 rows are the 2^32 threads a launch may have
@@ -348,13 +348,11 @@ extern "C" int cqlrec_pairs_topk(const uint16_t* H_b, const uint16_t* E_b, const
     return CQLREC_ERR_HIP;
   }
   hipLaunchKernelGGL(pt_plan_kernel, dim3(cql_ceil_div(n_sel, 256)), dim3(256), 0, s, a);
-#define PT_LAUNCH(DD)                                                                          \
-  do {                                                                                         \
-    hipLaunchKernelGGL(pt_row_kernel<DD>, dim3((unsigned)n_sel), dim3(64), 0, s, a);           \
-    hipLaunchKernelGGL(pt_piece_kernel<DD>, dim3(PT_MAX_EXTRA), dim3(64), 0, s, a);            \
-  } while (0)
-  if (d == 64) PT_LAUNCH(64); else if (d == 128) PT_LAUNCH(128); else PT_LAUNCH(256);
-#undef PT_LAUNCH
+  const int rc = cql_by_d(d, [&](auto D) {
+    hipLaunchKernelGGL(pt_row_kernel<decltype(D)::value>, dim3((unsigned)n_sel), dim3(64), 0, s, a);
+    hipLaunchKernelGGL(pt_piece_kernel<decltype(D)::value>, dim3(PT_MAX_EXTRA), dim3(64), 0, s, a);
+  });
+  if (rc != CQLREC_OK) return rc;
   if (k > 0) hipLaunchKernelGGL(pt_merge_kernel, dim3(PT_MAX_EXTRA), dim3(64), 0, s, a);
   CQL_LAUNCH_CHECK("pairs_topk");
   return CQLREC_OK;

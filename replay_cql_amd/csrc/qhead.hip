@@ -560,10 +560,8 @@ static void qs_launch_d(const QArgs& a, int64_t rblks, hipStream_t s) {
 
 template <int MODE, int SPW>
 static int qs_launch_mode(const QArgs& a, int d, int64_t rblks, hipStream_t s) {
-  if (d == 64) qs_launch_d<64, SPW, MODE>(a, rblks, s);
-  else if (d == 128) qs_launch_d<128, SPW, MODE>(a, rblks, s);
-  else qs_launch_d<256, SPW, MODE>(a, rblks, s);
-  return 0;
+  // the dispatcher's status; the callers of qs_launch do not look at it: each sits behind its entry point's cql_d_ok check
+  return cql_by_d(d, [&](auto D) { qs_launch_d<decltype(D)::value, SPW, MODE>(a, rblks, s); });
 }
 
 static int qs_launch_switch(int mode, const QArgs& a, int d, int64_t rblks, hipStream_t s);
@@ -809,7 +807,7 @@ static int qhead_fwd_impl(const uint16_t* H_b, int64_t rows, const uint16_t* E_o
                          int32_t d, int32_t mode, void* ws, int64_t ws_bytes, float* out_val, int32_t* out_idx,
                          float* out_nlse2, cqlrec_stream stream, bool skeleton) {
   CQL_REQUIRE(H_b && E_out_b && b_out && ws && out_val, "qhead_fwd: NULL pointer");
-  CQL_REQUIRE(d == 64 || d == 128 || d == 256, "qhead_fwd: d=%d unsupported", d);
+  CQL_REQUIRE(cql_d_ok(d), "qhead_fwd: d=%d unsupported", d);
   CQL_REQUIRE(rows > 0 && n_items > 0, "qhead_fwd: rows=%lld n_items=%lld", (long long)rows, (long long)n_items);
   CQL_REQUIRE(mode == CQLREC_QHEAD_LSE || mode == CQLREC_QHEAD_ARGMAX, "qhead_fwd: bad mode %d", mode);
   CQL_REQUIRE(ws_bytes >= cqlrec_qhead_ws_bytes(rows, n_items, d), "qhead_fwd: workspace too small");
@@ -853,11 +851,11 @@ static int qhead_fwd_impl(const uint16_t* H_b, int64_t rows, const uint16_t* E_o
     }
     CqlProfScope prof(CQLREC_PH_QHEAD_SMALL, s);
     dim3 rg((unsigned)rows), rb(64);
-#define RES_AM(DD)                                                                                                \
-  hipLaunchKernelGGL(qhead_argmax_resolve_kernel<DD>, rg, rb, 0, s, a.part_a, a.part_i, a.nsplit, rows, H_b, E_out_b, \
-                     b_out, n_items, out_val, out_idx)
-    if (d == 64) RES_AM(64); else if (d == 128) RES_AM(128); else RES_AM(256);
-#undef RES_AM
+    const int rc = cql_by_d(d, [&](auto D) {
+      hipLaunchKernelGGL(qhead_argmax_resolve_kernel<decltype(D)::value>, rg, rb, 0, s, a.part_a, a.part_i, a.nsplit, rows,
+                         H_b, E_out_b, b_out, n_items, out_val, out_idx);
+    });
+    if (rc != CQLREC_OK) return rc;
   }
   CQL_LAUNCH_CHECK("qhead_fwd");
   return CQLREC_OK;
@@ -880,7 +878,7 @@ extern "C" int cqlrec_qhead_bwd_states(const uint16_t* H_b, const float* nlse2, 
                                        int32_t d, float scale, void* ws, int64_t ws_bytes, float* dH,
                                        cqlrec_stream stream) {
   CQL_REQUIRE(H_b && nlse2 && coef && act && E_out_b && b_out && ws && dH, "qhead_bwd_states: NULL pointer");
-  CQL_REQUIRE(d == 64 || d == 128 || d == 256, "qhead_bwd_states: d=%d unsupported", d);
+  CQL_REQUIRE(cql_d_ok(d), "qhead_bwd_states: d=%d unsupported", d);
   CQL_REQUIRE(batch > 0 && n_items > 0, "qhead_bwd_states: batch=%lld n_items=%lld", (long long)batch, (long long)n_items);
   CQL_REQUIRE(ws_bytes >= cqlrec_qhead_bwd_ws_bytes(batch, n_items, d), "qhead_bwd_states: workspace too small");
   hipStream_t s = (hipStream_t)stream;
@@ -900,13 +898,12 @@ extern "C" int cqlrec_qhead_bwd_states(const uint16_t* H_b, const float* nlse2, 
   CqlProfScope prof(CQLREC_PH_QHEAD_SMALL, s);
   const int64_t n4 = batch * (d / 4);
   dim3 grid(cql_ceil_div(n4, 256)), block(256);
-#define RED_DH(DD)                                                                                                  \
-  hipLaunchKernelGGL(qhead_bwd_reduce_kernel<DD>, grid, block, 0, s, a.slab, a.nsplit, batch, scale, coef, act, E_out_b, \
-                     dH)
-  if (d == 64) RED_DH(64); else if (d == 128) RED_DH(128); else RED_DH(256);
-#undef RED_DH
+  const int rc = cql_by_d(d, [&](auto D) {
+    hipLaunchKernelGGL(qhead_bwd_reduce_kernel<decltype(D)::value>, grid, block, 0, s, a.slab, a.nsplit, batch, scale, coef,
+                       act, E_out_b, dH);
+  });
   CQL_LAUNCH_CHECK("qhead_bwd_states");
-  return CQLREC_OK;
+  return rc;
 }
 
 // g_E_out / g_b_out only: the persistent, statically balanced kernel of qhead_de.hip, then (do_sparse) the one-hot
@@ -918,22 +915,22 @@ static int qhead_bwd_items_impl(const uint16_t* H_b, const float* nlse2, const f
                                const float* nlse_nat = nullptr) {
   if (defer) defer->valid = 0;
   CQL_REQUIRE(H_b && nlse2 && coef && act && E_out_b && b_out && ws && g_E_out && g_b_out, "qhead_bwd_items: NULL pointer");
-  CQL_REQUIRE(d == 64 || d == 128 || d == 256, "qhead_bwd_items: d=%d unsupported", d);
+  CQL_REQUIRE(cql_d_ok(d), "qhead_bwd_items: d=%d unsupported", d);
   CQL_REQUIRE(batch > 0 && n_items > 0, "qhead_bwd_items: batch=%lld n_items=%lld", (long long)batch, (long long)n_items);
   CQL_REQUIRE(ws_bytes >= cqlrec_qhead_bwd_ws_bytes(batch, n_items, d), "qhead_bwd_items: workspace too small");
   hipStream_t s = (hipStream_t)stream;
-  const int rc = cql_qde_launch(H_b, nlse2, batch, E_out_b, b_out, n_items, d, scale, ws, ws_bytes, g_E_out, g_b_out, 0, s,
-                                defer, nlse_nat);
+  int rc = cql_qde_launch(H_b, nlse2, batch, E_out_b, b_out, n_items, d, scale, ws, ws_bytes, g_E_out, g_b_out, 0, s, defer,
+                          nlse_nat);
   if (rc != CQLREC_OK) return rc;
   if (do_sparse) {
     CqlProfScope prof(CQLREC_PH_QHEAD_SMALL, s);
     dim3 g2(cql_ceil_div(batch, 4)), block(256);
-#define SP_DE(DD) hipLaunchKernelGGL(qhead_bwd_sparse_kernel<DD>, g2, block, 0, s, coef, act, H_b, batch, g_E_out, g_b_out)
-    if (d == 64) SP_DE(64); else if (d == 128) SP_DE(128); else SP_DE(256);
-#undef SP_DE
+    rc = cql_by_d(d, [&](auto D) {
+      hipLaunchKernelGGL(qhead_bwd_sparse_kernel<decltype(D)::value>, g2, block, 0, s, coef, act, H_b, batch, g_E_out, g_b_out);
+    });
   }
   CQL_LAUNCH_CHECK("qhead_bwd_items");
-  return CQLREC_OK;
+  return rc;
 }
 
 extern "C" int cqlrec_qhead_bwd_items(const uint16_t* H_b, const float* nlse2, const float* coef, const int32_t* act,
@@ -982,7 +979,7 @@ int cql_qhead_fwd_lse_dh(const uint16_t* H_b, int64_t rows, const uint16_t* E_ou
                          int32_t d, void* ws, int64_t ws_bytes, float* out_lse, float* out_nlse2, hipStream_t s,
                          float* out_nlse_nat, int flag_cleared) {
   CQL_REQUIRE(H_b && E_out_b && b_out && ws && out_lse, "qhead_fwd_lse_dh: NULL pointer");
-  CQL_REQUIRE(d == 64 || d == 128 || d == 256, "qhead_fwd_lse_dh: d=%d unsupported", d);
+  CQL_REQUIRE(cql_d_ok(d), "qhead_fwd_lse_dh: d=%d unsupported", d);
   CQL_REQUIRE(rows > 0 && n_items > 0, "qhead_fwd_lse_dh: rows=%lld n_items=%lld", (long long)rows, (long long)n_items);
   const FusedWs f = fused_ws(ws, rows, n_items, d);
   CQL_REQUIRE(ws_bytes >= f.bytes, "qhead_fwd_lse_dh: workspace too small");
@@ -1038,22 +1035,19 @@ int cql_qhead_fwd_lse_dh(const uint16_t* H_b, int64_t rows, const uint16_t* E_ou
 int cql_qhead_dh_finish(const void* ws, int64_t rows, int64_t n_items, int32_t d, const float* lse, const float* coef,
                         const int32_t* act, const uint16_t* E_out_b, float scale, float* dH, hipStream_t s, int part) {
   CQL_REQUIRE(ws && lse && act && E_out_b && dH && (coef || part == 1) && part >= 0 && part <= 2, "qhead_dh_finish: bad arguments");
+  CQL_REQUIRE(cql_d_ok(d), "qhead_dh_finish: d=%d unsupported", d);      // in front of the workspace arithmetic on d
   const FusedWs f = fused_ws(const_cast<void*>(ws), rows, n_items, d);
   CqlProfScope prof(CQLREC_PH_QHEAD_SMALL, s);
   const int64_t n4 = rows * (d / 4);
   dim3 grid(cql_ceil_div(n4, 256)), block(256);
-#define FIN_DH(DD, PP)                                                                                                   \
-  hipLaunchKernelGGL((qhead_dh_finish_kernel<DD, PP>), grid, block, 0, s, f.slab, f.part_a, f.sp.nsplit, rows, lse, scale, \
-                     coef, act, E_out_b, dH)
-#define FIN_DH_D(PP)                                                                                                     \
-  do {                                                                                                                   \
-    if (d == 64) FIN_DH(64, PP); else if (d == 128) FIN_DH(128, PP); else FIN_DH(256, PP);                               \
-  } while (0)
-  if (part == 0) FIN_DH_D(0); else if (part == 1) FIN_DH_D(1); else FIN_DH_D(2);
-#undef FIN_DH_D
-#undef FIN_DH
+  const int rc = cql_by_d(d, [&](auto D) {
+    cql_dispatch<0, 1, 2>(part, [&](auto P) {       // part is 0..2: checked above
+      hipLaunchKernelGGL((qhead_dh_finish_kernel<decltype(D)::value, decltype(P)::value>), grid, block, 0, s, f.slab, f.part_a,
+                         f.sp.nsplit, rows, lse, scale, coef, act, E_out_b, dH);
+    });
+  });
   CQL_LAUNCH_CHECK("qhead_dh_finish");
-  return CQLREC_OK;
+  return rc;
 }
 
 extern "C" int64_t cqlrec_qhead_fused_ws_bytes(int64_t rows, int64_t n_items, int32_t d) {

@@ -362,12 +362,13 @@ static void qde_launch_n(const QDeArgs& a, int grid, hipStream_t s) {
   }
   hipLaunchKernelGGL((qde_kernel<D, NBUF, WAVES>), dim3(grid), dim3(64 * WAVES), smem, s, a);
 }
-// the fix-up launch: the slab pieces of `sl` onto the gradient
-static void qde_fixup(const QdeSlab& sl, float* out, float* out_cs, hipStream_t s) {
+// the fix-up launch: the slab pieces of `sl` onto the gradient; the dispatcher's status (both callers return it)
+static int qde_fixup(const QdeSlab& sl, float* out, float* out_cs, hipStream_t s) {
   CqlProfScope prof(CQLREC_PH_QHEAD_SMALL, s);
-#define FIXUP(DD) hipLaunchKernelGGL((qde_fixup_kernel<DD, qde_items(DD)>), dim3(sl.pc.G), dim3(256), 0, s, sl, out, out_cs)
-  if (sl.D == 64) FIXUP(64); else if (sl.D == 128) FIXUP(128); else FIXUP(256);
-#undef FIXUP
+  return cql_by_d(sl.D, [&](auto D) {
+    constexpr int DD = decltype(D)::value;
+    hipLaunchKernelGGL((qde_fixup_kernel<DD, qde_items(DD)>), dim3(sl.pc.G), dim3(256), 0, s, sl, out, out_cs);
+  });
 }
 
 // g_E_out / g_b_out rows [0, n_items) of this call: out (+)= scale * dE (accumulate: on top of what is there)
@@ -414,9 +415,11 @@ int cql_qde_launch(const uint16_t* H_b, const float* nlse2, int64_t batch, const
     if (rc != CQLREC_OK) return rc;
   } else {
     CqlProfScope prof(CQLREC_PH_QHEAD_BWD_DE, s);
-    if (d == 64) qde_launch_n<64, QDE_NBUF, de_waves(64)>(a, grid, s);
-    else if (d == 128) qde_launch_n<128, QDE_NBUF, de_waves(128)>(a, grid, s);
-    else qde_launch_n<256, QDE_NBUF, de_waves(256)>(a, grid, s);
+    const int rc = cql_by_d(d, [&](auto D) {
+      constexpr int DD = decltype(D)::value;
+      qde_launch_n<DD, QDE_NBUF, de_waves(DD)>(a, grid, s);
+    });
+    if (rc != CQLREC_OK) return rc;
   }
   if (pl.pc.any_cut()) {
     const QdeSlab sl = {a.slab, a.slab_cs, pl.pc, items, d, scale, n_items};
@@ -424,7 +427,8 @@ int cql_qde_launch(const uint16_t* H_b, const float* nlse2, int64_t batch, const
       defer->valid = 1;
       defer->s = sl;
     } else {
-      qde_fixup(sl, out, out_cs, s);
+      const int rc = qde_fixup(sl, out, out_cs, s);
+      if (rc != CQLREC_OK) return rc;
     }
   }
   CQL_LAUNCH_CHECK("qde");
@@ -465,7 +469,7 @@ int cql_qde_launch(const uint16_t* H_b, const float* nlse2, int64_t batch, const
 // the rows between the long kernel and the slabs: the one-hot part, see train.hip)
 int cql_qde_fixup_deferred(const CqlAdamFix& f, float* out, float* out_cs, hipStream_t s) {
   if (!f.valid) return CQLREC_OK;
-  qde_fixup(f.s, out, out_cs, s);
+  const int rc = qde_fixup(f.s, out, out_cs, s);
   CQL_LAUNCH_CHECK("qde fix-up");
-  return CQLREC_OK;
+  return rc;
 }

@@ -633,7 +633,7 @@ extern "C" int cqlrec_score_topk_phase(const uint16_t* H_b, int64_t n_users, con
                                phase == CQLREC_TOPK_SEEN_BESIDE);
   }
   CQL_REQUIRE(H_b && E_b && b && ws && out_idx && out_val && out_cnt, "score_topk: NULL pointer");
-  CQL_REQUIRE(d == 64 || d == 128 || d == 256, "score_topk: d=%d unsupported", d);
+  CQL_REQUIRE(cql_d_ok(d), "score_topk: d=%d unsupported", d);
   CQL_REQUIRE(n_users > 0 && n_cand > 0, "score_topk: n_users=%lld n_cand=%lld", (long long)n_users, (long long)n_cand);
   CQL_REQUIRE(k > 0 && k <= TK_MAX_K, "score_topk: k=%d out of range (1..%d)", k, TK_MAX_K);
   CQL_REQUIRE(seen_off == nullptr || seen_items != nullptr, "score_topk: seen_items is NULL");
@@ -727,31 +727,22 @@ extern "C" int cqlrec_score_topk_phase(const uint16_t* H_b, int64_t n_users, con
   CqlProfScope prof(CQLREC_PH_TOPK_SELECT, s);
   cql_sel_transpose(tm, ngroups, n_users, tm_t, gstride, s);
   dim3 grid((unsigned)n_users), block(64);
-#define TK_LAUNCH_CB(DD, KP, CB)                                                                                      \
-  hipLaunchKernelGGL((topk_select_kernel<DD, KP, CB>), grid, block, 0, s, H_b, n_users, E_b, b, n_cand, item_ids,        \
-                     seen_off, seen_items, seen_rows, (const float*)tm_t, gstride, ngroups, tg, k, out_idx, out_val,     \
-                     out_cnt)
-#define TK_LAUNCH(DD, KP)                                     \
-  do {                                                        \
-    if (k <= TK_CB_SMALL / 2) TK_LAUNCH_CB(DD, KP, TK_CB_SMALL); \
-    else TK_LAUNCH_CB(DD, KP, TK_CB_LARGE);                   \
-  } while (0)
-#define TKS_LAUNCH(DD, KP)                                                                                          \
-  hipLaunchKernelGGL((topk_select_small_kernel<DD, KP>), grid, block, 0, s, H_b, n_users, E_b, b, n_cand, item_ids,  \
-                     seen_off, seen_items, seen_rows, (const float*)tm_t, gstride, ngroups, tg, k, out_idx, out_val,  \
-                     out_cnt)
+  // both selection kernels take the one argument list
+  const auto launch = [&](auto* kernel) {
+    hipLaunchKernelGGL(kernel, grid, block, 0, s, H_b, n_users, E_b, b, n_cand, item_ids, seen_off, seen_items, seen_rows,
+                       (const float*)tm_t, gstride, ngroups, tg, k, out_idx, out_val, out_cnt);
+  };
   const bool small_k = k <= TKS_MAX_K;
-#define TK_BY_KPL(DD)                                                       \
-  do {                                                                      \
-    if (ngroups <= 1024) { if (small_k) TKS_LAUNCH(DD, 16); else TK_LAUNCH(DD, 16); }      \
-    else if (ngroups <= 2048) { if (small_k) TKS_LAUNCH(DD, 32); else TK_LAUNCH(DD, 32); } \
-    else { if (small_k) TKS_LAUNCH(DD, 64); else TK_LAUNCH(DD, 64); }                      \
-  } while (0)
-  if (d == 64) TK_BY_KPL(64); else if (d == 128) TK_BY_KPL(128); else TK_BY_KPL(256);
-#undef TK_BY_KPL
-#undef TKS_LAUNCH
-#undef TK_LAUNCH
-#undef TK_LAUNCH_CB
+  const int kpl = ngroups <= 1024 ? 16 : ngroups <= 2048 ? 32 : 64;           // bound entries per lane
+  const int cb = k <= TK_CB_SMALL / 2 ? TK_CB_SMALL : TK_CB_LARGE;            // candidate buffer
+  const int rc = cql_by_d(d, [&](auto D) {
+    cql_dispatch<16, 32, 64>(kpl, [&](auto KP) {
+      if (small_k) launch(topk_select_small_kernel<decltype(D)::value, decltype(KP)::value>);
+      else cql_dispatch<TK_CB_SMALL, TK_CB_LARGE>(cb, [&](auto CB) {
+          launch(topk_select_kernel<decltype(D)::value, decltype(KP)::value, decltype(CB)::value>);
+        });
+    });
+  });
   CQL_LAUNCH_CHECK("score_topk");
-  return CQLREC_OK;
+  return rc;
 }

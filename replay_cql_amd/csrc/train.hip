@@ -136,7 +136,7 @@ int check_ctx(const cqlrec_train_ctx* c) {
   CQL_REQUIRE(c->batch > 0 && c->window > 0 && c->world > 0 && c->rank >= 0 && c->rank < c->world,
               "train_step: batch=%d window=%d world=%d rank=%d", c->batch, c->window, c->world, c->rank);
   const int32_t d = c->layout.d;
-  CQL_REQUIRE(d == 64 || d == 128 || d == 256, "train_step: d=%d unsupported", d);
+  CQL_REQUIRE(cql_d_ok(d), "train_step: d=%d unsupported", d);
   CQL_REQUIRE(c->ws_bytes >= cqlrec_train_ws_bytes(c->batch, c->layout.n_items, d, c->window),
               "train_step: workspace too small");
   return CQLREC_OK;
@@ -532,7 +532,7 @@ extern "C" int cqlrec_train_step_update(const cqlrec_train_ctx* c, uint64_t step
 // The last step of a call runs the zeroing forms (E_in still through its map, so that stale rows count as zero and are
 // cleared), which leaves ctx->grads all zeros as the phase entry points expect.  A single-step call runs the full forms only.
 //
-// The E_in launch is also deferred per row (misc.hip, adam_ema_rows_deferred_kernel): a row without a gradient that the
+// The E_in launch is also deferred per row (adam.hip, adam_ema_rows_deferred_kernel): a row without a gradient that the
 // NEXT step's forward does not gather is left behind and only its age (workspace, zero when a call starts) moves on; the
 // launch that needs it replays the missed steps.  The next step's read map comes from sample_ahead under an event of its
 // own; a step whose successor was not sampled ahead, and the last step of a call, bring every row up to date, so the

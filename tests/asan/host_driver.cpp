@@ -113,6 +113,59 @@ static void refused_calls() {
   EXPECT(cqlrec_runtime_probe_count() == 0);
 }
 
+// every entry point that takes the embedding width refuses d = 96 and d = 0 -- with every other argument acceptable, so it is
+// the width that is refused -- in front of any launch (this build has no device code: a launch would fail)
+static void unsupported_widths() {
+  std::vector<uint16_t> h(64 * 256);
+  std::vector<float> f(64 * 256);
+  std::vector<int32_t> i32(4096);
+  std::vector<int64_t> i64(4096);
+  std::vector<unsigned char> wsv(1 << 22);
+  void* ws = wsv.data();
+  const int64_t wb = (int64_t)wsv.size();
+  uint16_t* hp = h.data();
+  float* fp = f.data();
+  int32_t* ip = i32.data();
+  int64_t* lp = i64.data();
+  cqlrec_layout lay;
+  for (int32_t d : {96, 0}) {
+#define REFUSED(call)                                                                  \
+  do {                                                                                 \
+    cqlrec_layout_make(8, 128, nullptr); /* leaves another text in the error buffer */ \
+    EXPECT((call) == CQLREC_ERR_INVALID);                                              \
+    EXPECT(strstr(cqlrec_last_error(), "unsupported") != nullptr);                     \
+  } while (0)
+    REFUSED(cqlrec_layout_make(100, d, &lay));
+    REFUSED(cqlrec_gather_pool_fwd(hp, lp, ip, ip, nullptr, 0, 8, 8, d, fp, hp, ip, nullptr));
+    REFUSED(cqlrec_gather_pool_bwd(fp, lp, ip, ip, nullptr, 0, 8, 8, d, fp, nullptr));
+    REFUSED(cqlrec_gather_pool_bwd_prepare(lp, ip, ip, nullptr, 0, 8, 8, d, 64, ws, wb, nullptr));
+    REFUSED(cqlrec_gather_pool_bwd_apply(fp, 8, 8, d, 64, ws, wb, fp, nullptr));
+    REFUSED(cqlrec_gather_pool_bwd_sorted(fp, lp, ip, ip, nullptr, 0, 8, 8, d, 64, ws, wb, fp, nullptr));
+    REFUSED(cqlrec_linear_bf16(hp, hp, fp, 8, d, 1, fp, hp, nullptr));
+    REFUSED(cqlrec_encoder_fwd(hp, hp, fp, hp, fp, 8, d, hp, hp, nullptr));
+    REFUSED(cqlrec_encoder_bwd(fp, hp, hp, hp, hp, 8, d, ws, wb, fp, fp, fp, fp, fp, nullptr));
+    REFUSED(cqlrec_qhead_fwd(hp, 8, hp, fp, 64, d, CQLREC_QHEAD_LSE, ws, wb, fp, nullptr, fp, nullptr));
+    REFUSED(cqlrec_qhead_fwd(hp, 8, hp, fp, 64, d, CQLREC_QHEAD_ARGMAX, ws, wb, fp, ip, nullptr, nullptr));
+    REFUSED(cqlrec_gather_dot(hp, hp, fp, ip, 8, d, fp, nullptr));
+    REFUSED(cqlrec_qhead_bwd(hp, fp, fp, ip, 8, hp, fp, 64, d, 1.f, ws, wb, fp, fp, fp, nullptr));
+    REFUSED(cqlrec_qhead_bwd_items(hp, fp, fp, ip, 8, hp, fp, 64, d, 1.f, ws, wb, fp, fp, nullptr));
+    REFUSED(cqlrec_qhead_bwd_states(hp, fp, fp, ip, 8, hp, fp, 64, d, 1.f, ws, wb, fp, nullptr));
+    REFUSED(cqlrec_qhead_fwd_lse_dh(hp, 8, hp, fp, 64, d, ws, wb, fp, fp, nullptr));
+    REFUSED(cqlrec_qhead_dh_finish(ws, 8, 64, d, fp, fp, ip, hp, 1.f, fp, nullptr));
+    REFUSED(cqlrec_score_topk(hp, 8, hp, fp, 64, d, nullptr, nullptr, nullptr, nullptr, 4, ws, wb, ip, fp, ip, nullptr));
+    REFUSED(cqlrec_score_topk_phase(hp, 8, hp, fp, 64, d, nullptr, nullptr, nullptr, nullptr, 4, ws, wb, ip, fp, ip,
+                                    CQLREC_TOPK_SCORE, nullptr));
+    REFUSED(cqlrec_item_norms(hp, 64, d, fp, nullptr));
+    REFUSED(cqlrec_item_knn(hp, fp, 64, d, ip, 8, nullptr, 64, CQLREC_SIM_DOT, 4, ws, wb, ip, fp, ip, nullptr));
+    REFUSED(cqlrec_pairs_topk(hp, hp, fp, 64, d, lp, ip, nullptr, 8, nullptr, nullptr, 4, ws, wb, fp, ip, fp, ip, nullptr));
+#undef REFUSED
+    // the width only selects a form here (d = 128 has one of its own): nothing to refuse, nothing launched, "no form"
+    int32_t form = 7;
+    EXPECT(cqlrec_topk_seen_form(ws, 8, 64, d, 4, &form, nullptr) == CQLREC_OK && form == -1);
+    EXPECT(cqlrec_item_knn_ws_bytes(8, 64, d, 4) == 0 && cqlrec_pairs_topk_ws_bytes(8, 64, d, 4) == 0);
+  }
+}
+
 // the error message buffer is thread-local: concurrent failing calls must not trample each other's text
 static void threads() {
   std::vector<std::thread> th;
@@ -195,6 +248,7 @@ int main(int argc, char** argv) {
   layouts();
   workspace_sizes();
   refused_calls();
+  unsupported_widths();
   threads();
   if (fails) {
     fprintf(stderr, "host_driver: %d expectation(s) failed\n", fails);
