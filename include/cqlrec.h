@@ -8,7 +8,10 @@
  * the reference code whose role it takes over.  Arithmetic follows SURVEY.md section 8.0 (S1-S7, P1-P4).
  *
  * Conventions
- *   - every pointer is a DEVICE pointer (hipMalloc'd / a torch tensor's data_ptr()) unless marked [host];
+ *   - every pointer is a DEVICE pointer (hipMalloc'd / a torch tensor's data_ptr()) unless marked [host].  The marker
+ *     is load-bearing: the Python binding reads its ctypes table from this file (replay_cql_amd/_header.py), and a comment
+ *     holding [host] inside a parameter's own text is what makes that parameter a typed host pointer there instead of a
+ *     device pointer that takes a tensor.  A pointer to a cqlrec_* struct is a host pointer with or without it;
  *   - plain pointers and sizes only, no torch types; `stream` is a hipStream_t passed as void* (0 = null stream);
  *   - all calls are asynchronous on `stream`, allocate nothing, never synchronise: they may be captured in a hipGraph
  *     (after one warm-up call: kernels with > 64 KiB of dynamic LDS opt in on first use; tests/test_gpu_kernels.py
@@ -228,8 +231,8 @@ int cqlrec_score_topk_phase(const uint16_t* H_b, int64_t n_users, const uint16_t
  * kernel.  *out (host) = -1: this shape filters by bitmap only; 0: entry lists (256-byte slots per 128 users x 64 items
  * + an overflow area, built in the bitmap's space; the bitmap was not built); 1: the lists did not fit, bitmap.
  * Synchronises `stream`. */
-int cqlrec_topk_seen_form(const void* ws, int64_t n_users, int64_t n_cand, int32_t d, int32_t k, int32_t* out,
-                          cqlrec_stream stream);
+int cqlrec_topk_seen_form(const void* ws, int64_t n_users, int64_t n_cand, int32_t d, int32_t k,
+                          int32_t* out /* [host] */, cqlrec_stream stream);
 
 /* ---------------------------------------------------------------------------------------------------------
  * a11  Item-to-item nearest neighbours.  Takes the place of ItemVectorModel._get_nearest_items' cross join of the item
@@ -777,7 +780,7 @@ typedef struct cqlrec_features_pop {
 #define CQLREC_FEATURES_COL_POP_NA 7
 int cqlrec_features_block(const int64_t* user_idx, const int64_t* item_idx, int64_t n_pairs, const double* utab,
                           const int32_t* ucount, int64_t n_users, int32_t fu, const double* itab, const int32_t* icount,
-                          int64_t n_items, int32_t fi, const int32_t* colmap, int32_t n_cols,
+                          int64_t n_items, int32_t fi, const int32_t* colmap /* [host] */, int32_t n_cols,
                           const cqlrec_features_pop* pops, int32_t n_pop, int32_t dtype, void* block,
                           cqlrec_stream stream);
 

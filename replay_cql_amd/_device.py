@@ -24,7 +24,7 @@ _PLANS = {}
 
 def _plan(name: str, args):
     """(the entry point's symbol, the positions in `args` that hold pointers, the position of the `Ws` or None), made
-    once per entry point from its declared argument types in `_native.SIGNATURES`"""
+    once per entry point from its argument types in `_native.SIGNATURES`, i.e. from its prototype in include/cqlrec.h"""
     types = list(N.SIGNATURES["cqlrec_" + name][1][:-1])                   # the stream is appended by `call`
     ws_at = next((i for i, a in enumerate(args) if isinstance(a, Ws)), None)
     if ws_at is not None:

@@ -9,6 +9,9 @@ import os
 from pathlib import Path
 from typing import Optional
 
+from . import _header
+from ._header import CqlrecError, f32, f64, i32, i64, u64, vp  # noqa: F401  (the scalar types, by their short names)
+
 # HIP multiplexes a process's streams onto GPU_MAX_HW_QUEUES hardware queues (default 4).  The step driver runs four
 # streams concurrently (the caller's + three internal), the predict pass and the data-parallel loop one more each: ask
 # for eight -- effective when this module is imported before the first HIP call of the process (importing torch makes
@@ -20,26 +23,10 @@ _LIB_PATH = Path(os.environ["CQLREC_LIB"]).resolve() if os.environ.get("CQLREC_L
     Path(__file__).resolve().parent / "libcqlrec.so"
 _lib: Optional[C.CDLL] = None
 
-ABI_VERSION = 2
-TOPK_ALL, TOPK_SEEN, TOPK_SCORE, TOPK_SEEN_BESIDE = 0, 1, 2, 3
-SIM_DOT, SIM_COSINE, SIM_EUCLID = 0, 1, 2
-ITEM_KNN_MAX_K = 512
-PAIRS_MAX_K = 512
-QHEAD_LSE = 1
-QHEAD_ARGMAX = 2
-EVAL_EXTRAS = ("RocAuc", "Unexpectedness", "Surprisal", "NCISPrecision")
-NCIS_NONE, NCIS_SIGMOID, NCIS_SOFTMAX = 0, 1, 2
-
-vp, i32, i64, u64, f32, f64 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64, C.c_float, C.c_double
+EVAL_EXTRAS = ("RocAuc", "Unexpectedness", "Surprisal", "NCISPrecision")     # names of the header's EVAL_EXTRAS slots
 
 
-class Layout(C.Structure):
-    _fields_ = [
-        ("n_items", i64), ("d", i32), ("reserved", i32),
-        ("off_E_in", i64), ("off_E_out", i64), ("off_b_out", i64), ("off_W1", i64), ("off_b1", i64),
-        ("off_W2", i64), ("off_b2", i64), ("total", i64),
-    ]
-
+class _LayoutMethods:
     SEGMENTS = ("E_in", "E_out", "b_out", "W1", "b1", "W2", "b2")
 
     def offset(self, name: str) -> int:
@@ -51,192 +38,19 @@ class Layout(C.Structure):
                 "b2": (d,)}[name]
 
 
-class TrainCtx(C.Structure):
-    _fields_ = [
-        ("layout", Layout),
-        ("offsets", vp), ("items", vp), ("rewards", vp), ("n_users", i64),
-        ("theta", vp), ("grads", vp), ("adam_m", vp), ("adam_v", vp), ("target", vp), ("theta_b", vp),
-        ("target_b", vp),
-        ("batch", i32), ("window", i32), ("world", i32), ("rank", i32),
-        ("gamma", f64), ("alpha", f64), ("lr", f64), ("beta1", f64), ("beta2", f64), ("eps", f64), ("tau", f64),
-        ("seed", u64),
-        ("ws", vp), ("ws_bytes", i64),
-    ]
-
-
-class TrainViews(C.Structure):
-    _fields_ = [(n, vp) for n in (
-        "users", "tpos", "act", "a_star", "rew", "done", "q_a", "lse", "q_targ", "y", "coef", "dH", "dh0", "h0_s",
-        "hb_s", "hb_sn", "hb_tn")]
-
-
-class FeaturesPop(C.Structure):
-    """cqlrec_features_pop: one fitted conditional-popularity table as cqlrec_features_block reads it"""
-    _fields_ = [("code", vp), ("pair_code", vp), ("keys", vp), ("pop", vp), ("entity_off", vp), ("n_code", i64), ("n_entity", i64),
-                ("n_cat", i64), ("m", i64), ("entity_is_item", i32), ("reserved", i32)]
-
-
-FEATURES_STATS, FEATURES_MAX_COLS, FEATURES_MAX_POP = 6, 64, 8
-FEAT_MEAN_GATHER, FEAT_MEAN_ABNORMALITY, FEAT_MEAN_ABNORMALITY_CR = 0, 1, 2
-(FEAT_COL_USER, FEAT_COL_ITEM, FEAT_COL_NA_USER, FEAT_COL_NA_ITEM, FEAT_COL_DIFF_USER, FEAT_COL_DIFF_ITEM, FEAT_COL_POP,
- FEAT_COL_POP_NA) = range(8)
-
-NEIGHBOUR_FIT, NEIGHBOUR_PREDICT = 0, 1
-NEIGHBOUR_MAX_K = 1024
-NEIGHBOUR_WEIGHTINGS = {None: 0, "tf_idf": 1, "bm25": 2}
-
-ALS_PIECE, ALS_GRAM_BLOCK, ALS_MAX_RANK, ALS_MAX_K = 1024, 4096, 128, 512
-ALS_EXPLICIT, ALS_IMPLICIT = 0, 1
-
-DENSE_GRAM_PIECE, DENSE_BLOCK = 1024, 64
-SLIM_MAX_ITEMS = 16384
-
-# name -> (restype, argtypes); every symbol include/cqlrec.h declares
-SIGNATURES = {
-    "cqlrec_abi_version": (i32, []),
-    "cqlrec_last_error": (C.c_char_p, []),
-    "cqlrec_layout_make": (i32, [i64, i32, C.POINTER(Layout)]),
-    "cqlrec_sample_transitions": (i32, [vp, vp, vp, i64, u64, u64, u64, i32, vp, vp, vp, vp, vp, vp]),
-    "cqlrec_gather_pool_fwd": (i32, [vp, vp, vp, vp, vp, i32, i64, i32, i32, vp, vp, vp, vp]),
-    "cqlrec_gather_pool_bwd": (i32, [vp, vp, vp, vp, vp, i32, i64, i32, i32, vp, vp]),
-    "cqlrec_gather_pool_bwd_ws_bytes": (i64, [i64, i32, i32]),
-    "cqlrec_gather_pool_bwd_prepare": (i32, [vp, vp, vp, vp, i32, i64, i32, i32, i64, vp, i64, vp]),
-    "cqlrec_gather_pool_bwd_apply": (i32, [vp, i64, i32, i32, i64, vp, i64, vp, vp]),
-    "cqlrec_gather_pool_bwd_sorted": (i32, [vp, vp, vp, vp, vp, i32, i64, i32, i32, i64, vp, i64, vp, vp]),
-    "cqlrec_linear_bf16": (i32, [vp, vp, vp, i64, i32, i32, vp, vp, vp]),
-    "cqlrec_encoder_fwd": (i32, [vp, vp, vp, vp, vp, i64, i32, vp, vp, vp]),
-    "cqlrec_encoder_bwd_ws_bytes": (i64, [i64, i32]),
-    "cqlrec_encoder_bwd": (i32, [vp, vp, vp, vp, vp, i64, i32, vp, i64, vp, vp, vp, vp, vp, vp]),
-    "cqlrec_qhead_ws_bytes": (i64, [i64, i64, i32]),
-    "cqlrec_qhead_fwd": (i32, [vp, i64, vp, vp, i64, i32, i32, vp, i64, vp, vp, vp, vp]),
-    "cqlrec_gather_dot": (i32, [vp, vp, vp, vp, i64, i32, vp, vp]),
-    "cqlrec_td_loss": (i32, [vp, vp, vp, vp, vp, i32, f32, f32, f32, vp, vp, vp, vp]),
-    "cqlrec_qhead_bwd_ws_bytes": (i64, [i64, i64, i32]),
-    "cqlrec_qhead_bwd": (i32, [vp, vp, vp, vp, i64, vp, vp, i64, i32, f32, vp, i64, vp, vp, vp, vp]),
-    "cqlrec_qhead_bwd_items": (i32, [vp, vp, vp, vp, i64, vp, vp, i64, i32, f32, vp, i64, vp, vp, vp]),
-    "cqlrec_qhead_bwd_states": (i32, [vp, vp, vp, vp, i64, vp, vp, i64, i32, f32, vp, i64, vp, vp]),
-    "cqlrec_adam_ema": (i32, [vp, vp, vp, vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, f32, i32, vp]),
-    "cqlrec_cast_bf16": (i32, [vp, vp, i64, vp]),
-    "cqlrec_topk_ws_bytes": (i64, [i64, i64, i32, i32]),
-    "cqlrec_score_topk": (i32, [vp, i64, vp, vp, i64, i32, vp, vp, vp, vp, i32, vp, i64, vp, vp, vp, vp]),
-    "cqlrec_topk_seen_form": (i32, [vp, i64, i64, i32, i32, C.POINTER(C.c_int32), vp]),
-    "cqlrec_score_topk_phase": (i32, [vp, i64, vp, vp, i64, i32, vp, vp, vp, vp, i32, vp, i64, vp, vp, vp, i32, vp]),
-    "cqlrec_item_norms": (i32, [vp, i64, i32, vp, vp]),
-    "cqlrec_item_knn_ws_bytes": (i64, [i64, i64, i32, i32]),
-    "cqlrec_item_knn": (i32, [vp, vp, i64, i32, vp, i64, vp, i64, i32, i32, vp, i64, vp, vp, vp, vp]),
-    "cqlrec_pairs_topk_ws_bytes": (i64, [i64, i64, i32, i32]),
-    "cqlrec_pairs_topk": (i32, [vp, vp, vp, i64, i32, vp, vp, vp, i64, vp, vp, i32, vp, i64, vp, vp, vp, vp, vp]),
-    "cqlrec_train_ws_bytes": (i64, [i32, i64, i32, i32]),
-    "cqlrec_train_step_fwd_bwd": (i32, [C.POINTER(TrainCtx), u64, vp, vp]),
-    "cqlrec_train_step_update": (i32, [C.POINTER(TrainCtx), u64, vp]),
-    "cqlrec_train_step_forward": (i32, [C.POINTER(TrainCtx), u64, vp, vp]),
-    "cqlrec_train_step_forward_after": (i32, [C.POINTER(TrainCtx), u64, vp, vp, vp]),
-    "cqlrec_train_step_forward_early_items": (i32, [C.POINTER(TrainCtx), u64, vp, vp, vp, vp]),
-    "cqlrec_train_step_backward_items": (i32, [C.POINTER(TrainCtx), u64, vp]),
-    "cqlrec_train_step_backward_rest": (i32, [C.POINTER(TrainCtx), u64, vp]),
-    "cqlrec_train_step_update_range": (i32, [C.POINTER(TrainCtx), u64, i64, i64, vp]),
-    "cqlrec_set_concurrency": (i32, [i32]),
-    "cqlrec_runtime_init": (i32, []),
-    "cqlrec_runtime_probe_count": (i32, []),
-    "cqlrec_aux_stream": (vp, [i32]),
-    "cqlrec_qhead_fused_ws_bytes": (i64, [i64, i64, i32]),
-    "cqlrec_qhead_fwd_lse_dh": (i32, [vp, i64, vp, vp, i64, i32, vp, i64, vp, vp, vp]),
-    "cqlrec_qhead_dh_finish": (i32, [vp, i64, i64, i32, vp, vp, vp, vp, C.c_float, vp, vp]),
-    "cqlrec_train_steps": (i32, [C.POINTER(TrainCtx), u64, i32, vp, vp]),
-    "cqlrec_train_views_get": (i32, [C.POINTER(TrainCtx), u64, C.POINTER(TrainViews)]),
-    "cqlrec_build_csr_ws_bytes": (i64, [i64]),
-    "cqlrec_build_csr": (i32, [vp, vp, vp, vp, i64, i64, vp, i64, vp, vp, vp, vp]),
-    "cqlrec_eval_topk_ws_bytes": (i64, [i64, i32]),
-    "cqlrec_eval_topk": (i32, [vp, i64, i32, vp, vp, vp, C.POINTER(i32), i32, vp, i64, vp, vp, vp]),
-    "cqlrec_recs_frame_to_block_ws_bytes": (i64, [i64, i64]),
-    "cqlrec_recs_frame_to_block": (i32, [vp, vp, vp, vp, i64, i64, i32, i32, vp, i64, vp, vp, vp, vp, vp]),
-    "cqlrec_recs_join_prev": (i32, [vp, vp, i64, vp, vp, i64, vp, vp]),
-    "cqlrec_recs_ncis_weights": (i32, [vp, vp, vp, i64, i32, i32, f64, vp]),
-    "cqlrec_eval_extras_ws_bytes": (i64, [i64, i32]),
-    "cqlrec_eval_extras": (i32, [vp, i64, i32, vp, vp, vp, vp, i32, vp, i64, vp, C.POINTER(i32), i32, vp, i64, vp, vp,
-                                 vp]),
-    "cqlrec_eval_item_user_counts_ws_bytes": (i64, [i64]),
-    "cqlrec_eval_item_user_counts": (i32, [vp, vp, i64, i64, vp, i64, vp, vp, vp]),
-    "cqlrec_eval_surprisal_weights": (i32, [vp, i64, i64, vp, vp]),
-    "cqlrec_eval_coverage": (i32, [vp, vp, i64, i32, i64, C.POINTER(i32), i32, vp, vp, vp]),
-    "cqlrec_eval_item_hist": (i32, [vp, i64, i32, i64, vp, vp]),
-    "cqlrec_split_rank_ws_bytes": (i64, [i64, i64]),
-    "cqlrec_split_rank": (i32, [vp, vp, i64, i64, i32, u64, vp, i64, vp, vp, vp, vp]),
-    "cqlrec_split_kth_key_ws_bytes": (i64, [i64]),
-    "cqlrec_split_kth_key": (i32, [vp, i64, i64, vp, i64, vp, vp]),
-    "cqlrec_split_new_users_ws_bytes": (i64, [i64]),
-    "cqlrec_split_new_users": (i32, [vp, vp, i64, i64, f64, vp, i64, vp, vp, vp]),
-    "cqlrec_split_pick_users_ws_bytes": (i64, [i64]),
-    "cqlrec_split_pick_users": (i32, [vp, i64, u64, i64, vp, i64, vp, vp]),
-    "cqlrec_split_classify": (i32, [i32, vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, f64, u64, vp, vp, vp]),
-    "cqlrec_split_filter_test_ws_bytes": (i64, [i64, i64]),
-    "cqlrec_split_filter_test": (i32, [vp, vp, vp, vp, i64, i64, i64, i32, i32, i32, vp, i64, vp, vp]),
-    "cqlrec_split_compact_ws_bytes": (i64, [i64]),
-    "cqlrec_split_compact": (i32, [vp, vp, i64, vp, i64, vp, vp, vp, vp]),
-    "cqlrec_prepare_rank_ws_bytes": (i64, [i64, i64]),
-    "cqlrec_prepare_rank": (i32, [vp, vp, vp, i64, i64, i64, vp, i64, vp, vp, vp]),
-    "cqlrec_prepare_count": (i32, [vp, i64, i64, vp, vp]),
-    "cqlrec_prepare_minmax": (i32, [vp, vp, i64, i64, vp, vp, vp]),
-    "cqlrec_prepare_keep": (i32, [i32, vp, vp, vp, vp, vp, vp, i64, i64, i32, i32, i64, i64, i32, f64, vp, vp]),
-    "cqlrec_prepare_compact_ws_bytes": (i64, [i64]),
-    "cqlrec_prepare_compact": (i32, [vp, i64, vp, i64, vp, vp, vp]),
-    "cqlrec_prepare_distinct_ws_bytes": (i64, [i64]),
-    "cqlrec_prepare_distinct": (i32, [vp, i64, vp, i64, vp, vp, vp]),
-    "cqlrec_prepare_sort_labels_ws_bytes": (i64, [i64]),
-    "cqlrec_prepare_sort_labels": (i32, [vp, i64, vp, i64, vp, vp, vp]),
-    "cqlrec_prepare_lookup": (i32, [vp, i64, vp, vp, i64, vp, vp, vp]),
-    "cqlrec_prepare_gather": (i32, [vp, i64, vp, i64, vp, vp, vp]),
-    "cqlrec_features_day": (i32, [vp, i64, i64, vp, vp]),
-    "cqlrec_features_segments_ws_bytes": (i64, [i64, i64]),
-    "cqlrec_features_segments": (i32, [vp, vp, i64, i64, vp, i64, vp, vp, vp]),
-    "cqlrec_features_segment_stats_ws_bytes": (i64, [i64, i64]),
-    "cqlrec_features_segment_stats": (i32, [vp, vp, vp, i64, i64, vp, i64, vp, vp]),
-    "cqlrec_features_segment_mean_ws_bytes": (i64, [i64, i64]),
-    "cqlrec_features_segment_mean": (i32, [i32, vp, vp, vp, vp, vp, vp, i64, f64, f64, i64, i64, vp, i64, vp, vp]),
-    "cqlrec_features_segment_distinct": (i32, [vp, vp, vp, vp, i64, i64, vp, vp]),
-    "cqlrec_features_pair_counts_ws_bytes": (i64, [i64]),
-    "cqlrec_features_pair_counts": (i32, [vp, vp, vp, vp, i64, i64, i64, vp, i64, vp, vp, vp, vp, vp]),
-    "cqlrec_features_block": (i32, [vp, vp, i64, vp, vp, i64, i32, vp, vp, i64, i32, C.POINTER(i32), i32,
-                                    C.POINTER(FeaturesPop), i32, i32, vp, vp]),
-    "cqlrec_neighbour_weights": (i32, [vp, vp, vp, vp, vp, i64, i64, i32, f64, f64, vp, vp]),
-    "cqlrec_neighbour_norms": (i32, [vp, vp, vp, i64, i64, vp, vp]),
-    "cqlrec_neighbour_count_ws_bytes": (i64, [i64]),
-    "cqlrec_neighbour_count": (i32, [vp, vp, i64, i64, vp, i64, vp, i64, vp, vp, vp, vp]),
-    "cqlrec_neighbour_topk_ws_bytes": (i64, [i64, i64, i64, i64, i32]),
-    "cqlrec_neighbour_topk": (i32, [i32, vp, vp, vp, i64, i64, vp, vp, vp, i64, i64, vp, vp, i64, i64, i32, vp, vp, f64, vp,
-                                    vp, vp, vp, i64, vp, vp, vp, vp]),
-    "cqlrec_neighbour_pair_scores": (i32, [vp, vp, i64, vp, vp, i64, vp, vp, vp, i64, vp, vp, vp]),
-    "cqlrec_rules_distinct": (i32, [vp, vp, vp, vp, i64, vp, vp]),
-    "cqlrec_rules_topk_ws_bytes": (i64, [i64, i64, i64, i32]),
-    "cqlrec_rules_topk": (i32, [vp, vp, vp, i64, i64, vp, vp, vp, i64, vp, vp, i64, i64, i32, i64, i64, vp, i64, vp, vp, vp,
-                                vp, vp, vp, vp]),
-    "cqlrec_als_gram_ws_bytes": (i64, [i64, i32]),
-    "cqlrec_als_gram": (i32, [vp, i64, i32, vp, i64, vp, vp]),
-    "cqlrec_als_normal_equations_ws_bytes": (i64, [i64, i64, i32]),
-    "cqlrec_als_normal_equations": (i32, [vp, vp, vp, i64, vp, i64, i32, vp, i32, f64, vp, i64, i64, vp, i64, vp, vp, vp, vp]),
-    "cqlrec_als_half_step_ws_bytes": (i64, [i64, i64, i32]),
-    "cqlrec_als_half_step": (i32, [vp, vp, vp, i64, vp, i64, i32, vp, i32, f64, f64, vp, i64, i64, vp, i64, vp, vp, vp, vp]),
-    "cqlrec_als_topk": (i32, [vp, i64, vp, vp, i64, vp, vp, i64, i32, vp, vp, vp, i32, vp, vp, vp, vp]),
-    "cqlrec_als_pair_scores": (i32, [vp, vp, i64, vp, vp, i64, vp, vp, i64, i32, vp, vp, vp]),
-    "cqlrec_dense_gemm_f64": (i32, [vp, i64, i32, vp, i64, i32, vp, i64, f64, f64, i64, i64, i64, vp, i64, vp]),
-    "cqlrec_dense_gram_ws_bytes": (i64, [i64, i64]),
-    "cqlrec_dense_gram": (i32, [vp, vp, vp, vp, vp, vp, i64, i64, i64, vp, i64, vp, vp]),
-    "cqlrec_dense_spd_inverse_ws_bytes": (i64, [i64]),
-    "cqlrec_dense_spd_inverse": (i32, [vp, i64, i64, f64, vp, i64, vp, vp, vp]),
-    "cqlrec_admm_iteration_ws_bytes": (i64, [i64]),
-    "cqlrec_admm_iteration": (i32, [vp, vp, vp, vp, i64, f64, f64, vp, i64, vp, vp]),
-    "cqlrec_admm_compact": (i32, [vp, i64, i64, vp, vp, vp, vp]),
-    "cqlrec_slim_fit_ws_bytes": (i64, [i64]),
-    "cqlrec_slim_fit": (i32, [vp, i64, i64, i64, f64, f64, f64, i32, i64, i64, vp, i64, vp, i64, vp, vp, vp, vp]),
-    "cqlrec_prof_enable": (i32, [i32]),
-    "cqlrec_prof_select": (i32, [C.c_uint32]),
-    "cqlrec_debug_marks_enable": (i32, [i32]),
-    "cqlrec_debug_marks_read": (i32, [C.POINTER(C.c_float)]),
-    "cqlrec_prof_read": (i32, [C.POINTER(C.c_double), C.POINTER(i64)]),
-}
-
-PHASES = ("sample", "gather_fwd", "encoder_fwd", "qhead_lse", "qhead_argmax", "qhead_bwd_dh", "qhead_bwd_de",
-          "qhead_small", "encoder_bwd", "gather_bwd", "adam", "topk_tilemax", "topk_select")
+# Everything include/cqlrec.h declares, read from it (_header.py): every `#define CQLREC_X n` as the module attribute X
+# (ABI_VERSION and AUX_STREAMS among them), the structs as ctypes Structures, and SIGNATURES = {symbol: (restype,
+# argtypes)} -- the table `load` binds and `_device.Engine` reads which arguments are device pointers from.
+_H = _header.read(mixins={"Layout": _LayoutMethods})
+_K = _H.constants
+if _K["EVAL_EXTRAS"] != len(EVAL_EXTRAS):
+    raise CqlrecError(f"cqlrec.h has {_K['EVAL_EXTRAS']} extra metrics, _native.EVAL_EXTRAS names {len(EVAL_EXTRAS)}")
+globals().update({k: v for k, v in _K.items() if k != "EVAL_EXTRAS"})
+Layout, TrainCtx, TrainViews, FeaturesPop = (_H.structs[n] for n in ("Layout", "TrainCtx", "TrainViews", "FeaturesPop"))
+SIGNATURES = _H.signatures
+PHASES = tuple(k[len("PH_"):].lower() for k in list(_H.enum)[:_H.enum["PH_COUNT"]])
+NEIGHBOUR_WEIGHTINGS = {None: _K["NEIGHBOUR_WEIGHT_NONE"], "tf_idf": _K["NEIGHBOUR_WEIGHT_TF_IDF"],
+                        "bm25": _K["NEIGHBOUR_WEIGHT_BM25"]}
 
 
 def prof_read():
@@ -245,10 +59,6 @@ def prof_read():
     cnt = (i64 * len(PHASES))()
     check(load().cqlrec_prof_read(ms, cnt), "prof_read")
     return {p: (float(ms[i]), int(cnt[i])) for i, p in enumerate(PHASES)}
-
-
-class CqlrecError(RuntimeError):
-    pass
 
 
 def lib_path() -> Path:
@@ -274,13 +84,12 @@ def load() -> C.CDLL:
         except AttributeError as exc:  # pragma: no cover
             raise CqlrecError(f"{_LIB_PATH} does not export {name}; rebuild it") from exc
         fn.restype, fn.argtypes = res, args
-    if lib.cqlrec_abi_version() != ABI_VERSION:
-        raise CqlrecError(f"libcqlrec ABI {lib.cqlrec_abi_version()} != expected {ABI_VERSION}; rebuild it")
+    if lib.cqlrec_abi_version() != _K["ABI_VERSION"]:                # the .so against the header it ships with
+        raise CqlrecError(f"libcqlrec ABI {lib.cqlrec_abi_version()} != expected {_K['ABI_VERSION']}; rebuild it")
     _lib = lib
     return lib
 
 
-AUX_STREAMS = 2
 _aux_cache: dict = {}
 
 

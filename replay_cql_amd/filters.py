@@ -47,13 +47,13 @@ from typing import Optional, Union
 import torch
 
 from . import _log as L
+from . import _native as N
 from . import _prepare as P
 from .splitters import _instant_ns, _threshold_key
 
 __all__ = ["filter_by_min_count", "filter_out_low_ratings", "take_num_user_interactions", "take_num_days_of_user_hist",
            "take_time_period", "take_num_days_of_global_hist"]
 
-_MIN_COUNT, _MIN_VALUE, _NUM_INTERACTIONS, _DAYS_USER, _DAYS_GLOBAL, _PERIOD = range(6)
 DAY_S = 86400
 
 
@@ -108,7 +108,7 @@ def filter_by_min_count(data_frame, num_entries: int, group_by: str = "user_idx"
     (group, n_groups), = L.dense_ids(lg, [group_by])
     prep = P.Prep(lg.device)
     count = prep.count(group, n_groups)
-    rows = prep.compact(prep.keep(_MIN_COUNT, lg.n, group=group, count=count,
+    rows = prep.compact(prep.keep(N.KEEP_MIN_COUNT, lg.n, group=group, count=count,
                                   n=L.clip64(math.ceil(num_entries))))
     diff = (lg.n - rows.numel()) / lg.n
     (_logger().warning if diff > 0.5 else _logger().info)("current threshold removes %s%% of data", diff)
@@ -124,7 +124,7 @@ def filter_out_low_ratings(data_frame, value: float, rating_column="relevance", 
     if lg.n == 0:
         return _result(lg, _no_rows(lg), return_rows)
     prep = P.Prep(lg.device)
-    rows = prep.compact(prep.keep(_MIN_VALUE, lg.n, value=L.float_column(lg, rating_column), x=value))
+    rows = prep.compact(prep.keep(N.KEEP_MIN_VALUE, lg.n, value=L.float_column(lg, rating_column), x=value))
     return _result(lg, rows, return_rows)
 
 
@@ -146,7 +146,7 @@ def take_num_user_interactions(log, num_interactions: int = 10, first: bool = Tr
     (user, n_users), (item, n_items) = ids[0], (ids[1] if item_col is not None else (None, 0))
     prep = P.Prep(lg.device)
     rank, count = prep.rank(user, n_users, lg.key(date_col), item, n_items)
-    rows = prep.compact(prep.keep(_NUM_INTERACTIONS, lg.n, group=user, rank=rank, count=count, n=n, first=bool(first)))
+    rows = prep.compact(prep.keep(N.KEEP_NUM_INTERACTIONS, lg.n, group=user, rank=rank, count=count, n=n, first=bool(first)))
     return _result(lg, rows, return_rows)
 
 
@@ -168,7 +168,7 @@ def take_num_days_of_user_hist(log, days: int = 10, first: bool = True, date_col
     if lg.n == 0:
         return _result(lg, _no_rows(lg), return_rows)
     (user, n_users), = L.dense_ids(lg, [user_col])
-    rows = _days(lg, P.Prep(lg.device), _DAYS_USER, lg.key(date_col), user, n_users, days, bool(first))
+    rows = _days(lg, P.Prep(lg.device), N.KEEP_DAYS_USER, lg.key(date_col), user, n_users, days, bool(first))
     return _result(lg, rows, return_rows)
 
 
@@ -188,7 +188,7 @@ def take_time_period(log, start_date: Optional[Union[str, datetime]] = None,
     lo = L.I64_MIN if start_date is None else L.clip64(_threshold_key(start_date, lg.ts_kind))
     hi = 0 if end_date is None else L.clip64(_threshold_key(end_date, lg.ts_kind))
     prep = P.Prep(lg.device)
-    rows = prep.compact(prep.keep(_PERIOD, lg.n, key=key, lo=lo, hi=hi, open_end=end_date is None))
+    rows = prep.compact(prep.keep(N.KEEP_PERIOD, lg.n, key=key, lo=lo, hi=hi, open_end=end_date is None))
     return _result(lg, rows, return_rows)
 
 
@@ -201,5 +201,5 @@ def take_num_days_of_global_hist(log, duration_days: int, first: bool = True, da
     lg = L.open_log(src, "take_num_days_of_global_hist")
     if lg.n == 0:
         return _result(lg, _no_rows(lg), return_rows)
-    rows = _days(lg, P.Prep(lg.device), _DAYS_GLOBAL, lg.key(date_column), None, 1, days, bool(first))
+    rows = _days(lg, P.Prep(lg.device), N.KEEP_DAYS_GLOBAL, lg.key(date_column), None, 1, days, bool(first))
     return _result(lg, rows, return_rows)

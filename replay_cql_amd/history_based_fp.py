@@ -189,21 +189,21 @@ class LogStatFeaturesProcessor(EmptyFeatureProcessor):
         u, i = sides["u"], sides["i"]
         if self.calc_relevance_based:
             ist = i["stats"]
-            u["cols"]["abnormality"] = feat.segment_mean(feat.N.FEAT_MEAN_ABNORMALITY, u["perm"], u["offsets"], n_users,
+            u["cols"]["abnormality"] = feat.segment_mean(feat.N.FEATURES_MEAN_ABNORMALITY, u["perm"], u["offsets"], n_users,
                                                          item, ist[:, 1], value=rel)
             std_present = ist[:, 2][i["count"] > 0]
             lo_s, hi_s = torch.stack([std_present.min(), std_present.max()]).cpu().tolist()
             if hi_s - lo_s != 0:
                 self._has_cr = True
-                u["cols"]["abnormalityCR"] = feat.segment_mean(feat.N.FEAT_MEAN_ABNORMALITY_CR, u["perm"], u["offsets"],
+                u["cols"]["abnormalityCR"] = feat.segment_mean(feat.N.FEATURES_MEAN_ABNORMALITY_CR, u["perm"], u["offsets"],
                                                                n_users, item, ist[:, 1], ist[:, 2], value=rel,
                                                                min_std=lo_s, max_std=hi_s)
         # the log counts enter the cross means as they stand in the tables: finite for every id a row names
         ilog = i["cols"]["i_log_num_interact"].contiguous()
         ulog = u["cols"]["u_log_num_interact"].contiguous()
-        u["cols"]["u_mean_i_log_num_interact"] = feat.segment_mean(feat.N.FEAT_MEAN_GATHER, u["perm"], u["offsets"],
+        u["cols"]["u_mean_i_log_num_interact"] = feat.segment_mean(feat.N.FEATURES_MEAN_GATHER, u["perm"], u["offsets"],
                                                                    n_users, item, ilog)
-        i["cols"]["i_mean_u_log_num_interact"] = feat.segment_mean(feat.N.FEAT_MEAN_GATHER, i["perm"], i["offsets"],
+        i["cols"]["i_mean_u_log_num_interact"] = feat.segment_mean(feat.N.FEATURES_MEAN_GATHER, i["perm"], i["offsets"],
                                                                    n_items, user, ulog)
         self._ucount, self._icount = u["count"], i["count"]
         self._udates, self._idates = u.get("dates"), i.get("dates")
@@ -254,12 +254,12 @@ class LogStatFeaturesProcessor(EmptyFeatureProcessor):
     def _block_parts(self):
         """(colmap entries, names) of this processor's share of a block"""
         from . import _native as N
-        cm = [(N.FEAT_COL_USER, j, 0) for j in range(len(self._unames))]
-        cm += [(N.FEAT_COL_ITEM, j, 0) for j in range(len(self._inames))]
-        cm += [(N.FEAT_COL_NA_USER, 0, 0), (N.FEAT_COL_NA_ITEM, 0, 0),
-               (N.FEAT_COL_DIFF_USER, self._unames.index("u_log_num_interact"),
+        cm = [(N.FEATURES_COL_USER, j, 0) for j in range(len(self._unames))]
+        cm += [(N.FEATURES_COL_ITEM, j, 0) for j in range(len(self._inames))]
+        cm += [(N.FEATURES_COL_NA_USER, 0, 0), (N.FEATURES_COL_NA_ITEM, 0, 0),
+               (N.FEATURES_COL_DIFF_USER, self._unames.index("u_log_num_interact"),
                 self._inames.index("i_mean_u_log_num_interact")),
-               (N.FEAT_COL_DIFF_ITEM, self._inames.index("i_log_num_interact"),
+               (N.FEATURES_COL_DIFF_ITEM, self._inames.index("i_log_num_interact"),
                 self._unames.index("u_mean_i_log_num_interact"))]
         names = self._unames + self._inames + ["na_u_log_features", "na_i_log_features", "u_i_log_num_interact_diff",
                                                "i_u_log_num_interact_diff"]
@@ -428,7 +428,7 @@ def _plan(log_proc, pop_procs, lg=None):
     for proc in pop_procs:
         tabs, nms = proc._pops(lg)
         for t in tabs:
-            colmap += [(N.FEAT_COL_POP, len(pops), 0), (N.FEAT_COL_POP_NA, len(pops), 0)]
+            colmap += [(N.FEATURES_COL_POP, len(pops), 0), (N.FEATURES_COL_POP_NA, len(pops), 0)]
             pops.append(t)
         names += nms
     return colmap, names, pops

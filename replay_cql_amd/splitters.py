@@ -37,6 +37,7 @@ from typing import Optional, Union
 import numpy as np
 import torch
 
+from . import _native as N
 from . import data as D
 from ._device import Engine, Ws
 from ._log import _Log, dense_ids, float_column
@@ -44,7 +45,6 @@ from ._log import _Log, dense_ids, float_column
 __all__ = ["Splitter", "UserSplitter", "DateSplitter", "RandomSplitter", "NewUsersSplitter", "ColdUserRandomSplitter",
            "k_folds"]
 
-_QUANTITY, _PROPORTION, _DATE, _RANDOM_ROW, _RANDOM_USER, _NEW_USERS, _FOLD = range(7)
 _U64 = (1 << 64) - 1
 
 
@@ -63,9 +63,9 @@ def _check_test_size(test_size) -> None:
 
 def _item_rule(item_test_size) -> int:
     if 0 <= item_test_size < 1.0:
-        return _PROPORTION
+        return N.SPLIT_PROPORTION
     if item_test_size >= 1 and _is_int(item_test_size):
-        return _QUANTITY
+        return N.SPLIT_QUANTITY
     raise ValueError(f"`test_size` value must be [0, 1) or a positive integer; test_size={item_test_size}")
 
 
@@ -250,9 +250,9 @@ class UserSplitter(Splitter):
         if self.user_test_size is not None:
             n_pick = self._test_user_count(int(present.item()))         # argument validation: one small sync
             test_user = run.pick_users(count, seed, n_pick)
-        if rule == _QUANTITY:
-            return run.classify(_QUANTITY, rank=rank, test_user=test_user, n=int(self.item_test_size))
-        return run.classify(_PROPORTION, rank=rank, count=count, test_user=test_user, frac=float(self.item_test_size))
+        if rule == N.SPLIT_QUANTITY:
+            return run.classify(N.SPLIT_QUANTITY, rank=rank, test_user=test_user, n=int(self.item_test_size))
+        return run.classify(N.SPLIT_PROPORTION, rank=rank, count=count, test_user=test_user, frac=float(self.item_test_size))
 
 
 class DateSplitter(Splitter):
@@ -291,7 +291,7 @@ class DateSplitter(Splitter):
         else:
             thr = torch.tensor([_threshold_key(self.test_start, run.log.ts_kind)], dtype=torch.int64,
                                    device=run.dev)
-        return run.classify(_DATE, key=key, threshold=thr)
+        return run.classify(N.SPLIT_DATE, key=key, threshold=thr)
 
 
 class RandomSplitter(Splitter):
@@ -314,7 +314,7 @@ class RandomSplitter(Splitter):
 
     def _core_split(self, run: _Run):
         _check_test_size(self.test_size)
-        return run.classify(_RANDOM_ROW, frac=1 - self.test_size, seed=_seed64(self.seed))
+        return run.classify(N.SPLIT_RANDOM_ROW, frac=1 - self.test_size, seed=_seed64(self.seed))
 
 
 class NewUsersSplitter(Splitter):
@@ -339,7 +339,7 @@ class NewUsersSplitter(Splitter):
         _check_test_size(self.test_size)
         key = run.log.key(self.date_col)
         start, thr = run.new_users(key, self.test_size)
-        return run.classify(_NEW_USERS, key=key, user_start=start, threshold=thr)
+        return run.classify(N.SPLIT_NEW_USERS, key=key, user_start=start, threshold=thr)
 
 
 class ColdUserRandomSplitter(Splitter):
@@ -362,7 +362,7 @@ class ColdUserRandomSplitter(Splitter):
 
     def _core_split(self, run: _Run):
         _check_test_size(self.test_size)
-        return run.classify(_RANDOM_USER, frac=1 - self.test_size, seed=_seed64(self.seed))
+        return run.classify(N.SPLIT_RANDOM_USER, frac=1 - self.test_size, seed=_seed64(self.seed))
 
 
 def k_folds(log, n_folds: Optional[int] = 5, seed: Optional[int] = None, splitter: Optional[str] = "user",
@@ -383,5 +383,5 @@ def k_folds(log, n_folds: Optional[int] = 5, seed: Optional[int] = None, splitte
     run = _Run(lg, user_col, None, False)
     rank, _, _ = run.rank(None, True, _seed64(seed))
     for fold in range(n_folds):
-        train_rows, test_rows = run.compact(*run.classify(_FOLD, rank=rank, n=n_folds, fold=fold))
+        train_rows, test_rows = run.compact(*run.classify(N.SPLIT_FOLD, rank=rank, n=n_folds, fold=fold))
         yield lg.take(train_rows), lg.take(test_rows)

@@ -83,7 +83,7 @@ def main():
     N.check(lib.cqlrec_debug_marks_enable(1))
     core.train_steps(64)
     torch.cuda.synchronize()
-    ms = (C.c_float * 12)()
+    ms = (C.c_float * N.DEBUG_MARKS)()
     N.check(lib.cqlrec_debug_marks_read(ms))
     N.check(lib.cqlrec_debug_marks_enable(0))
     names = ("loss", "dH", "dE_out", "enc+gather bwd", "adam E_in", "adam E_out", "next prologue", "next LSE", "next loss", "enc dx", "gather bwd",
